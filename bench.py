@@ -389,6 +389,40 @@ def selftest_launch(rank, world):
     dist.destroy_process_group()
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, states, stats, extra=None, epoch0_ns=0):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, one DIR/<name>.npy per array, all float64: the final
+    states (every f64 field, the epoch as nanoseconds past `epoch0_ns` - exact below 2**53 - and the step hint), the per-trajectory
+    statistics, and `extra` (per-trajectory arrays of the path, or whole-ensemble ones such as the moments).  The inputs are
+    seeded, so two builds given the same arguments can be compared array for array.  Arrays indexed by trajectory share a fixed,
+    seeded sample of the trajectories when everything would pass DUMP_LIMIT_BYTES (the indices in sample_index.npy)."""
+    n = states.n
+    per = {f: getattr(states, f) for f in _abi.F64_FIELDS}
+    per["epoch_offset_ns"] = states.epoch_ns - np.int64(epoch0_ns)
+    per["step_ns"] = states.step_ns
+    for f in ("status", "last_attempts", "last_step_ns", "last_error", "n_accepted", "n_rejected", "n_evals"):
+        per[f] = getattr(stats, f)
+    whole = {}
+    for k, v in (extra or {}).items():
+        v = np.asarray(v)
+        (per if v.ndim >= 1 and v.shape[0] == n and k != "ensemble_moments" else whole)[k] = v
+    per_traj = sum(np.asarray(v)[:1].size for v in per.values()) * 8
+    room = DUMP_LIMIT_BYTES - sum(np.asarray(v).size for v in whole.values()) * 8 - n * 8
+    index = None
+    if per_traj * n > room:
+        m = max(1, room // (per_traj + 8))
+        index = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        whole["sample_index"] = index
+    os.makedirs(path, exist_ok=True)
+    for k, v in per.items():
+        v = np.asarray(v)
+        np.save(os.path.join(path, k + ".npy"), (v if index is None else v[index]).astype(np.float64))
+    for k, v in whole.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray(v).astype(np.float64))
+
+
 def single_process(args, w):
     """`--single-process`: ONE process drives every device through the C symbol `nyx_hip_propagate_batch_sharded` (one context
     and one host thread per device, contiguous index shards, results in place; host buffers: the staging copies are inside
@@ -411,6 +445,8 @@ def single_process(args, w):
     for _ in range(args.steps):
         out, st = nx.propagate_sharded(ctxs, full, dur_ns)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, st, epoch0_ns=int(full.epoch_ns[0]))
     if (st.status != 0).any():
         raise SystemExit(f"{int((st.status != 0).sum())} trajectories failed")
     k_ms = [c.last_kernel_ms() for c in ctxs]
@@ -574,6 +610,8 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="initialise the process group and run the all-gather / all-reduce of every step even with ONE rank "
                          "(exercises the RCCL path on a 1-GPU box; the line says so in `launch`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; with N ranks DIR/rank<r>/)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense-output", action="store_true", help="skip the extra launch with the trajectories recorded")
@@ -581,6 +619,8 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the one-pass measurements of configs 3, 4, 5 and of the full-chip launch that the headline run carries in `other_configs`")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- how many ranks, and who starts them.  Under torchrun (the driver's N > 1 launch) WORLD_SIZE is set and must agree
     # with --gpus; started as one process with --gpus N > 1 the ranks are started HERE (spawn_ranks) - `--gpus N` always
@@ -755,6 +795,20 @@ def main():
         dist.all_gather(kall, torch.tensor([k_ms, gather_ms], dtype=torch.float64, device=red))
         per_rank_kernel_ms = [float(t[0].item()) for t in kall]
         gather_ms = max(float(t[1].item()) for t in kall)
+    if args.dump_outputs:
+        # before any further launch on these buffers (host call, dense output): the last timed step's results
+        where = args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}")
+        if not w["stm"]:
+            got, got_st = _abi.StateBatch(n), _abi.StatsBatch(n)
+            for f in ["epoch_ns", "step_ns", *_abi.F64_FIELDS]:
+                getattr(got, f)[:] = tout[f].cpu().numpy()
+            for f in tst:
+                getattr(got_st, f)[:] = tst[f].cpu().numpy()
+            dump_outputs(where, got, got_st, {"ensemble_moments": mom.cpu().numpy()}, epoch0_ns=int(shard.epoch_ns[0]))
+        else:
+            r = last["res"]
+            dump_outputs(where, r.states, r.stats, {"stm": r.states.stm, "covar": r.covar, "state_deviation": r.state_deviation,
+                                                    "n_updates": r.n_updates}, epoch0_ns=int(shard.epoch_ns[0]))
 
     if not w["stm"]:
         n_evals = int(tst["n_evals"].sum().item())

@@ -119,3 +119,51 @@ def test_rccl_refuses_shared_device_with_a_message():
         pytest.skip("needs a box where two ranks must share a device")
     p, line = _run(["--gpus", "2", "--oversubscribe", *SMALL])
     assert p.returncode != 0 and line is None
+
+
+def test_dump_outputs_writes_float64_and_keeps_under_the_limit(tmp_path, monkeypatch):
+    """`--dump-outputs`: one float64 .npy per array; past the size limit a fixed, seeded sample of trajectories, the same every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from nyx_amd import _abi
+    n = 1000
+    st, stats = _abi.StateBatch(n), _abi.StatsBatch(n)
+    st.x_km[:] = np.arange(n)
+    st.epoch_ns[:] = 757_339_200 * 10**9 + np.arange(n)
+    stats.n_evals[:] = 3 * np.arange(n)
+    mom = np.linspace(0.0, 1.0, 55)
+    bench.dump_outputs(str(tmp_path / "all"), st, stats, {"ensemble_moments": mom}, epoch0_ns=757_339_200 * 10**9)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(got) >= {*_abi.F64_FIELDS, "epoch_offset_ns", "step_ns", "status", "n_evals", "ensemble_moments"}
+    assert "sample_index" not in got and all(v.dtype == np.float64 for v in got.values())
+    assert (got["x_km"] == np.arange(n)).all() and (got["epoch_offset_ns"] == np.arange(n)).all() and (got["ensemble_moments"] == mom).all()
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 * 1024)
+    for k in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / k), st, stats, {"ensemble_moments": mom}, epoch0_ns=757_339_200 * 10**9)
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 * 1024 + 128 * len(a)   # (+ the .npy headers)
+    idx = a["sample_index"].astype(np.int64)
+    assert 0 < len(idx) < n and (np.diff(idx) > 0).all()
+    assert (a["x_km"] == idx).all() and (a["n_evals"] == 3 * idx).all() and (a["ensemble_moments"] == mom).all()
+    assert all((a[k] == b[k]).all() for k in a)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_whatever_the_step_count(tmp_path):
+    """Same arguments, same inputs: the last timed step's outputs do not depend on how many steps ran before it."""
+    import numpy as np
+    got = []
+    for k, steps in (("one", "1"), ("two", "2")):
+        args = list(SMALL)
+        args[args.index("--steps") + 1] = steps
+        p, line = _run(["--gpus", "1", *args, "--dump-outputs", str(tmp_path / k)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert line["steps"] == int(steps) and line["ms_per_step"] > 0
+        got.append({q.stem: np.load(q) for q in (tmp_path / k).iterdir()})
+    a, b = got
+    assert a["x_km"].shape == (256,) and (a["status"] == 0).all() and (a["epoch_offset_ns"] == 900 * 10**9).all()
+    assert a["ensemble_moments"][0] == 256.0
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)

@@ -75,10 +75,8 @@ def test_shadr_loader(tmp_path):
 
 def test_fixture_matches_reference_file_when_present():
     """nyx_amd/data/jgm3_70x70.f64 == what the C++ loader reads from the reference's own JGM3.cof.gz
-    (only runnable where /root/reference exists; the GPU box uses the committed fixture)."""
-    src = "/root/reference/data/01_planetary/JGM3.cof.gz"
-    if not os.path.exists(src):
-        pytest.skip("reference checkout not present")
+    (kept verbatim as tests/golden/JGM3.cof.gz)."""
+    src = os.path.join(ROOT, "tests", "golden", "JGM3.cof.gz")
     g = nx.GravityFieldData.from_cof(src, 70, 70, True, FRAME)  # reference io/gravity.rs:533-567 loads 50x50 of the same file
     f = nx.GravityFieldData.from_packed_file(JGM3_PATH, FRAME)
     assert (g.degree, g.order) == (70, 70) == (f.degree, f.order)
