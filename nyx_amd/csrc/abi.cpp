@@ -112,10 +112,6 @@ struct nyx_hip_ctx {
     size_t rs_cap[3] = {0, 0, 0};
     ColHdr *d_rs_cols[3] = {nullptr, nullptr, nullptr};
     bool rs_dirty = true;
-    // experiment knobs of the helper dealing (environment, only with NYX_HIP_TUNING_ENV: tools/sweep.py)
-    double coop_fast_weight = 4.0 / 3.0;  // speed of a helper column wave on a SIMD that hosts three of them (beside the producer / the answering wave)
-    double coop_start_rows = 4.0;         // what the start of one more column on a helper wave is charged, in rows
-    int coop_deal = 1;                    // 1: balanced dealing (build_schedule), 0: the longest columns, one per wave
     ColHdr *d_cols = nullptr;
     double *d_records = nullptr;
     std::vector<int32_t> col_len;  // rows per column (index = c)
@@ -131,9 +127,6 @@ struct nyx_hip_ctx {
     WKey last_key = WKey(0, 0, 0, 0);      // shape of the last launch
     DevArrays cal;                         // scratch outputs of the calibration launches
     bool block_schedule = true;  // one contiguous run of columns per wave where the owner streams the table (fill_schedule)
-    bool fit_big = false;        // (tools: NYX_HIP_FIT_BIG - the free-order placement for the large cooperative shape too)
-    bool fit_quad = false;       // (tools: NYX_HIP_FIT_QUAD - ... and for the sixteen-wave quad STM shape)
-    bool fit_solo = false;       // (tools: NYX_HIP_FIT_SOLO - ... and for workgroups that walk every column themselves)
     bool fit_partition = true;   // ... placed along the column list in a free wave order so that every wave meets its target (fill_schedule)
     bool block_force = false;
     int coop_parts = 1;  // sub-jobs per evaluation of the schedules in host_cfg (1, or 2: two helper workgroups per owner and evaluation; fan-out: 2 .. DEV_FAN_MAX)
@@ -141,7 +134,6 @@ struct nyx_hip_ctx {
     bool coop_fan = false;  // the schedules in host_cfg are those of the fan-out mode: coop_parts DEDICATED helper workgroups per owner (small shards, see launch())
     int forced_quad = -1;  // STM layout: -1 = by ensemble size, 0 = 64 trajectories x D3 per workgroup, 1 = quad layout (16 x 4 lanes, D1)
     double role_handicap[3] = {0.0, 0.0, 0.0};  // integrator, almanac, perturbations (harmonics-term units)
-    int role_place[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, role_place_sums = -1, role_place_twobody = -1;  // (tools only: ExpKnobs)
     DevArrays in, out;
     int64_t *d_prof = nullptr;
     CoopBox *d_coop = nullptr;  // cooperative-mode mailboxes, one per trajectory-owning workgroup, then the packed scan words
@@ -282,32 +274,16 @@ static double ns_to_seconds_host(int64_t ns) {  // Duration::to_seconds for |ns|
     return (double)q + (double)r * 1e-9;
 }
 
+// tuning.debug_flags that still select something (nyx_hip.h); nyx_hip_ctx_create refuses every other bit
+static constexpr uint32_t kLiveDebugFlags = 0x100 | 0x200 | 0x400 | 0x800 | 0x4000 | 0x8000 | 0x10000 | 0x80000 | 0x100000 | 0x2000000 |
+                                            0x4000000 | 0x8000000 | 0x20000000;
+
 // config.tuning -> the context's copy.  The process environment is consulted ONLY when NYX_HIP_TUNING_ENV is set (the A/B
 // tools of this repository: tools/*.py, tools/*.sh): a library behind a C-ABI takes its switches through its config struct.
-struct ExpKnobs {  // experiment knobs of tools/sweep.py that have no field in nyx_hip_tuning_t (the helper dealing, round 5); < 0 / 0: unset
-    double fast_weight = 0.0, start_rows = -1.0;
-    int deal = -1;
-    int place[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // role fan-out: the wave of the k-th duty (duties heaviest first), assign_roles
-    int place_sums = -1, place_twobody = -1;         // ... and of the two offloaded integrator pieces
-    bool fit_big = false, fit_quad = false, fit_solo = false;  // the free-order column placement for the large cooperative / the quad STM / the solo shape too
-};
-static nyx_hip_tuning_t resolve_tuning(const nyx_hip_tuning_t *t, ExpKnobs *xk = nullptr) {
+static nyx_hip_tuning_t resolve_tuning(const nyx_hip_tuning_t *t) {
     nyx_hip_tuning_t r = NYX_HIP_TUNING_DEFAULT;
     if (t) r = *t;
     if (!std::getenv("NYX_HIP_TUNING_ENV")) return r;
-    if (xk) {
-        if (const char *e = std::getenv("NYX_HIP_COOP_FASTW")) xk->fast_weight = std::atof(e);
-        if (const char *e = std::getenv("NYX_HIP_COOP_START")) xk->start_rows = std::atof(e);
-        if (const char *e = std::getenv("NYX_HIP_COOP_DEAL")) xk->deal = std::atoi(e);
-        if (const char *e = std::getenv("NYX_HIP_ROLE_PLACE")) {
-            const char *q = e;
-            for (int k = 0; k < 8 && *q; ++k) { xk->place[k] = (int)std::strtol(q, (char **)&q, 10); if (*q == ',') ++q; }
-        }
-        if (const char *e = std::getenv("NYX_HIP_ROLE_OFFLOAD")) (void)std::sscanf(e, "%d,%d", &xk->place_sums, &xk->place_twobody);
-        xk->fit_big = std::getenv("NYX_HIP_FIT_BIG") != nullptr;
-        xk->fit_quad = std::getenv("NYX_HIP_FIT_QUAD") != nullptr;
-        xk->fit_solo = std::getenv("NYX_HIP_FIT_SOLO") != nullptr;
-    }
     auto geti = [](const char *name, int32_t &dst) { if (const char *e = std::getenv(name)) dst = (int32_t)std::strtol(e, nullptr, 0); };
     auto getd = [](const char *name, double &dst) { if (const char *e = std::getenv(name)) dst = std::atof(e); };
     int32_t cal = -1;
@@ -527,7 +503,7 @@ static bool fill_schedule(const nyx_hip_ctx *ctx, DevSched &sd, int n_waves, con
         // Same box, product kernel, 24 h: 625.0 ms linear partition, 617.0 free order with the old table, 614.0 with this one.
         static const double model_coop_fit[16] = {1.00, 1.413, 0.549, 1.95, 1.83, 1.48, 1.40, 1.23, 1.04, 0.88, 0.85, 0.62, 0.50, 0.36, 0.34, 0.16};
         const bool blk = ctx->block_schedule && n_waves == DEV_MAX_WAVES && !ctx->sched_quad && ((ctx->host_cfg.harm_feed & 1) || ctx->block_force);
-        fit = (blk && (!all_columns || ctx->fit_solo) && (ctx->host_cfg.n_cols <= 96 || ctx->fit_big) && ctx->fit_partition) || (ctx->fit_quad && ctx->sched_quad && n_waves == DEV_MAX_WAVES);
+        fit = blk && !all_columns && ctx->host_cfg.n_cols <= 96 && ctx->fit_partition;
         const double *model = ctx->sched_quad ? model_quad
                               : (blk ? (all_columns ? model_solo_blk : (ctx->host_cfg.n_cols > 96 ? model_coop_big_blk : (fit ? model_coop_fit : model_coop_blk)))
                                      : (all_columns ? model_solo : model_coop));
@@ -765,7 +741,6 @@ static void assign_roles(nyx_hip_ctx *ctx, int n_waves, bool fanout, double *hc)
         bool taken[DEV_MAX_WAVES] = {true};
         std::sort(duties.begin(), duties.end(), [](const Duty &a, const Duty &b) { return a.cost > b.cost; });
         bool placed_all = true;
-        int duty_no = 0;
         for (const Duty &d : duties) {
             int best_w = -1;
             double best_load = 1e300;
@@ -774,8 +749,6 @@ static void assign_roles(nyx_hip_ctx *ctx, int n_waves, bool fanout, double *hc)
                 for (int k = sd; k < n_waves; k += 4) if (!taken[k]) { w = k; break; }
                 if (w >= 0 && simd_load[sd] < best_load) { best_load = simd_load[sd]; best_w = w; }
             }
-            if (duty_no < 8 && ctx->role_place[duty_no] > 0 && ctx->role_place[duty_no] < n_waves && !taken[ctx->role_place[duty_no]]) best_w = ctx->role_place[duty_no];  // (tools: NYX_HIP_ROLE_PLACE)
-            ++duty_no;
             if (best_w < 0) { placed_all = false; break; }
             taken[best_w] = true;
             simd_load[best_w % 4] += d.cost;
@@ -795,8 +768,6 @@ static void assign_roles(nyx_hip_ctx *ctx, int n_waves, bool fanout, double *hc)
                     if (w1 < 0 || spare(w) < spare(w1)) { w2 = w1; w1 = w; }
                     else if (w2 < 0 || spare(w) < spare(w2)) w2 = w;
                 }
-                if (ctx->role_place_sums > 0 && ctx->role_place_sums < n_waves && dc.role_kind[ctx->role_place_sums] == DEV_ROLE_ALMANAC) w1 = ctx->role_place_sums;  // (tools: NYX_HIP_ROLE_OFFLOAD)
-                if (ctx->role_place_twobody > 0 && ctx->role_place_twobody < n_waves && dc.role_kind[ctx->role_place_twobody] == DEV_ROLE_ALMANAC) w2 = ctx->role_place_twobody;
                 if (w1 >= 0) {
                     if (w2 < 0) w2 = w1;
                     dc.role_mask[w1] |= DEV_ROLE_SUMS; hc[w1] += 4.0;
@@ -837,10 +808,10 @@ static void assign_roles(nyx_hip_ctx *ctx, int n_waves, bool fanout, double *hc)
     // ONE almanac wave (the sixteen-wave column shapes): distinct-segment units pay here too - Earth -> EMB sits on the chain of
     // every body of an Earth-centred run and was evaluated once per BODY per stage (five Chebyshev evaluations for Sun + Moon where
     // four segments are distinct).  The wave evaluates every distinct segment once, the readers sum the chains (ed_body(): the same
-    // additions in the same order, bit-identical).  (0x1000: A/B switch, same results)
+    // additions in the same order, bit-identical).
     int chain_evals = 0;
     for (int sl = 0; sl < dc.n_slots; ++sl) chain_evals += dc.slot[sl].n_chain;
-    if (segment_units_fit(dc) && distinct_segments(dc) < chain_evals && !(ctx->tune.debug_flags & 0x1000)) {
+    if (segment_units_fit(dc) && distinct_segments(dc) < chain_evals) {
         dc.seg_mode = 1;
         dc.n_useg = distinct_segments(dc, dc.useg_seg);
         dc.ed_seg_base = (dc.has_grav || dc.has_drag || dc.has_tides) ? 9 : 0;
@@ -851,6 +822,11 @@ static void assign_roles(nyx_hip_ctx *ctx, int n_waves, bool fanout, double *hc)
         dc.role_mask[1] = DEV_ROLE_DCM | ((1 << dc.n_useg) - 1);
     }
 }
+
+// The balanced helper dealing (build_schedule): the speed of a helper column wave on a SIMD that hosts three of them (beside the
+// producer / the answering wave), and what the start of one more column on a helper wave is charged, in rows.
+static constexpr double kCoopFastWeight = 4.0 / 3.0;
+static constexpr double kCoopStartRows = 4.0;
 
 static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
     DevCfg &dc = ctx->host_cfg;
@@ -883,7 +859,7 @@ static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
     // then leaves the buffers of stage parity 0 free for the epoch data of t + h)
     // (with a gravity field: one almanac wave; without: any fan-out, almanac and perturbation duties in waves of their own)
     dc.spec = (dc.pipe && !(dc.flags & NYX_HIP_FLAG_STM) && dc.stages % 2 == 0 &&
-               (dc.has_grav ? (dc.n_alm == 1 || (ctx->tune.debug_flags & 0x10000000) != 0) : (n_waves >= 3 && dc.role_kind[1] != DEV_ROLE_ALMANAC_PERT && (dc.n_slots > 0 || dc.has_drag || dc.has_tides))) &&
+               (dc.has_grav ? dc.n_alm == 1 : (n_waves >= 3 && dc.role_kind[1] != DEV_ROLE_ALMANAC_PERT && (dc.n_slots > 0 || dc.has_drag || dc.has_tides))) &&
                !dc.has_grav2 &&  // (the second field's wave reads the attempt's epoch at stage 0: it would have to wait for step control)
                ctx->tune.chained_attempts != 0) ? 1 : 0;
     dc.ed_reuse = (dc.spec || dc.seg_mode) ? 0 : ctx->ed_reuse_fit;  // (chained attempts need no copy of the stage-0 epoch data: a rejected lane keeps its k_0)
@@ -899,7 +875,6 @@ static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
     // time is then one long column (~18 batches), which is within 17 % of the ideal x * terms / 16 for x <= 0.35, and the
     // owner keeps the many short columns that let it balance its fifteen waves.  (Interleaving the two sets column by
     // column was measured 10-25 % slower: the helper's waves then hold a long AND a short column each.)
-    dc.sums_wave1 = 0;
     if (n_waves == DEV_MAX_WAVES && nc >= 8 && ctx->coop_fan) {
         // FAN-OUT mode (launch(): the idle CUs outnumber the owners at least two to one - a shard of an ensemble, a small Monte Carlo).
         // Every owner has K = coop_parts dedicated helper workgroups (propagate_kernel.hip, helper_body under NYX_COOP_FAN); the owner's
@@ -923,16 +898,6 @@ static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
         }
         if (n_help > 0 && !own.empty() && fill_schedule(ctx, dc.sched[DEV_SCHED_PRIMARY], n_waves, own, hc, false)) {
             dc.coop_ok = 1;
-            // The sums wave (round 6, fan_sums): the owner's period is its integrator's chain, of which the two stage sums of a window are
-            // ~40 %; a column wave that holds no column of the PRIMARY schedule forms them beside it - on a SIMD that hosts no role wave
-            // when there is one (waves 3, 7, 11, 15).  debug_flags 0x40000000: the integrator forms them itself (A/B, same bits).
-#if NYX_FAN_SUMS
-            if (dc.pipe && !dc.has_drag && !(ctx->tune.debug_flags & 0x40000000)) {  // (the six values live in the drag rows of the perturbation buffers)
-                static const int order[] = {15, 11, 7, 3, 14, 13, 12, 10, 9, 8, 6, 5, 4};
-                for (int w : order)
-                    if (dc.role_kind[w] == DEV_ROLE_COLUMNS && dc.sched[DEV_SCHED_PRIMARY].n_ranges[w] == 0) { dc.sums_wave1 = w + 1; break; }
-            }
-#endif
         } else {
             dc.coop_ok = 0;
             for (int k = 0; k < DEV_N_SCHED; ++k)
@@ -968,15 +933,15 @@ static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
         // the other two four - and with the streamed table a helper is bound by its SIMDs' issue, so a wave of a three-wave SIMD walks
         // 4/3 the rows of the others in the same time.  The longest columns still go one per wave; when the share asks for more than
         // those, the FAST waves get a second, medium column each out of one contiguous block of the table (the owners keep contiguous
-        // runs on either side), chosen so that every SIMD of the helper finishes together.  (debug_flags 0x400000: the old dealing.)
-        const bool balanced = ctx->coop_deal != 0 && parts_cfg == 1 && max_cols == col_waves && nc > 3 * col_waves;
+        // runs on either side), chosen so that every SIMD of the helper finishes together.
+        const bool balanced = parts_cfg == 1 && max_cols == col_waves && nc > 3 * col_waves;
         std::vector<int> topup;
         if (balanced) {
             double first = 0.0;
             for (int c = 1; c <= col_waves; ++c) first += ctx->col_len[c];
             const double extra = share * terms - first;
             const int n_fast = 6;
-            const double per = extra / n_fast - ctx->coop_start_rows;  // rows of the second column of a fast wave
+            const double per = extra / n_fast - kCoopStartRows;  // rows of the second column of a fast wave
             if (per >= 6.0) {
                 // columns of `per` rows: col_len[c] = deg + 2 - c
                 int c_mid = dc.deg + 2 - (int)(per + 0.5);
@@ -1013,28 +978,8 @@ static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
             if (part >= parts) continue;
             std::vector<int> mine;
             for (size_t k = 0; k < help.size(); ++k) if ((int)(k % (size_t)parts) == part) mine.push_back(help[k]);
-            if (ctx->coop_deal >= 2 && parts_cfg == 1 && max_cols == col_waves) {
-                // EXPERIMENT (tools only: NYX_HIP_COOP_DEAL=2 / 3), measured in round 5 and LOST: two waves per SIMD, each with a pair of
-                // columns of equal sum (k-th longest + k-th shortest of the helper's set) - on the microbenchmark two waves saturate a
-                // SIMD's issue, so four one-column waves that finish at 8 / 10 / 13 / 16-17 k cycles looked like oldest-first skew a pair
-                // of two-column waves would avoid.  They do not: a column walk is a dependent chain per row (108 cycles per row and wave
-                // whatever the SIMD's load), 129 rows on one wave are 15.6 k cycles - 95.4 ms per 3 h of configs[1] against 77.4 (scalar
-                // feed), 102.3 against 77.0 (streamed).  One column per wave on fourteen waves stays.
-                static const int pair_waves[12] = {1, 2, 4, 3, 5, 6, 8, 7, 9, 10, 12, 11};
-                const int nm = (int)mine.size();
-                const int use = ctx->coop_deal == 3 ? 12 : 8;   // (3: three waves per SIMD, for comparison)
-                int q = 0;
-                for (int a = 0, b = nm - 1; a <= b; ++a, --b, ++q) {
-                    const int w = pair_waves[q % use];
-                    if (hs.n_ranges[w] + 2 > DEV_MAX_RANGES) break;
-                    int r = hs.n_ranges[w]++;
-                    hs.range_c0[w][r] = mine[a]; hs.range_cnt[w][r] = 1;
-                    if (b > a) { r = hs.n_ranges[w]++; hs.range_c0[w][r] = mine[b]; hs.range_cnt[w][r] = 1; }
-                }
-                continue;
-            }
             if (balanced) {
-                // longest column first onto the wave that would finish it soonest: load / speed, speed = coop_fast_weight on the SIMDs with
+                // longest column first onto the wave that would finish it soonest: load / speed, speed = kCoopFastWeight on the SIMDs with
                 // three column waves (waves 4 8 12 beside the producer, 3 7 11 beside the answering wave)
                 double load[DEV_MAX_WAVES] = {0.0};
                 for (int c : mine) {  // (ascending column number = descending length)
@@ -1043,12 +988,12 @@ static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
                     for (int q = 0; q < col_waves; ++q) {
                         const int w = wave_order[q];
                         if (hs.n_ranges[w] >= DEV_MAX_RANGES) continue;
-                        const double speed = (w % 4 == 0 || w % 4 == 3) ? ctx->coop_fast_weight : 1.0;
-                        const double t = (load[w] + ctx->col_len[c] + (hs.n_ranges[w] > 0 ? ctx->coop_start_rows : 0.0)) / speed;
+                        const double speed = (w % 4 == 0 || w % 4 == 3) ? kCoopFastWeight : 1.0;
+                        const double t = (load[w] + ctx->col_len[c] + (hs.n_ranges[w] > 0 ? kCoopStartRows : 0.0)) / speed;
                         if (t < best_t - 1e-9) { best_t = t; best = w; }
                     }
                     if (best < 0) break;
-                    load[best] += ctx->col_len[c] + (hs.n_ranges[best] > 0 ? ctx->coop_start_rows : 0.0);
+                    load[best] += ctx->col_len[c] + (hs.n_ranges[best] > 0 ? kCoopStartRows : 0.0);
                     const int r = hs.n_ranges[best]++;
                     hs.range_c0[best][r] = c; hs.range_cnt[best][r] = 1;
                 }
@@ -1317,23 +1262,20 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
                                         cfg->tides ? &cfg->tides->rotation : nullptr, cfg->gravity2 ? &cfg->gravity2->rotation : nullptr})
         if (r)
             if (const char *why = check_rotation(*r, cfg->n_segments)) { nyx_set_error("body-fixed orientation: %s", why); return NYX_HIP_RC_BAD_ARG; }
+    const nyx_hip_tuning_t tune = resolve_tuning(cfg->tuning);
+    if (const uint32_t retired = (uint32_t)tune.debug_flags & ~kLiveDebugFlags) {
+        nyx_set_error("tuning.debug_flags 0x%x: not a debug switch of this library (the A/B path it selected was retired)", retired & (0u - retired));
+        return NYX_HIP_RC_BAD_ARG;
+    }
     if (nyx_hip_device_count() <= device || device < 0) { nyx_set_error("no HIP device %d", device); return NYX_HIP_RC_NO_DEVICE; }
     HIP_TRY(hipSetDevice(device));
 
     nyx_hip_ctx *ctx = new nyx_hip_ctx();
     ctx->device = device;
-    ExpKnobs xk;
-    ctx->tune = resolve_tuning(cfg->tuning, &xk);
+    ctx->tune = tune;
     ctx->block_schedule = (ctx->tune.debug_flags & 0x8000) == 0;  // (0x8000: the two-ended column fill of rounds 1-3 everywhere)
     ctx->block_force = (ctx->tune.debug_flags & 0x10000) != 0;    // (0x10000: contiguous runs whatever the feed - the A/B partner of the streamed walk)
-    ctx->fit_big = xk.fit_big; ctx->fit_quad = xk.fit_quad; ctx->fit_solo = xk.fit_solo;
     ctx->fit_partition = (ctx->tune.debug_flags & 0x2000000) == 0;  // (0x2000000: the linear partition of round 4 for the cooperative 70x70 shape too, fill_schedule)
-    ctx->coop_deal = (ctx->tune.debug_flags & 0x400000) ? 0 : 1;  // (0x400000: the helper dealing of rounds 1-4 - the longest columns, one per wave)
-    if (xk.fast_weight > 0.0) ctx->coop_fast_weight = xk.fast_weight;  // (experiment knobs of the tools, never of a caller: resolve_tuning)
-    if (xk.start_rows >= 0.0) ctx->coop_start_rows = xk.start_rows;
-    if (xk.deal >= 0) ctx->coop_deal = xk.deal;
-    for (int k = 0; k < 8; ++k) ctx->role_place[k] = xk.place[k];
-    ctx->role_place_sums = xk.place_sums; ctx->role_place_twobody = xk.place_twobody;
     DevCfg &dc = ctx->host_cfg;
     std::memset(&dc, 0, sizeof dc);
     const NyxTableau &tb = NYX_TABLEAUX[o.method];
@@ -1432,9 +1374,9 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
     // Device layout of the records.  cheby_eval() works on a sixteen-coefficient register window and has to blank the entries past a
     // segment's own count (two v_cndmask per coefficient on the almanac wave, every stage).  When the whole table stays small the
     // records of segments with <= 16 coefficients are therefore laid out SIXTEEN wide, zero-padded: the zeros are in the table, the
-    // selects go (DevSeg.stride = 50 tells the kernel; same values, same bits).  (0x2000: A/B switch, same results)
+    // selects go (DevSeg.stride = 50 tells the kernel; same values, same bits).
     const int kChebWin = 16;
-    bool pad16 = !(ctx->tune.debug_flags & 0x2000);
+    bool pad16 = true;
     {
         size_t packed = 0, padded = 0;
         for (int i = 0; i < cfg->n_segments; ++i) {
@@ -1569,7 +1511,6 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
         if (nyx_kernel_lds_bytes(DEV_MAX_WAVES, dc.rec_in_lds ? dc.rec_doubles : 0, 0, nf) <= 160 * 1024) dc.ed_reuse = nf;
     }
     ctx->ed_reuse_fit = dc.ed_reuse;
-    dc.coop_late = (ctx->tune.debug_flags & 0x1000000) ? 0 : 1;  // (0x1000000: the answer collected inside the window, rounds 1-4)
     dc.coop_frac = 0.30;  // measured optimum with two owners per helper (10 000 trajectories, 70x70): 0.28-0.33 is flat
     if (ctx->tune.coop_fraction > 0.0) dc.coop_frac = std::min(0.9, std::max(0.05, ctx->tune.coop_fraction));
     {
@@ -1863,19 +1804,17 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
         const int64_t n_own = (in->n + DEV_LANES - 1) / DEV_LANES;
         // Helpers start right behind the owners and fill every CU that is left (round 4: 99 helpers instead of 96 for 157 owners is
         // 3.9 % of the north-star run - the helpers' queues are what the owners wait in; rounds 1-3 rounded both to multiples of
-        // eight for XCD affinity, which buys nothing measurable: debug_flags 0x20000 restores it).
-        const bool pack = (ctx->tune.debug_flags & 0x20000) == 0;
-        const int64_t base = pack ? n_own : (n_own + 7) / 8 * 8;
+        // eight for XCD affinity, which buys nothing measurable).
+        const int64_t base = n_own;
         const bool stm_ctx = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
         if (want && !stm_ctx && ctx->host_cfg.has_grav && ctx->host_cfg.g_slot < 0 && nw == DEV_MAX_WAVES && ctx->host_cfg.coop_ok &&
             base + 8 <= ctx->n_cu) {
             // (more helpers than owners: the jobs are claimed, not assigned, so extra helpers shorten the queue of a set)
             // Two-part hand-off: when the idle CUs outnumber the owners by a quarter and a helper job holds several columns per wave
             // (large fields), every evaluation's hand-off is split in two sub-jobs for two helper workgroups (see build_schedule); the
-            // helper count then goes up to two per owner.  (debug_flags 0x40000 / 0x80000 force two parts / one part.)
-            const int64_t free_cus = pack ? ctx->n_cu - base : (ctx->n_cu - base) / 8 * 8;
+            // helper count then goes up to two per owner.  (debug_flags 0x80000 forces one part.)
+            const int64_t free_cus = ctx->n_cu - base;
             int parts = (ctx->host_cfg.n_cols > 96 && 4 * free_cus >= 5 * n_own) ? 2 : 1;
-            if (ctx->tune.debug_flags & 0x40000) parts = 2;
             if (ctx->tune.debug_flags & 0x80000) parts = 1;
             // Fan-out mode (round 6): when the idle CUs outnumber the owners at least two to one - what a rank runs when ONE ensemble is
             // cut over the GPUs of a node (configs[1] over 2 / 4 / 8 ranks: 79 / 40 / 20 owners), or a small Monte Carlo - every owner gets
@@ -1884,7 +1823,7 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
             // 648 / 642 / 639 ms against 615 for 10 000 - a rank of 8 was no faster than one GPU alone.  Fields up to degree 95 (larger
             // ones keep the two-part claim mode, whose jobs hold several columns per wave).  debug_flags 0x8000000 switches it off.
             bool fan = ctx->host_cfg.n_cols <= 96 && free_cus >= 2 * n_own && n_own >= 1 && !(ctx->tune.debug_flags & 0x8000000) &&
-                       !(ctx->tune.debug_flags & (0x40000 | 0x80000)) && !(ctx->tune.coop_helper_ratio > 0.0);
+                       !(ctx->tune.debug_flags & 0x80000) && !(ctx->tune.coop_helper_ratio > 0.0);
             if (fan) parts = (int)std::min<int64_t>(DEV_FAN_MAX, free_cus / n_own);
             double h_ratio = parts == 2 ? 2.0 : 1.0;
             if (ctx->tune.coop_helper_ratio > 0.0) h_ratio = std::min(3.0, std::max(0.25, ctx->tune.coop_helper_ratio));
@@ -1943,7 +1882,7 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
                     bt.coop_posted = words; bt.coop_claimed = words + (ctx->coop_cap + 64); bt.coop_finished = words + 2 * (ctx->coop_cap + 64);
                     bt.coop_sets = (int32_t)((n_own + 15) / 16);
                     bt.coop_parts = ctx->coop_parts;
-                    bt.coop_mute = (ctx->tune.coop_mute ? 1 : 0) | ((ctx->tune.debug_flags & 0x200000) ? 2 : 0);  // (bit 1: helpers fetch a job's inputs speculatively, before they know they won its claim)
+                    bt.coop_mute = ctx->tune.coop_mute ? 1 : 0;  // (bit 1, the retired speculative fetch of helper_body, stays clear)
                     ctx->last_coop_helpers = (int)helpers;
                 }
             }
@@ -1951,9 +1890,8 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
     }
     if (!ctx->h_tab.empty() && ctx->host_cfg.harm_feed != 0 && !(ctx->host_cfg.flags & NYX_HIP_FLAG_STM)) {
         // workgroups that stream the table walk run streams: one per schedule, every range of a wave at the head of a sixteen-row
-        // group (DevCfg.rs_*; debug_flags 0x800000: the common stream, as in round 4 - same bits)
-        const bool want = (ctx->tune.debug_flags & 0x800000) == 0;
-        if (want && ctx->rs_dirty) {
+        // group (DevCfg.rs_*)
+        if (ctx->rs_dirty) {
             for (int k = 0; k < 3; ++k) {
                 const bool used = k == 0 ? (ctx->host_cfg.harm_feed & 1) != 0
                                   : (ctx->host_cfg.coop_ok != 0 && (k == 1 ? (ctx->host_cfg.harm_feed & 1) != 0 : (ctx->host_cfg.harm_feed & 2) != 0));
@@ -1978,9 +1916,6 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
                 ctx->host_cfg.rs_cols[k] = (uint64_t)ctx->d_rs_cols[k];
             }
             ctx->rs_dirty = false;
-            HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
-        } else if (!want && (ctx->host_cfg.rs_hyb[0] | ctx->host_cfg.rs_hyb[1] | ctx->host_cfg.rs_hyb[2]) != 0) {
-            ctx->host_cfg.rs_hyb[0] = ctx->host_cfg.rs_hyb[1] = ctx->host_cfg.rs_hyb[2] = 0;
             HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
         }
     }

@@ -54,14 +54,6 @@ DEVFN bool coop_get(const uint64_t *g, uint32_t seq, double &v) {
 // (round 5: the five rows are read from LDS through an LDS-qualified pointer and all at once, THEN stored.  Through the generic pointer
 //  of rounds 1-4 every row was a flat_load behind `s_waitcnt vmcnt(0) lgkmcnt(0)`, i.e. behind the previous row's stores to uncached
 //  memory: five serial round trips, 4.7 k cycles of the integrator's window per evaluation.)
-#ifndef COOP_INLINE
-#define COOP_INLINE 0
-#endif
-#if COOP_INLINE
-#define COOP_FN static __device__ __forceinline__
-#else
-#define COOP_FN static __device__ __attribute__((noinline))
-#endif
 // (`mult`: what the scan words count - sub-jobs: 1 per evaluation, or 2 with the two-part hand-off)
 DEVFN void coop_post_inl(CoopBox *box, uint32_t *posted, int lane, uint32_t seq, LdsCPtr inb, uint32_t mult) {
     double v[5];
@@ -71,7 +63,7 @@ DEVFN void coop_post_inl(CoopBox *box, uint32_t *posted, int lane, uint32_t seq,
     for (int q = 0; q < 5; ++q) coop_put(&box->in[seq & 1u][q][0][lane], v[q], seq);
     if (lane == 0) coop_store(posted, mult * seq);
 }
-COOP_FN void coop_post(CoopBox *box, uint32_t *posted, int lane, uint32_t seq, LdsCPtr inb) {
+static __device__ __attribute__((noinline)) void coop_post(CoopBox *box, uint32_t *posted, int lane, uint32_t seq, LdsCPtr inb) {
     double v[5];
 #pragma unroll
     for (int q = 0; q < 5; ++q) v[q] = inb[q * DEV_LANES + lane];
@@ -123,7 +115,7 @@ DEVFN CoopAnswer coop_wait_inl(CoopBox *box, int lane, uint32_t seq) {
     a.ok = 1;
     return a;
 }
-COOP_FN CoopAnswer coop_wait(CoopBox *box, int lane, uint32_t seq) { return coop_wait_inl(box, lane, seq); }
+static __device__ __attribute__((noinline)) CoopAnswer coop_wait(CoopBox *box, int lane, uint32_t seq) { return coop_wait_inl(box, lane, seq); }
 // two parts: part 0 from the mailbox, part 1 from the array of second answers, added in that order whichever helper answered first
 DEVFN CoopAnswer coop_wait2_inl(CoopBox *box, CoopOut *out2, int lane, uint32_t seq) {
     CoopAnswer a = {0.0, 0.0, 0.0, 0.0, 0};
@@ -205,15 +197,6 @@ static __device__ __attribute__((noinline)) Partial4 coop_fallback(uint64_t cfg_
  * kernel of config 3, whose integrator shares its SIMD with one almanac wave, 46.8 ms with two pows against 47.2 with one */
 #define STEP_ONE_POW ((NYX_EMIT & (NYX_EMIT_PLAIN16 | NYX_EMIT_PLAIN16_P2 | NYX_EMIT_PLAIN16_FAN)) ? 1 : 0)
 #endif
-#ifndef FAN_POLL_FETCH
-#define FAN_POLL_FETCH 0  /* 1: the fan-out producer's poll fetches all ten granules (one round trip from post to inputs instead of two); measured neutral, round 6: 1 250 x 24 h 357.2-359.9 ms against 357.7-359.5 */
-#endif
-#ifndef FAN_SKIP
-#define FAN_SKIP 1  /* fan-out kernel: a wave without columns under the schedule in force skips its walk (five LDS reads, a call, the schedule lookup) */
-#endif
-#ifndef FAN_SUMS
-#define FAN_SUMS NYX_FAN_SUMS  /* devcfg.h: fan-out mode, the integrator's two stage sums formed by a column wave of their own (fan_sums, DevCfg.sums_wave1) */
-#endif
 #ifndef STEP_OOL
 #ifdef NYX_COOP_FAN
 #define STEP_OOL 1          /* step control out of line (integ_step, round 6): the fan-out kernel, whose period IS the integrator's chain (1 250 x 24 h: 391 -> 382.5 ms) */
@@ -221,22 +204,14 @@ static __device__ __attribute__((noinline)) Partial4 coop_fallback(uint64_t cfg_
 #define STEP_OOL 0          /* the other INTEG_OOL kernels keep it inline: measured same box, 24 h of configs[1]: 601.9 ms out of line against 597.9 inline (three interleaved pairs; step control 19 k -> 11.9 k cycles per attempt either way, but the period there is the column waves') */
 #endif
 #endif
-#ifndef STEP_SUMS_UNROLL
-#define STEP_SUMS_UNROLL 0  /* step control: unroll factor of the loop over the stages of its two sums (0: as the compiler leaves it) */
-#endif
-#ifndef COOP_AFFINITY
-#define COOP_AFFINITY 1  /* helpers take a job of their own first (see helper_body) */
-#endif
-#ifndef HELPER_SLOTS
-#define HELPER_SLOTS 2  /* jobs in flight inside a helper (see helper_body: three and four were measured, slower) */
-#endif
-#define HELPER_LDS_BYTES ((HELPER_SLOTS * DEV_MAX_WAVES * 4 * DEV_LANES + HELPER_SLOTS * 5 * DEV_LANES) * 8 + 64 * 4)
+// Jobs in flight inside a helper: two.  Round 5 measured three and four (in-kernel accounting of a helper, tools/sweep.py "profile"):
+// with two slots the producer waits ~9 k cycles per job for a slot and only then scans, claims and fetches (~10 k cycles of uncached
+// round trips); more slots do move the claim under the arithmetic - and lose, 84.9 -> 92.3 -> 103.3 ms per 3 h of configs[1]:
+// a job claimed early queues INSIDE this helper behind two or three others while another helper would have been free sooner
+// (lost claims per job 2.4 -> 2.6 -> 4.0): the rate of jobs is the owners', what counts is each job's turnaround.
+constexpr int HELPER_SLOTS = 2;
+constexpr size_t HELPER_LDS_BYTES = (HELPER_SLOTS * DEV_MAX_WAVES * 4 * DEV_LANES + HELPER_SLOTS * 5 * DEV_LANES) * 8 + 64 * 4;
 DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols, char *smem, int lane, int wave) {
-    // HELPER_SLOTS jobs in flight.  Round 5 measured three and four (in-kernel accounting of a helper, tools/sweep.py "profile"): with
-    // two slots the producer waits ~9 k cycles per job for a slot and only then scans, claims and fetches (~10 k cycles of uncached
-    // round trips); more slots do move the claim under the arithmetic - and lose, 84.9 -> 92.3 -> 103.3 ms per 3 h of configs[1]:
-    // a job claimed early queues INSIDE this helper behind two or three others while another helper would have been free sooner
-    // (lost claims per job 2.4 -> 2.6 -> 4.0): the rate of jobs is the owners', what counts is each job's turnaround.
     constexpr int NS = HELPER_SLOTS;
     double *part = (double *)smem;                                  // [NS][16][4][64]
     double *inl = part + NS * DEV_MAX_WAVES * 4 * DEV_LANES;        // [NS][5][64]
@@ -287,21 +262,14 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
                     slot_free = answered[s] == j - (NS - 1);
                     if (!slot_free) { __builtin_amdgcn_s_sleep(4); continue; }
                 }
-                // the poll IS the fetch (FAN_POLL_FETCH): all ten granules of this lane every time, accepted when every tag of every lane
-                // carries the sequence number - one uncached round trip from the owner's post to the inputs in hand instead of two (a poll of
-                // one granule, then the fetch), on the turnaround that bounds the owner's period in this mode
-#if FAN_POLL_FETCH
-                {
-#else
+                // poll one granule (lane 0's last), then fetch all ten granules of this lane until every tag carries the sequence number
+                // (fetching all ten at every poll instead was measured neutral in round 6)
                 if ((uint32_t)(coop_loadu(&b->in[par][4][1][0]) >> 32) == seq) {
-#endif
                     const bool got = coop_get(&b->in[par][0][0][lane], seq, v0) & coop_get(&b->in[par][1][0][lane], seq, v1) &
                                      coop_get(&b->in[par][2][0][lane], seq, v2) & coop_get(&b->in[par][3][0][lane], seq, v3) &
                                      coop_get(&b->in[par][4][0][lane], seq, v4);
                     if (__all(got)) break;
-#if !FAN_POLL_FETCH
                     continue;
-#endif
                 }
                 if ((it & 7) == 7 && coop_load(bt.coop_finished + fan_widx) != 0u) { owner = -1; break; }  // the owner is done (or carries on alone)
                 __builtin_amdgcn_s_sleep(2);
@@ -356,7 +324,6 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
                     const unsigned rot = turn++ & 63u;
                     const uint64_t hi = cand >> rot;
                     int pick = hi ? (int)rot + __builtin_ctzll(hi) : __builtin_ctzll(cand);
-#if COOP_AFFINITY
                     // ... but a job has a PREFERRED helper - (owner slot + job number) mod the set's helpers, so that an owner's consecutive
                     // jobs go round the set - and a helper takes one of its own first: two idle helpers of a set that see the same jobs no
                     // longer go for the same one.  Round 5, 3 h of configs[1], same box, alternating: 82.6 / 83.3 ms without, 79.3 / 79.2 with
@@ -369,10 +336,9 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
                         const uint64_t pref = __ballot(has && (int32_t)(posted - claimed) > 0 && hs > 0 && (int)(((unsigned)lane + claimed) % (unsigned)hs) == rank);
                         if (pref) pick = __builtin_ctzll(pref);
                     }
-#endif
                     // jobs are taken in order, one at a time: an owner may have two outstanding (the pipelined loop posts
-                    // stage i+1 before it has read the answer of stage i).  The five input rows of the job are fetched in the
-                    // shadow of the compare-and-swap (they were complete before `posted` moved): one memory round trip, not two.
+                    // stage i+1 before it has read the answer of stage i).  The five input rows of the job are fetched once the
+                    // compare-and-swap has won it (below).
                     const int owner_c = (int)__shfl((int)mine, pick);
                     const uint32_t sub_c = (uint32_t)__shfl((int)claimed, pick) + 1u;           // the sub-job being claimed (1, 2, ...)
                     const uint32_t seq_c = parts == 2 ? (sub_c + 1u) >> 1 : sub_c;             // its evaluation ...
@@ -385,14 +351,13 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
                     }
                     const CoopBox *b = bt.coop_box + owner_c;
                     const unsigned par = seq_c & 1u;
-                    // (measured: fetching only after the claim has succeeded costs 7 % of the north-star run - the helper's job
-                    //  latency is what bounds its share)
-                    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0, v4 = 0.0;
-                    bool got = false;
                     // Fetch the inputs only AFTER the claim has succeeded.  (Rounds 1-3 fetched them in the shadow of the compare-and-swap -
                     // measured then as 7 % faster; with the tagged-granule transport the opposite holds: every lost race was 5 KB of
-                    // uncached reads, and the north-star run is 5.5 % FASTER without them - 719.5 -> 679.8 ms, same box.  coop_mute bit 1
-                    // = debug_flags 0x200000 restores the speculative fetch.)
+                    // uncached reads, and the north-star run is 5.5 % FASTER without them - 719.5 -> 679.8 ms, same box.)
+                    // The speculative fetch is retired and the host never sets coop_mute bit 1, but its branch stays: without it the
+                    // register allocation of every kernel that carries helper_body moves (config 3: 43.8 -> 45.3 ms).
+                    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0, v4 = 0.0;
+                    bool got = false;
                     const bool lazy = (bt.coop_mute & 2) == 0;
                     if (!lazy)
                         got = coop_get(&b->in[par][0][0][lane], seq_c, v0) & coop_get(&b->in[par][1][0][lane], seq_c, v1) &
@@ -445,15 +410,6 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
 #endif  // NYX_COOP_FAN
     // optional accounting of the FIRST helper workgroup (NYX_HIP_PROFILE; rows 17.. of the profile, one per wave): [0] cycles in the
     // column walk, [1] cycles waiting for a job, [2] jobs, [3] cycles from a job's publication in LDS to this wave's delivery, [5] total
-#ifdef HELPER_PRIO
-    // issue priority against the arbiter's oldest-first rule: the four waves of a SIMD start a job together, and served oldest first the
-    // oldest is done after half the job's time and runs ahead into the next job while the youngest - whose column the answer waits
-    // for - gets what is left
-    if (wave != answer_wave) {
-        const int pr = HELPER_PRIO == 1 ? (wave >> 2) : (3 - (wave >> 2));
-        if (pr == 3) __builtin_amdgcn_s_setprio(3); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-    }
-#endif
     const bool hprof = NYX_PROF && bt.prof != nullptr && (int)blockIdx.x == bt.coop_base;
     int64_t hp_busy = 0, hp_wait = 0, hp_jobs = 0;
     const int64_t hp_start = hprof ? (int64_t)__builtin_readcyclecounter() : 0;

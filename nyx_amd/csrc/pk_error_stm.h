@@ -67,25 +67,6 @@ DEVFN double error_estimate(int ec, const double *e, const double *cand, const d
 // Fold of the 15 workers' partial accelerations (fixed wave order => deterministic).  Kept out of line on purpose:
 // inside the integrator role (at its 128-VGPR cap) the scheduler serialised the 60 LDS reads at one LDS latency each
 // (5 k cycles on the critical path of every force evaluation); on its own the function batches them.
-#ifndef FOLD_INLINE
-#define FOLD_INLINE 0
-#endif
-#if FOLD_INLINE
-// (inlined variant: the sixty reads in four batches of fifteen - one component at a time - so that they need 30 registers, not 120)
-static __device__ __forceinline__ Partial4 fold_partials(LdsCPtr part, int lane, double px, double py, double pz, double pw) {
-    double o[4] = {px, py, pz, pw};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double v[DEV_MAX_WAVES - 1];
-#pragma unroll
-        for (int w = 1; w < DEV_MAX_WAVES; ++w) v[w - 1] = part[(w * 4 + q) * DEV_LANES + lane];
-#pragma unroll
-        for (int w = 1; w < DEV_MAX_WAVES; ++w) o[q] += v[w - 1];
-    }
-    Partial4 r = {o[0], o[1], o[2], o[3]};
-    return r;
-}
-#else
 static __device__ __attribute__((noinline)) Partial4 fold_partials(LdsCPtr part, int lane, double px, double py, double pz, double pw) {
     double v[4][DEV_MAX_WAVES - 1];
 #pragma unroll
@@ -100,7 +81,6 @@ static __device__ __attribute__((noinline)) Partial4 fold_partials(LdsCPtr part,
     Partial4 r = {px, py, pz, pw};
     return r;
 }
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // STM variant: position partials of the perturbations (perturbation wave) and the per-step update

@@ -283,9 +283,6 @@ DEVFN void cpow_uniform(T zr, T zi, int e, T &pr, T &pi) {
         a1 = an;                                                                           \
     }
 
-#ifndef TOUCH_AHEAD
-#define TOUCH_AHEAD 1
-#endif
 // One batch of the table = 280 contiguous bytes = 70 SGPRs, fetched by six scalar loads behind a single wait.
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -309,6 +306,7 @@ DEVFN void load_batch(HarmPtr e, HarmBatch &b) {
         : "s"(e)
         : "memory");
 }
+constexpr int TOUCH_AHEAD = 1;  // batches between the one being loaded and the one being touched
 // Touch the (up to six) 64-byte lines of the batch TOUCH_AHEAD batches further on (results discarded): by the time its
 // loads are issued the lines are in the scalar cache or on their way.  (The table is padded accordingly.)
 // `sink` is read and written so that the register stays allocated for as long as a touch can be in flight: until the
@@ -379,7 +377,7 @@ DEVFN Partial4T<T> harmonics_core(CfgPtr cfg, HarmPtr htab, ColPtr cols, const i
                 // lane.  The loads are spelled out: left to the scheduler, instantiations under register pressure wait after every load.
                 HarmBatch hb;
                 load_batch(e, hb);
-                if (TOUCH_AHEAD) touch_batch(e, sink);
+                touch_batch(e, sink);
                 const HarmEntry h0 = HB_ENTRY(hb.q0, hb.q0, hb.q0, hb.q0, hb.q0, hb.q0, hb.q0, 0, 2, 4, 6, 8, 10, 12);
                 const HarmEntry h1 = HB_ENTRY(hb.q0, hb.q1, hb.q1, hb.q1, hb.q1, hb.q1, hb.q1, 14, 0, 2, 4, 6, 8, 10);
                 const HarmEntry h2 = HB_ENTRY(hb.q1, hb.q1, hb.q2, hb.q2, hb.q2, hb.q2, hb.q2, 12, 14, 0, 2, 4, 6, 8);
@@ -409,7 +407,7 @@ DEVFN Partial4T<T> harmonics_core(CfgPtr cfg, HarmPtr htab, ColPtr cols, const i
                     }
                 }
             }
-            if (TOUCH_AHEAD) touch_done(sink);
+            touch_done(sink);
             const T sc = rho * hd.scale;  // rho * c * sqrt(2)
             px = gfma(sc, gfma(rc, s1, gmul(ic, s2)), px);
             py = gfma(sc, gfma(rc, s2, -(gmul(ic, s1))), py);

@@ -1,4 +1,4 @@
-// pk_integrator_ool.h - part of propagate_kernel.hip (included there, in this order; not a stand-alone header): the integrator wave of the sixteen-wave plain kernels out of line: integ_front / integ_sums / integ_back / integ_step (and the fan-out mode's sums wave).
+// pk_integrator_ool.h - part of propagate_kernel.hip (included there, in this order; not a stand-alone header): the integrator wave of the sixteen-wave plain kernels out of line: integ_front / integ_back / integ_step.
 // ---------------------------------------------------------------------------------------------
 // INTEG_OOL (round 6): the integrator wave of the sixteen-wave plain kernels, out of line.
 //
@@ -24,9 +24,6 @@
 // ---------------------------------------------------------------------------------------------
 #ifndef INTEG_OOL
 #define INTEG_OOL ((NYX_EMIT & (NYX_EMIT_PLAIN16 | NYX_EMIT_PLAIN16_P2 | NYX_EMIT_PLAIN16_FAN)) ? 1 : 0)
-#endif
-#ifndef IX_SUMS_OOL
-#define IX_SUMS_OOL 0   /* 1: the window's two stage sums out of line too (integ_sums) - built and measured in round 6, same box, 24 h of configs[1]: 610 ms against 598.5 inline (fan-out shard of 1 250: 399 against 392): branch-free, it issues five times the VALU instructions of the branchy inline loops on the SIMD that also hosts three column waves */
 #endif
 #if INTEG_OOL
 #define IX_HOT 1       /* phase A from the position the previous window published (else: the caller did phase A, v3..5 are the stage velocity) */
@@ -89,11 +86,7 @@ static __device__ __attribute__((noinline)) int integ_front(uint32_t lds_v, uint
         }
 #pragma unroll
         for (int e = 0; e < 3; ++e) ysb[(3 + e) * DEV_LANES + lane] = vel[e];
-#if defined(NYX_COOP_FAN) && FAN_SUMS
-        if (cfg->has_drag || cfg->sums_wave1 != 0) {  // (... and the sums wave, which adds this stage's velocity term last: fan_sums)
-#else
         if (cfg->has_drag) {  // the perturbation wave is already in this stage's window; drag is the one term that wants the velocity
-#endif
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0) LCTL[4] = i + 1;
         }
@@ -169,72 +162,6 @@ static __device__ __attribute__((noinline)) int integ_front(uint32_t lds_v, uint
     return st;
 }
 
-// The two stage sums the integrator's window forms beside the column walk, out of line as well (round 6): the velocity part of
-// sum_{j<i} a_{i+1,j} k_j (phase A of the next stage adds the newest term) and the position part of the sum the NEXT window publishes
-// from (stage i + 2: j < i, then this stage's velocity; or, when the next window is the last of a chained attempt, y + sum (h b_j) k_j).
-// Inline in role_loop these were two loops of up to fourteen iterations with a uniform branch and an LDS round trip each - ~7 k cycles
-// of the integrator's ~19 k busy per evaluation, which is the owner's whole period once dedicated helpers carry its columns (fan-out
-// mode).  Here: the tableau rows as scalar loads from DevCfg (the same doubles propagate_body staged into LDS), the k rows in two
-// branch-free batches of seven stages (absent stages select +0.0 operands: +0.0 * +0.0 added to a sum that started from +0.0 leaves
-// its bits alone), the additions in the same ascending order: bit-identical sums.  A leaf inside the caller-saved registers.
-struct IxSums {
-    double w3, w4, w5, p0, p1, p2;
-};
-template <int COMP0>
-DEVFN void ix_sum_rows(const LdsPtr kb0, const CAS double *coef, double scale, bool scaled, int i, double (&acc)[3]) {
-    // acc[e] += c_j * k_j[COMP0 + e], j = 0 .. i - 1 ascending; c_j = coef[j], or scale * coef[j] (the h b_j of step control's sum)
-#pragma unroll
-    for (int j0 = 0; j0 < DEV_MAX_STAGES - 2; j0 += 7) {
-        if (j0 < i) {  // (uniform)
-            double c[7], k[7][3];
-#pragma unroll
-            for (int q = 0; q < 7; ++q) {
-                const int j = j0 + q;
-                const bool on = j < i;  // (uniform)
-                const double cj = coef[on ? j : 0];
-                c[q] = on ? (scaled ? scale * cj : cj) : 0.0;
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const double kv = kb0[(j * 6 + COMP0 + e) * DEV_LANES];
-                    k[q][e] = on ? kv : 0.0;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 7; ++q) {
-#pragma unroll
-                for (int e = 0; e < 3; ++e) acc[e] += c[q] * k[q][e];
-            }
-        }
-    }
-}
-static __device__ __attribute__((noinline)) IxSums integ_sums(uint32_t lds_v, uint64_t cfg_u, int i_v, int lane, double h, double v3, double v4, double v5) {
-    const int flags_v = 0;
-    IX_PROLOGUE
-    (void)flags; (void)kbuf; (void)kb_li; (void)KB_STR; (void)tabl;
-    const bool spec = cfg->spec != 0;
-    const LdsPtr kb0 = ix_rows(L.kbuf, lane);
-    const double vel[3] = {v3, v4, v5};
-    double w[3] = {0.0, 0.0, 0.0}, p[3] = {0.0, 0.0, 0.0};
-    if (i + 1 < stages) ix_sum_rows<3>(kb0, cfg->a + (i + 1) * i / 2, 0.0, false, i, w);
-    if (i + 2 < stages) {
-        const CAS double *row = cfg->a + (i + 2) * (i + 1) / 2;
-        ix_sum_rows<0>(kb0, row, 0.0, false, i, p);
-        const double a_ni = row[i];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] += a_ni * vel[e];
-    } else if (i + 2 == stages && spec) {
-        // the next window is the last: it publishes stage 0 of the next attempt, y + sum_j (h b_j) k_j
-#pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] = CS_Y(e);
-        ix_sum_rows<0>(kb0, cfg->b, h, true, i, p);
-        const double cbi = h * cfg->b[i];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] += cbi * vel[e];
-    }
-    IxSums r = {w[0], w[1], w[2], p[0], p[1], p[2]};
-    return r;
-}
-
 // Phase C of stage i (orbital.rs:80-114, spacecraft.rs:227-243), behind the stage barrier.  (a0, a1, a2): the two-body term formed in the
 // window.  A LEAF like integ_front (a function that keeps values live across calls of its own has to save the callee-saved registers it
 // uses in its prologue - fifty scratch stores and loads per call, measured on the first cut of this function): the wait for the helper's
@@ -277,11 +204,7 @@ static __device__ __attribute__((noinline)) IxBack integ_back(uint32_t lds_v, ui
     IX_PROLOGUE
     (void)stages; (void)tabl; (void)kbuf; (void)kb_li; (void)KB_STR;
     const bool has_grav = cfg->has_grav != 0, has_grav2 = cfg->has_grav2 != 0;
-#ifdef NYX_NO_TIDES
-    const bool has_tides = false;
-#else
     const bool has_tides = cfg->has_tides != 0;
-#endif
     const bool has_pm = cfg->n_pm > 0;
     IxBack out = {0.0, 0.0, 0.0, 0.0, 0};
     double acc[3] = {a0, a1, a2};
@@ -336,12 +259,6 @@ static __device__ __attribute__((noinline)) IxBack integ_back(uint32_t lds_v, ui
         }
     }
     ix_assemble(cfg, L, i, lane, acc, px, py, pz, pw, m_cur, s_, t_, u_, kfac, skip_k);
-#if defined(NYX_COOP_FAN) && FAN_SUMS
-    if (cfg->sums_wave1 != 0) {  // k_i is written: the sums wave may add its term (fan_sums; ctl[6] counts like the fold counter)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) LCTL[6] = __builtin_amdgcn_readfirstlane(fold_val_v);
-    }
-#endif
     return out;
 }
 // The rare other half of integ_back: the helper did not answer, the caller has walked its columns (fx..fw) on top of the fold (px..pw).
@@ -354,11 +271,7 @@ static __device__ __attribute__((noinline)) void integ_back_slow(uint32_t lds_v,
     (void)stages; (void)flags; (void)kbuf; (void)kb_li; (void)KB_STR;
     double acc[3] = {a0, a1, a2};
     const double *const pertc = (i & 1) ? L.pert2 : L.pert;
-#ifdef NYX_NO_TIDES
-    const bool has_tides = false;
-#else
     const bool has_tides = cfg->has_tides != 0;
-#endif
     if (cfg->n_pm > 0 || has_tides || cfg->has_grav2 != 0) {
         acc[0] += pertc[0 * DEV_LANES + lane]; acc[1] += pertc[1 * DEV_LANES + lane]; acc[2] += pertc[2 * DEV_LANES + lane];
     }
@@ -515,112 +428,5 @@ static __device__ __attribute__((noinline)) IxStep integ_step(uint32_t lds_v, ui
     cold_store(cs, 0, c);
     return out;
 }
-
-#if defined(NYX_COOP_FAN) && FAN_SUMS
-// FAN-OUT mode: the integrator's two stage sums on a wave of their own (round 6).  With dedicated helpers an owner's period IS its
-// integrator's chain (~19 k cycles per evaluation: integ_front 4.4 k, read-back + two-body + the two sums 8.3 k, fold + integ_back 5.3 k,
-// step control 0.7 k), while thirteen column waves of the workgroup hold three rows between them.  One of them (DevCfg.sums_wave1)
-// forms, in the window of stage i, what the integrator's window formed behind its post:
-//     W = sum_{j<i} a_{i+1,j} k_j[3..5]                          (phase A of stage i + 1 adds the newest term)
-//     P = sum_{j<i} a_{i+2,j} k_j[0..2] + a_{i+2,i} v_i          (the position part the NEXT window publishes from;
-//         or, when that window is the last of a chained attempt,  y + sum_{j<i} (h b_j) k_j[0..2] + (h b_i) v_i)
-// - the terms j <= i - 2 at once (their k rows were complete before the barrier this window starts behind), the term j = i - 1 when
-// the integrator's phase C of stage i - 1 has written k_{i-1} (ctl[6], raised by integ_back), the velocity term when integ_front has
-// stored v_i (ctl[4]) - and leaves the six values in the drag rows of the two perturbation buffers, which the integrator reads behind the stage barrier, in front of the
-// next integ_front.  The same additions in the same order as the inline sums: bit-identical results.  Every spin is bounded; a wait
-// that expires leaves NaNs, which end the step as NYX_HIP_ERR_NAN.
-static __device__ __attribute__((noinline)) void fan_sums(uint32_t lds_v, uint64_t cfg_u, int i_v, int lane, int flags_v, int kdone_v) {
-    IX_PROLOGUE
-    (void)kbuf; (void)kb_li; (void)KB_STR;
-    const bool spec = cfg->spec != 0;
-    const LdsPtr kb0 = ix_rows(L.kbuf, lane);
-    const LdsPtr ysb = ix_rows((i & 1) ? L.ys2 : L.ys, lane);
-    // (no LDS of its own: W in rows 6..8 of the even stages' perturbation buffer, P in those of the odd stages' - the drag rows, which
-    //  nothing touches in a configuration without drag; the host names a sums wave only then)
-    const LdsPtr out_w = ix_rows(L.pert + 6 * DEV_LANES, lane), out_p = ix_rows(L.pert2 + 6 * DEV_LANES, lane);
-    const bool need_w = i + 1 < stages, need_p = i + 2 < stages, need_b = !need_p && i + 2 == stages && spec;  // (uniform)
-    // the tableau from its LDS copy (uniform addresses: broadcast reads that queue with the k rows; scalar loads would drain the LDS queue
-    // at every wait): rows i + 1 and i + 2 of A, or h b for the last window of a chained attempt
-    const LdsCPtr row_w = (LdsCPtr)tabl + (need_w ? (i + 1) * DEV_MAX_STAGES : 0);
-    const LdsCPtr row_p = (LdsCPtr)tabl + (need_p ? (i + 2) * DEV_MAX_STAGES : DEV_MAX_STAGES * DEV_MAX_STAGES);
-    double w[3] = {0.0, 0.0, 0.0}, p[3] = {0.0, 0.0, 0.0};
-    double hh = 1.0;
-    bool bad = false;
-    if (need_b) {
-        hh = L.step[DEV_LANES + lane];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] = CS_Y(e);
-    }
-    const bool any_p = need_p || need_b;
-    // one term: w += a_{i+1,j} k_j[3..5];  p += a_{i+2,j} k_j[0..2]  (or (h b_j) k_j[0..2])
-    auto term = [&](const int j) __attribute__((always_inline)) {
-        if (need_w) {
-            const double a_nj = row_w[j];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) w[e] += a_nj * kb0[(j * 6 + 3 + e) * DEV_LANES];
-        }
-        if (any_p) {
-            const double c_nj = need_b ? hh * row_p[j] : row_p[j];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) p[e] += c_nj * kb0[(j * 6 + e) * DEV_LANES];
-        }
-    };
-    if (need_w || any_p) {
-        const int nh = i - 1;  // the terms j < i - 1: their k rows were complete before the barrier this window starts behind
-        int j = 0;
-        for (; j + 4 <= nh; j += 4) {  // four terms per batch: the loads together, the additions in ascending j
-            double cw[4], cp[4], kv[4][6];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                cw[q] = row_w[j + q];
-                cp[q] = row_p[j + q];
-#pragma unroll
-                for (int e = 0; e < 6; ++e) kv[q][e] = kb0[((j + q) * 6 + e) * DEV_LANES];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (need_w) {
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) w[e] += cw[q] * kv[q][3 + e];
-                }
-                if (any_p) {
-                    const double c_nj = need_b ? hh * cp[q] : cp[q];
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) p[e] += c_nj * kv[q][e];
-                }
-            }
-        }
-        for (; j < nh; ++j) term(j);
-        if (i >= 1) {
-            const int want = __builtin_amdgcn_readfirstlane(kdone_v);
-            int spin = 0;
-            while (LCTL[6] < want && ++spin < 4000000) __builtin_amdgcn_s_sleep(1);
-            if (spin >= 4000000) bad = true;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            term(i - 1);
-        }
-    }
-    // (always behind the velocity flag of this window: the integrator reads the previous window's six values in front of integ_front,
-    //  which raises it - the rows are free then)
-    if (flags & 1) {  // (a stage whose velocity integ_front forms in this window; else: stage 0 of an attempt opened behind barriers)
-        int spin = 0;
-        while (LCTL[4] != i + 1 && ++spin < 4000000) __builtin_amdgcn_s_sleep(1);
-        if (spin >= 4000000) bad = true;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-    if (any_p) {
-        const double cv = need_b ? hh * row_p[i] : row_p[i];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] += cv * ysb[(3 + e) * DEV_LANES];
-    }
-    if (bad) {
-        const double qn = __longlong_as_double(0x7ff8000000000000LL);
-#pragma unroll
-        for (int e = 0; e < 3; ++e) { w[e] = qn; p[e] = qn; }
-    }
-#pragma unroll
-    for (int e = 0; e < 3; ++e) { out_w[e * DEV_LANES] = w[e]; out_p[e * DEV_LANES] = p[e]; }
-}
-#endif
 #endif  // INTEG_OOL
 

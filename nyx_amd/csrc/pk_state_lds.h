@@ -7,10 +7,7 @@
 // Pipelined plain loop: what the integrator forms in window i for stage i + 1 - its position, s, t, u, (mu / r) / R_eq, its DCM - is
 // left in LDS and read back in phase A of stage i + 1 instead of being carried in registers across the window's and phase C's calls
 // (coop_post, fold_partials, coop_wait: the ABI keeps 48 VGPRs across a call, the role had ~90 live and spilled the rest to scratch
-// around each of them, every evaluation).  Same values, same bits.
-#ifndef NX_IN_LDS
-#define NX_IN_LDS 1
-#endif
+// around each of them, every evaluation).  Same values, same bits.  (The STM kernels carry them in registers.)
 // timing-only debug switches (NYX_HIP_DEBUG env, never set in production): results are physically wrong
 #define DBG_SKIP_SERIAL 0x100
 #define DBG_SKIP_HARMONICS 0x200

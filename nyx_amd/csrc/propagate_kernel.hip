@@ -124,11 +124,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
     const bool has_srp = cfg->has_srp != 0;
     const bool has_pm = cfg->n_pm > 0;
     const bool has_drag = cfg->has_drag != 0;
-#ifdef NYX_NO_TIDES
-    const bool has_tides = false;
-#else
     const bool has_tides = cfg->has_tides != 0;
-#endif
     const bool has_grav2 = cfg->has_grav2 != 0;  // (plain kernel: value; STM kernels: value and gradient, in either layout)
 #endif
     const bool need_almanac = has_grav || has_drag || has_tides || cfg->n_slots > 0;
@@ -267,18 +263,10 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
     // central gravity field.  The almanac wave with the DCM share holds its write of the next-but-one DCM for the fold counter then.
 #if INTEG_OOL
     constexpr bool ool = PIPE && !STM;   // (a compile-time property of these kernels: the host pipelines a sixteen-wave workgroup only with a gravity field, build_schedule)
-#if defined(NYX_COOP_FAN) && FAN_SUMS
-    // (uniform) fan-out mode: the integrator's two stage sums are formed by a column wave of their own (fan_sums)
-    const bool sums_on = ool && cfg->sums_wave1 != 0;
-    const bool sums_me = sums_on && !INTEG && !ALMANAC && !PERT && cfg->sums_wave1 == wave + 1;
-#else
-    constexpr bool sums_on = false;
-#endif
     const uint32_t lds_base = (uint32_t)(uintptr_t)(LdsPtr)L.kbuf;   // (the carve starts at the k-buffer)
 #define IX_STAMP(k) (int64_t)(((uint64_t)(uint32_t)LCTL[9 + 2 * (k)] << 32) | (uint64_t)(uint32_t)LCTL[8 + 2 * (k)])
 #else
     constexpr bool ool = false;
-    constexpr bool sums_on = false;
 #endif
     bool spec_now = false;  // stage 0 of the attempt being started was published in the previous attempt's last window
     bool keep_k0 = false;   // (integrator, per lane) the previous attempt was rejected: k_0 stands
@@ -306,7 +294,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
 
     auto begin_attempt = [&](ColdState &c) __attribute__((always_inline)) { begin_attempt_fn(L, lane, c); };
     double h_next = 0.0;  // (chained attempts: the step of the attempt step control has just opened)
-#if defined(NYX_COOP_FAN) && FAN_SKIP
+#ifdef NYX_COOP_FAN
     const bool rows_primary = cfg->sched[DEV_SCHED_PRIMARY].n_ranges[wave] > 0, rows_solo = cfg->sched[DEV_SCHED_SOLO].n_ranges[wave] > 0;  // (uniform)
 #endif
 
@@ -421,7 +409,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                         for (int e = 3; e < 6; ++e) ysb[e * DEV_LANES + lane] = ys[e];
                     } else {
                     const double a_last = A_ROW(i, i - 1);
-                    if (!STM && NX_IN_LDS) {  // (the position the previous window published: read back, not carried - see NX_IN_LDS)
+                    if (!STM) {  // (the position the previous window published: read back, not carried - see pk_state_lds.h)
 #pragma unroll
                         for (int e = 0; e < 3; ++e) ys[e] = ysb[e * DEV_LANES + lane];
                     } else {
@@ -446,7 +434,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                             if (es) st_att = es;
                         }
                     }
-                    if (!STM && NX_IN_LDS) {
+                    if (!STM) {
                         if (has_grav) {
                             // s, t, u, (mu / r) / R_eq of this stage from the rows the publishing window left them in (wave 0's slot of the partial
                             // sums: the integrator of a pipelined workgroup carries no columns), its DCM from the epoch data (this parity's
@@ -683,9 +671,6 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                             second_field_into_pert(cfg, rec_in_lds ? (const double *)L.rec : records, edc, lane, wave, ns_to_seconds(ep2), ysp, pertp);
                 }
             }
-#if defined(NYX_COOP_FAN) && FAN_SUMS
-            if (sums_me) fan_sums(lds_base, (uint64_t)cfg, i, lane, (i > 0 || spec_now) ? 1 : 0, fold_base + i);
-#endif
             double acc[3] = {0.0, 0.0, 0.0};
             // The integrator's window.  Round 5: in the pipelined plain loop the position and the recursion inputs of the next stage are
             // formed and POSTED first, everything else (two-body term, the velocity part of the next stage sum, the position part of the
@@ -757,7 +742,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                     inbn[3 * DEV_LANES + lane] = rho;
                     inbn[4 * DEV_LANES + lane] = r_ * cfg->g_inv_re;
                     if (STM && QUAD) publish_d1_inputs(cfg, rb0, rb1, rb2, ql, inbn, lane);
-                    if (!STM && NX_IN_LDS) {
+                    if (!STM) {
                         L.part[0 * DEV_LANES + lane] = nx_s; L.part[1 * DEV_LANES + lane] = nx_t; L.part[2 * DEV_LANES + lane] = nx_u; L.part[3 * DEV_LANES + lane] = nx_kfac;
                     }
                     }
@@ -776,10 +761,6 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
             if (INTEG && fastp && ool) {
                 const bool hot = i > 0 || spec_now;
                 const bool pub = i + 1 < stages || spec;
-                if (sums_on && i > 0) {  // the two sums the sums wave formed in the previous window (behind the stage barrier: complete)
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) { wpre[3 + e] = L.pert[(6 + e) * DEV_LANES + lane]; pre_wr[e] = L.pert2[(6 + e) * DEV_LANES + lane]; }
-                }
                 uint32_t sq = 0;
                 if (pub && coop_on) sq = ++coop_seq;
                 const int64_t pf0_ = prof_on ? (int64_t)__builtin_readcyclecounter() : 0;   // (accounting twin: slot 0 = integ_front, slot 1 = the whole window)
@@ -813,17 +794,8 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                     const double f = -cfg->mu_central / cube(rmag);
                     acc[0] = f * ys[0]; acc[1] = f * ys[1]; acc[2] = f * ys[2];
                 }
-                // the two stage sums (integ_sums): velocity part of the next stage's, position part of the one the NEXT window publishes from
-#if IX_SUMS_OOL
-                {
-                    const IxSums sm = integ_sums(lds_base, (uint64_t)cfg, i, lane, h, ys[3], ys[4], ys[5]);
-                    wpre[0] = wpre[1] = wpre[2] = 0.0;
-                    wpre[3] = sm.w3; wpre[4] = sm.w4; wpre[5] = sm.w5;
-                    if (i + 2 < stages || (i + 2 == stages && spec)) { pre_wr[0] = sm.p0; pre_wr[1] = sm.p1; pre_wr[2] = sm.p2; }
-                }
-#else
-                // (A/B switch: the sums inline, as the first cut of the out-of-line integrator had them)
-                if (!sums_on) {
+                // the two stage sums: velocity part of the next stage's, position part of the one the NEXT window publishes from (inline:
+                // out of line they were measured slower in round 6, 610 ms against 598.5 for 24 h of configs[1])
 #pragma unroll
                 for (int e = 0; e < 6; ++e) wpre[e] = 0.0;
                 if (i + 1 < stages) {
@@ -862,8 +834,6 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
 #pragma unroll
                     for (int e = 0; e < 3; ++e) pre_wr[e] += cbi * ys[3 + e];
                 }
-                }
-#endif
             } else
 #endif
             if (INTEG && fastp && !ool) {
@@ -983,7 +953,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                 const int sched = LCTL[1] ? DEV_SCHED_PRIMARY : DEV_SCHED_SOLO;
                 const double *const inbw = (pipe && (i & 1)) ? L.inb2 : L.inb;
                 Partial4 pr = {0.0, 0.0, 0.0, 0.0};
-#if defined(NYX_COOP_FAN) && FAN_SKIP
+#ifdef NYX_COOP_FAN
                 // (fan-out mode: the owner's waves hold next to no columns, and the walk of a wave WITHOUT columns - five LDS reads, a call,
                 //  the schedule lookup through the scalar cache - is ~2 k cycles per stage on the almanac wave, which bounds the period there)
                 if (!(pipe && INTEG) && (sched == DEV_SCHED_PRIMARY ? rows_primary : rows_solo)) {
@@ -1027,7 +997,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
             // C(i) -> A(i + 1) -> the inputs of stage i + 2, which has ~12 k cycles to spare before the column waves ask for them.  The
             // deadline of a job moves out by that much: the helpers can be loaded further.  (The inputs of this stage in LDS - the
             // fallback's operands - are not overwritten before window i + 1 publishes stage i + 2 into the same parity: behind this point.)
-            if ((!pipe || cfg->coop_late == 0) && !ool) {  // (INTEG_OOL: always collected in phase C)
+            if (!pipe && !ool) {
                 const int64_t w0_ = prof_on ? (int64_t)__builtin_readcyclecounter() : 0;
                 COOP_COLLECT()
                 if (prof_on && INTEG) { pl_tc = (int64_t)__builtin_readcyclecounter(); pl_wait += pl_tc - w0_; }
@@ -1060,10 +1030,6 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                     if (coop_on) { ++dbg_fallbacks; dbg_fb_seq = seq_cur; }
                     const Partial4 fb = coop_fallback((uint64_t)cfg, (uint64_t)htab, (uint64_t)cols, (i & 1) ? L.inb2 : L.inb, lane | COOP_FB_PARTS);
                     integ_back_slow(lds_base, (uint64_t)cfg, (uint64_t)records, i, lane, acc[0], acc[1], acc[2], rb_.px, rb_.py, rb_.pz, rb_.pw, fb.x, fb.y, fb.z, fb.w, skip_k);
-                    if (sums_on) {  // (k_i is written: see integ_back)
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (lane == 0) LCTL[6] = fold_base + i + 1;
-                    }
                     coop_on = false;  // (pipelined: ctl[1] is rewritten for every stage, nothing to undo)
                     if (lane == 0) coop_store(bt.coop_finished + coop_widx, 1u);
                 }
@@ -1096,7 +1062,7 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
                         if (lane == 0) LCTL[3] = fold_base + i + 1;
                     }
                     SEG(8)   /* phase C up to the fold */
-                    if (pipe && cfg->coop_late != 0) {
+                    if (pipe) {
                         const int64_t w0_ = prof_on ? (int64_t)__builtin_readcyclecounter() : 0;
                         COOP_COLLECT()
                         SEG(9)   /* the answer */
@@ -1252,9 +1218,6 @@ DEVFN void role_loop(const DevBatch &bt, CfgPtr cfg, const DevCfg *cfg_g, HarmPt
             double next[9], err[9];
 #pragma unroll
             for (int e = 0; e < 9; ++e) { next[e] = y[e]; err[e] = 0.0; }
-#if STEP_SUMS_UNROLL
-#pragma unroll STEP_SUMS_UNROLL
-#endif
             for (int i = 0; i < stages; ++i) {
                 const double ce = h * BD_COEF(i);
                 const double cb = h * B_COEF(i);

@@ -150,6 +150,33 @@ def test_ctx_create_refuses_what_the_device_code_cannot_represent():
         assert rc in (0, _abi.RC_NO_DEVICE), msg
 
 
+LIVE_DEBUG_FLAGS = (0x100, 0x200, 0x400, 0x800, 0x4000, 0x8000, 0x10000, 0x80000, 0x100000, 0x2000000, 0x4000000, 0x8000000, 0x20000000)
+RETIRED_DEBUG_FLAGS = (0x1000, 0x2000, 0x20000, 0x40000, 0x200000, 0x400000, 0x800000, 0x1000000, 0x10000000, 0x40000000)
+
+
+def test_ctx_create_refuses_retired_debug_flags():
+    """A debug_flags bit whose A/B path was retired is an error that names the bit, never a silent run of the default path;
+    the live bits get past the same validation."""
+    prop, almanac, central = leo_full_setup(degree=4)
+
+    def with_flags(flags):
+        cc = prop.compile(almanac, central)
+        tuning = nx.Tuning(debug_flags=flags)
+        cc.cfg.tuning = C.pointer(tuning)
+        return _create_rc(cc)
+
+    for bit in RETIRED_DEBUG_FLAGS:
+        rc, msg = with_flags(bit)
+        assert rc == _abi.RC_BAD_ARG and f"0x{bit:x}" in msg, (hex(bit), msg)
+        rc, msg = with_flags(bit | 0x800 | 0x8000)  # (beside live bits too)
+        assert rc == _abi.RC_BAD_ARG and f"0x{bit:x}" in msg, (hex(bit), msg)
+    live = 0
+    for bit in LIVE_DEBUG_FLAGS:
+        live |= bit
+    rc, msg = with_flags(live)
+    assert rc in (0, _abi.RC_NO_DEVICE), msg
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("ncoef", [16, 26, 32])
 def test_wide_coefficient_segments_device_vs_oracle(ncoef):

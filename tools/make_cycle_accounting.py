@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""profiles/round06_cycle_accounting.md from the logs of tools/r6_call20.sh (gpurun_out/r6_cycle_accounting.log: one tools/sweep.py run per
-workload, product kernel and accounting twin) - the header states what the tables are, the numbers are read off the tables themselves.
+"""profiles/round06_cycle_accounting.md from the log of one tools/sweep.py run per workload, product kernel and accounting twin
+(r6_cycle_accounting.log) - the header states what the tables are, the numbers are read off the tables themselves.
 usage: tools/make_cycle_accounting.py [out.md]"""
 import os
 import re
