@@ -11,6 +11,7 @@
 #include <array>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -20,7 +21,7 @@
 #include "../../include/nyx_hip.h"
 #include "butcher.h"
 #include "devcfg.h"
-#include "col_partition.h"
+#include "launch_plan.h"
 #include "predict_args.h"
 #include "traj_args.h"
 #include "moments_args.h"
@@ -102,7 +103,7 @@ struct nyx_hip_ctx {
     ColHdr *d_cols2 = nullptr;
     double *d_hyb = nullptr;  // the same table in the hybrid-feed layout (devcfg.h HYB_*)
     // Run streams (DevCfg.rs_*): the table once more per column schedule - [0] SOLO, [1] PRIMARY, [2] the helpers' - with every RANGE of
-    // a wave starting a sixteen-row group of its own.  Rebuilt when a schedule changes (build_schedule sets rs_dirty), uploaded by
+    // a wave starting a sixteen-row group of its own.  Rebuilt when a schedule changes (launch() sets rs_dirty), uploaded by
     // launch() before a launch that streams the table.
     std::vector<HarmEntry> h_tab;  // host copy of the entry table (without its tail padding)
     std::vector<ColHdr> h_cols;
@@ -117,21 +118,13 @@ struct nyx_hip_ctx {
     std::vector<int32_t> col_len;  // rows per column (index = c)
     int n_waves = 1;
     int forced_waves = 0;
-    bool sched_quad = false;  // the schedule / roles in host_cfg were built for the quad layout
+    SchedShape shape;         // what the schedules in host_cfg were built for (launch_plan.h)
     bool sched_dirty = false; // weights changed: rebuild the schedule at the next launch
-    // Per-wave column weights, calibrated on this device for every workgroup shape this context has launched (see calibrate()):
-    // key = (waves per workgroup, pipelined loop, quad layout, cooperative share in tenths or -1 when working alone)
-    typedef std::tuple<int, int, int, int> WKey;
-    std::map<WKey, std::array<double, 2 * DEV_MAX_WAVES>> weights;  // [0..16): speed weights, [16..32): measured duties (harmonics-term units)
+    WeightMap weights;        // per-wave column weights, calibrated on this device per workgroup shape (see calibrate())
     std::map<WKey, double> weight_spread;  // (max - min) / mean of the per-wave windows after calibration
     WKey last_key = WKey(0, 0, 0, 0);      // shape of the last launch
     DevArrays cal;                         // scratch outputs of the calibration launches
-    bool block_schedule = true;  // one contiguous run of columns per wave where the owner streams the table (fill_schedule)
-    bool fit_partition = true;   // ... placed along the column list in a free wave order so that every wave meets its target (fill_schedule)
-    bool block_force = false;
-    int coop_parts = 1;  // sub-jobs per evaluation of the schedules in host_cfg (1, or 2: two helper workgroups per owner and evaluation; fan-out: 2 .. DEV_FAN_MAX)
     const PredictArgs *fused_pred = nullptr;  // set around the ONE launch of a fused covariance-mapping loop (nyx_hip_predict_until): DEVICE copy of its arguments
-    bool coop_fan = false;  // the schedules in host_cfg are those of the fan-out mode: coop_parts DEDICATED helper workgroups per owner (small shards, see launch())
     int forced_quad = -1;  // STM layout: -1 = by ensemble size, 0 = 64 trajectories x D3 per workgroup, 1 = quad layout (16 x 4 lanes, D1)
     double role_handicap[3] = {0.0, 0.0, 0.0};  // integrator, almanac, perturbations (harmonics-term units)
     DevArrays in, out;
@@ -439,627 +432,9 @@ static void build_run_stream(const nyx_hip_ctx *ctx, std::initializer_list<int> 
     build_hybrid(t, hyb, vec_off);
 }
 
-// Column schedule: wave w walks at most two contiguous ranges — long columns from the low-c end,
-// topped up with short columns from the high-c end — so that one complex power per range suffices.
-// Waves 0/1/2 also carry the integrator / almanac / perturbation duties (`role_handicap`, in units of
-// one harmonics term), so they receive a reduced share of the columns, possibly none.
-// Water-filling of the columns [c_lo, c_hi] over `n_waves` waves with per-wave handicaps hc[] (work a wave does besides
-// its columns, in harmonics-term units) and SIMD age weights.  Wave 0 takes what is left.
-// `list`: the columns to distribute, ascending (= longest first).  Returns false if a wave would need more than
-// DEV_MAX_RANGES contiguous ranges.
-static bool fill_schedule(const nyx_hip_ctx *ctx, DevSched &sd, int n_waves, const std::vector<int> &list, const double *hc_model,
-                          bool all_columns) {
-    double hc[DEV_MAX_WAVES];
-    for (int w = 0; w < DEV_MAX_WAVES; ++w) hc[w] = hc_model[w];
-    for (int w = 0; w < DEV_MAX_WAVES; ++w) sd.n_ranges[w] = 0;
-    if (list.empty()) return true;
-    // cost of a column in rows: its length plus what it costs to START one (header, complex power of the range, a cold first batch).
-    // With the short columns of a small field in the quad layout that start is most of a column: 21x21, 1 000 trajectories, sixty
-    // segments: 11.45 ms with 0 rows, 11.1 with 4, 10.83 with 6, 10.95 with 8 (four runs each, +-0.03).  70x70 plain kernel: no effect
-    // up to 6, slower beyond (the measured per-wave weights already carry it there).  Round 4, with the roles fanned out over eight of
-    // the sixteen waves: 6 rows left the oldest pure column wave without a column (the two-ended fill ran out of columns before it
-    // reached wave 4) and the youngest ones with the longest; config 4, three runs each: 10.10 ms with 6, 9.83 with 8, 9.55-9.60 with
-    // 9 ... 18 (a plateau: every wave holds one or two columns then) - same bits, the quad layout's sums do not depend on the split.
-    double col_fix = (ctx->sched_quad && n_waves == DEV_MAX_WAVES) ? 12.0 : 0.0;  // (the quad layout's production shape: sixteen waves)
-    if (ctx->tune.column_start_cost >= 0.0) col_fix = ctx->tune.column_start_cost;
-    auto cost = [&](int c) { return (double)ctx->col_len[c] + col_fix; };
-    double terms = 0.0;
-    for (int c : list) terms += cost(c);
-    // Per-wave weights.  The four waves that share a SIMD (w, w+4, w+8, w+12) are arbitrated oldest-first, so with equal
-    // shares the oldest finishes early and the youngest runs the tail alone, with nothing to hide its scalar-load latency;
-    // role waves carry their duty besides.  The weights are MEASURED: calibrate() runs the workload's own first steps with
-    // the in-kernel cycle accounting and moves columns from the late waves to the early ones until the windows agree;
-    // before that (and with calibration off) a structural guess by age class is used.
-    double per_wave[DEV_MAX_WAVES];
-    bool fit = false;  // (the runs of a block schedule placed along the list in a free wave order: the cooperative 70x70 shape, see below)
-    {
-        const nyx_hip_ctx::WKey key(n_waves, (ctx->host_cfg.pipe && (!(ctx->host_cfg.flags & NYX_HIP_FLAG_STM) || ctx->sched_quad)) ? 1 : 0, ctx->sched_quad ? 1 : 0,
-                                    all_columns ? -1 : (int)(ctx->host_cfg.coop_frac * 10.0 + 0.5));
-        const auto it = ctx->weights.find(key);
-        // The cost model of NYX_HIP_SCHED_MODEL: the speed of a wave is a property of its place in the workgroup (the four waves of a
-        // SIMD are arbitrated oldest first; role waves and their SIMD-mates run differently) and of the workgroup's shape, not of
-        // the force model.  Measured once with the calibration below on the BASELINE workloads (tools/dump_weights.py, two contexts
-        // each, agreement ~2 %) and frozen here, so that the default schedule - hence the summation order, hence every bit of the
-        // result - is the same in every context, process and rank.
-        static const double model_coop[16] = {1.70, 1.66, 1.48, 2.14, 2.08, 1.70, 1.65, 1.67, 1.45, 0.97, 1.05, 1.02, 0.70, 0.53, 0.56, 0.55};
-        static const double model_solo[16] = {1.41, 1.41, 1.26, 1.61, 1.59, 1.29, 1.375, 1.23, 1.06, 0.98, 0.98, 0.98, 0.77, 0.69, 0.70, 0.70};
-        // (quad table, round 5: re-fitted by hill-climbing the explicit weights on config 4 with the position-only pieces of phase C on
-        //  the DCM wave (assign_roles, DEV_ROLE_QPRE) - with the integrator's window shorter the column waves are the period again:
-        //  8.99 ms with the round-4 table {0.70 x 4, 1.26, 2.03, 1.78, 1.59, 1.58, 1.68, 0.96, 1.02, 0.875, 0.93, 0.86, 0.91}, 8.61 with this)
-        static const double model_quad[16] = {0.700, 0.700, 0.505, 0.876, 1.173, 1.490, 1.795, 2.380, 3.445, 2.528, 0.927, 1.020, 0.875, 0.930, 0.941, 1.124};
-        // Round 4, the shapes that deal ONE contiguous run of columns per wave (below) and stream the table in the trajectory-owning
-        // workgroups: fitted with tools/tune_schedule.py (windows of every wave -> rows that would equalise them -> weights, best
-        // kernel time of 8-14 iterations, two boxes) on configs[1] at 10 000 (cooperative) and 16 384 trajectories (alone) and on
-        // configs[4] (150x150, cooperative, helper jobs of several columns).  The role duties of the water-filling are unchanged.
-        // (cooperative 70x70 table: fitted on the FULL day of configs[1] - the perturbation wave's duty grows over the day, 14 k -> 20 k cycles
-        //  per evaluation once the lanes' eclipse transitions no longer coincide, and a table fitted on the first three hours overloaded it:
-        //  719 -> 680 ms per 10 000 x 24 h, same box)
-        static const double model_coop_blk[16] = {1.00, 1.413, 0.549, 1.946, 1.892, 1.523, 1.588, 1.292, 1.066, 0.828, 0.937, 0.692, 0.430, 0.347, 0.357, 0.142};
-        static const double model_coop_big_blk[16] = {1.00, 1.755, 1.706, 1.802, 1.733, 1.22, 1.246, 1.181, 1.087, 0.672, 0.621, 0.604, 0.549, 0.279, 0.284, 0.255};
-        static const double model_solo_blk[16] = {1.00, 1.612, 1.263, 1.906, 1.764, 1.346, 1.331, 1.198, 1.113, 0.757, 0.659, 0.568, 0.513, 0.398, 0.291, 0.27};
-        // Round 5, the cooperative 70x70 shape with its runs placed in a free wave order (`fit`, below): the column waves' weights as
-        // tools/tune_schedule.py settles on them with that partition (full day of configs[1]; the role waves keep the table's values -
-        // every row more on them costs the integrator's chain: 614 ms with these, 662 with ten rows more on each of the two).
-        // Same box, product kernel, 24 h: 625.0 ms linear partition, 617.0 free order with the old table, 614.0 with this one.
-        static const double model_coop_fit[16] = {1.00, 1.413, 0.549, 1.95, 1.83, 1.48, 1.40, 1.23, 1.04, 0.88, 0.85, 0.62, 0.50, 0.36, 0.34, 0.16};
-        const bool blk = ctx->block_schedule && n_waves == DEV_MAX_WAVES && !ctx->sched_quad && ((ctx->host_cfg.harm_feed & 1) || ctx->block_force);
-        fit = blk && !all_columns && ctx->host_cfg.n_cols <= 96 && ctx->fit_partition;
-        const double *model = ctx->sched_quad ? model_quad
-                              : (blk ? (all_columns ? model_solo_blk : (ctx->host_cfg.n_cols > 96 ? model_coop_big_blk : (fit ? model_coop_fit : model_coop_blk)))
-                                     : (all_columns ? model_solo : model_coop));
-        for (int w = 0; w < DEV_MAX_WAVES; ++w)
-            per_wave[w] = it != ctx->weights.end() ? it->second[w] : (n_waves == 16 ? model[w] : 1.0);
-        if (it != ctx->weights.end())  // measured duties replace the model's (the integrator keeps its window free: hc_model[0])
-            for (int w = 0; w < n_waves; ++w)
-                if (hc_model[w] < 1e8) hc[w] = it->second[DEV_MAX_WAVES + w];
-    }
-    if (ctx->tune.schedule == NYX_HIP_SCHED_EXPLICIT) {  // explicit weights: per wave, or one per SIMD age class
-        const bool per = any_nonzero(ctx->tune.wave_weights, 16), age_on = any_nonzero(ctx->tune.age_weights, 4);
-        for (int w = 0; w < DEV_MAX_WAVES; ++w) {
-            if (per) per_wave[w] = ctx->tune.wave_weights[w];
-            else if (age_on && n_waves == 16) per_wave[w] = ctx->tune.age_weights[w / 4];
-        }
-    }
-    auto wgt = [&](int w) { return per_wave[w]; };
-    // water-filling: level such that sum_w max(0, level * weight_w - hc[w]) = terms
-    double level = 0.0;
-    {
-        double hsum = 0.0;
-        for (int w = 0; w < n_waves; ++w) hsum += std::min(hc[w], 1e6);
-        double lo = 0.0, hi = 4.0 * (terms + hsum);
-        for (int it = 0; it < 80; ++it) {
-            level = 0.5 * (lo + hi);
-            double sum = 0.0;
-            for (int w = 0; w < n_waves; ++w) sum += std::max(0.0, level * wgt(w) - hc[w]);
-            if (sum < terms) lo = level; else hi = level;
-        }
-    }
-    if ((ctx->block_schedule && n_waves == DEV_MAX_WAVES && !ctx->sched_quad && ((ctx->host_cfg.harm_feed & 1) || ctx->block_force)) || (fit && ctx->sched_quad)) {
-        // ONE contiguous run of columns per wave (the hybrid stream walks a run as one piece of the table: every range START costs it a
-        // pipeline fill, the complex power of the range and up to seven rows in front of the run - with two or three ranges per wave
-        // and evaluation that is a third of a 70x70 owner's work).  Linear partition of the list (longest columns first) at the
-        // cumulative targets; the waves with the largest targets take the long columns, role waves the short ones at the end, where
-        // the granularity is finest.  The integrator wave (target 0 in the pipelined loop) gets nothing.
-        std::vector<int> order;
-        for (int w = 0; w < n_waves; ++w) order.push_back(w);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::max(0.0, level * wgt(a) - hc[a]) > std::max(0.0, level * wgt(b) - hc[b]); });
-        if (fit) {
-            // Round 5, the same contiguous runs in a FREE wave order.  The linear partition above deals whole columns at the cumulative
-            // targets in descending target order, so a wave's load is off by up to half a column - +-25 rows of ~230 for the waves
-            // that hold the 50-row columns of a 70x70 owner, and a column wave is bound by its OWN issue rate (one VALU instruction per
-            // ~9 cycles and wave, tools/_exp/exec_rate.hip): the two or three waves rounded UP set the workgroup's period.  A run of j
-            // columns starting at length L sums to jL - j(j-1)/2: which sums exist depends on WHERE in the list a run sits, so the
-            // waves are placed along the list in whatever order lets every one of them meet its target - a depth-first search over
-            // (columns consumed, waves placed) for the smallest tolerance D with |load_w - target_w| <= D * weight_w for every wave
-            // (the weight is the wave's speed: the same TIME error everywhere; col_partition.h).  A pure function of the configuration, like the rest.
-            std::vector<int> act;
-            for (int w : order) if (std::max(0.0, level * wgt(w) - hc[w]) > 0.0) act.push_back(w);
-            std::vector<double> cst, tg, wg;
-            for (int c : list) cst.push_back(cost(c));
-            for (int w : act) { tg.push_back(std::max(0.0, level * wgt(w) - hc[w])); wg.push_back(wgt(w)); }
-            std::vector<int> seq_w, seq_k;   // the placement found: wave index (into act) and its first column, in list order
-            const bool found = nyx_place_runs(cst, tg, wg, seq_w, seq_k);
-            if (found) {
-                for (size_t q = 0; q < seq_w.size(); ++q) {
-                    const int w = act[seq_w[q]];
-                    const size_t k0 = (size_t)seq_k[q], k1 = q + 1 < seq_w.size() ? (size_t)seq_k[q + 1] : list.size();
-                    int nr = 0;
-                    for (size_t a = k0; a < k1;) {
-                        size_t e = a + 1;
-                        while (e < k1 && list[e] == list[e - 1] + 1) ++e;
-                        if (nr >= DEV_MAX_RANGES) return false;
-                        sd.range_c0[w][nr] = list[a]; sd.range_cnt[w][nr] = (int)(e - a); ++nr;
-                        a = e;
-                    }
-                    sd.n_ranges[w] = nr;
-                }
-                return true;
-            }
-            // (no placement within the widest tolerance: the linear partition below)
-        }
-        double cum_t = 0.0, cum_r = 0.0;
-        size_t k = 0;
-        for (size_t q = 0; q < order.size(); ++q) {
-            const int w = order[q];
-            cum_t += std::max(0.0, level * wgt(w) - hc[w]);
-            const size_t k0 = k;
-            const bool last = q + 1 == order.size() || std::max(0.0, level * wgt(order[q + 1]) - hc[order[q + 1]]) <= 0.0;
-            while (k < list.size() && (last || cum_r + 0.5 * cost(list[k]) <= cum_t)) { cum_r += cost(list[k]); ++k; }
-            if (k > k0) {
-                // (the list is ascending in column number but may have gaps - the helper's columns: split the run at every gap)
-                int nr = 0;
-                for (size_t a = k0; a < k;) {
-                    size_t e = a + 1;
-                    while (e < k && list[e] == list[e - 1] + 1) ++e;
-                    if (nr >= DEV_MAX_RANGES) return false;
-                    sd.range_c0[w][nr] = list[a]; sd.range_cnt[w][nr] = (int)(e - a); ++nr;
-                    a = e;
-                }
-                sd.n_ranges[w] = nr;
-            }
-            if (last) break;
-        }
-        return true;
-    }
-    int lo = 0, hi = (int)list.size() - 1;  // indices into `list`
-    // plain column workers first (highest wave index), role waves last so they take what is left
-    // (round 6: what is left goes to the last wave that WALKS columns - the integrator wave of a pipelined workgroup walks none (hc = 1e9),
-    //  and a list of two or three short columns, the owner's share in the fan-out mode of a field below degree 40, is all "left over":
-    //  dealt to wave 0 it was never evaluated - 59 m after two hours, tests/test_gpu_rotation.py)
-    const int last_w = (hc[0] >= 1e8 && n_waves > 1) ? 1 : 0;
-    for (int w = n_waves - 1; w >= last_w; --w) {
-        const double tgt = std::max(0.0, level * wgt(w) - hc[w]);
-        std::vector<int> mine;
-        if (w == last_w) {
-            for (int k = lo; k <= hi; ++k) mine.push_back(list[k]);
-            lo = hi + 1;
-        } else {
-            double load = 0.0;
-            while (lo <= hi && load + 0.5 * cost(list[lo]) <= tgt) { load += cost(list[lo]); mine.push_back(list[lo++]); }
-            std::vector<int> tail;
-            while (lo <= hi && load + 0.5 * cost(list[hi]) <= tgt) { load += cost(list[hi]); tail.push_back(list[hi--]); }
-            mine.insert(mine.end(), tail.rbegin(), tail.rend());
-        }
-        // contiguous runs of column numbers -> ranges
-        int nr = 0;
-        for (size_t k = 0; k < mine.size();) {
-            size_t e = k + 1;
-            while (e < mine.size() && mine[e] == mine[e - 1] + 1) ++e;
-            if (nr >= DEV_MAX_RANGES) return false;
-            sd.range_c0[w][nr] = mine[k]; sd.range_cnt[w][nr] = (int)(e - k); ++nr;
-            k = e;
-        }
-        sd.n_ranges[w] = nr;
-        if (w == last_w) break;
-    }
-    return true;
-}
-
-// Role fan-out (small ensembles: the STM quad layout, and dynamics without a gravity field): with few workgroups on the
-// chip what counts is the latency of ONE force evaluation, and the almanac and perturbation duties are its longest serial
-// pieces.  They are dealt over several waves - the DCM and the body slots (or the distinct ephemeris segments, fanout_almanac_units) over up to DEV_MAX_ALM almanac waves (longest
-// first), point masses (+ tides) and SRP (+ drag) over two perturbation waves - each writing its own LDS rows, so the
-// arithmetic and its order do not change.  Costs in harmonics-term units, as `role_handicap`.
-// Units of the almanac duty: the DCM, then either the DISTINCT ephemeris segments of all chains (segment mode: Earth -> EMB sits on
-// every chain of an Earth-centred run and is evaluated once; the readers sum the chains, ed_bp() in the kernel) when their vectors
-// fit the body rows of the epoch data - 4 with a DCM, 7 without - or the body slots.
-static int distinct_segments(const DevCfg &dc, int *useg_seg = nullptr) {
-    int n = 0, list[DEV_MAX_SEG];
-    for (int s = 0; s < dc.n_slots; ++s)
-        for (int k = 0; k < dc.slot[s].n_chain; ++k) {
-            bool seen = false;
-            for (int q = 0; q < n; ++q) seen = seen || list[q] == dc.slot[s].seg[k];
-            if (!seen && n < DEV_MAX_SEG) list[n++] = dc.slot[s].seg[k];
-        }
-    if (useg_seg) for (int q = 0; q < n; ++q) useg_seg[q] = list[q];
-    return n;
-}
-static bool segment_units_fit(const DevCfg &dc) {
-    const bool dcm = dc.has_grav || dc.has_drag || dc.has_tides;
-    const int nu = distinct_segments(dc);
-    return nu >= 2 && nu <= (dcm ? DEV_MAX_SLOTS : DEV_MAX_SLOTS + 3);
-}
-static int fanout_almanac_units(const DevCfg &dc, int *unit_mask, double *unit_cost) {
-    int n = 0;
-    if (dc.has_grav || dc.has_drag || dc.has_tides) { unit_mask[n] = DEV_ROLE_DCM; unit_cost[n] = 18.0; ++n; }
-    if (segment_units_fit(dc)) {
-        int us[DEV_MAX_SEG];
-        const int nu = distinct_segments(dc, us);
-        for (int u = 0; u < nu; ++u) { unit_mask[n] = 1 << u; unit_cost[n] = 3.0 + 0.75 * dc.seg[us[u]].n_coef; ++n; }
-        return n;
-    }
-    for (int s = 0; s < dc.n_slots; ++s) { unit_mask[n] = 1 << s; unit_cost[n] = 12.0 * dc.slot[s].n_chain; ++n; }
-    return n;
-}
-static bool want_fanout(const nyx_hip_ctx *ctx, bool quad) {
-    if (ctx->tune.role_fanout >= 0) return ctx->tune.role_fanout != 0;
-    return quad || !ctx->host_cfg.has_grav;
-}
-static int fanout_role_waves(const nyx_hip_ctx *ctx, int *n_alm_out = nullptr, int *n_pert_out = nullptr) {
-    const DevCfg &dc = ctx->host_cfg;
-    int um[10]; double uc[10];
-    const int units = fanout_almanac_units(dc, um, uc);
-    const int n_alm = std::min(DEV_MAX_ALM, std::max(units, 0));
-    const int n_pert = ((dc.n_pm > 0 || dc.has_tides || dc.has_grav2) ? 1 : 0) + ((dc.has_srp || dc.has_drag) ? 1 : 0);
-    if (n_alm_out) *n_alm_out = n_alm;
-    if (n_pert_out) *n_pert_out = n_pert;
-    return 1 + n_alm + n_pert;
-}
-
-// Deals the roles of an n_waves workgroup (DevCfg.role_*) and returns the serial duty of every wave in `hc`.
-static void assign_roles(nyx_hip_ctx *ctx, int n_waves, bool fanout, double *hc) {
-    DevCfg &dc = ctx->host_cfg;
-    const int all_alm = DEV_ROLE_DCM | ((1 << dc.n_slots) - 1);
-    const int all_pert = (DEV_PERT_PM | DEV_PERT_SRP) << 16;
-    for (int w = 0; w < DEV_MAX_WAVES; ++w) { dc.role_kind[w] = DEV_ROLE_COLUMNS; dc.role_mask[w] = 0; dc.role_slot[w] = 0; hc[w] = 0.0; }
-    dc.n_alm = 1;
-    dc.seg_mode = 0;
-    dc.offload = 0;
-    dc.qpre_off = 0;
-    const double *rh = ctx->role_handicap;
-    if (n_waves == 1) { dc.role_kind[0] = DEV_ROLE_ALL; dc.role_mask[0] = all_alm | all_pert; hc[0] = rh[0] + rh[1] + rh[2]; return; }
-    dc.role_kind[0] = DEV_ROLE_INTEG; hc[0] = rh[0];
-    if (n_waves == 2 || dc.merge_roles) { dc.role_kind[1] = DEV_ROLE_ALMANAC_PERT; dc.role_mask[1] = all_alm | all_pert; hc[1] = rh[1] + rh[2]; return; }
-    int n_alm = 1, n_pert = 1;
-    if (fanout && fanout_role_waves(ctx, &n_alm, &n_pert) <= n_waves && n_alm >= 1 && n_pert >= 1) {
-        const bool stm = (dc.flags & NYX_HIP_FLAG_STM) != 0;
-        // the duties: almanac shares (longest unit first onto the least loaded share), then the perturbation shares
-        struct Duty { int kind, mask, slot; double cost; };
-        std::vector<Duty> duties;
-        {
-            int um[10]; double uc[10];
-            const int units = fanout_almanac_units(dc, um, uc);
-            int order[10];
-            for (int k = 0; k < units; ++k) order[k] = k;
-            std::sort(order, order + units, [&](int a, int b) { return uc[a] > uc[b]; });
-            double load[DEV_MAX_ALM] = {0.0};
-            int amask[DEV_MAX_ALM] = {0};
-            for (int k = 0; k < units; ++k) {
-                int best = 0;
-                for (int a = 1; a < n_alm; ++a) if (load[a] < load[best]) best = a;
-                amask[best] |= um[order[k]];
-                load[best] += uc[order[k]];
-            }
-            for (int a = 0; a < n_alm; ++a) duties.push_back({DEV_ROLE_ALMANAC, amask[a], a, load[a]});
-            dc.n_alm = n_alm;
-        }
-        // (measured on the device, in units of ~250 cycles: a plain point mass 4, a dual one 11; SRP with its occultation 12 + 8 per
-        //  shadow body, dual 25 + 25; drag 10; tides 14 + 8 per perturber)
-        const double pm_cost = (stm ? 11.0 : 4.0) * dc.n_pm + (dc.has_tides ? (stm ? 3.0 : 1.0) * (14.0 + 8.0 * dc.t_n) : 0.0) +
-                               (dc.has_grav2 ? 8.0 + 0.2 * ctx->terms2 : 0.0);
-        const double srp_cost = (dc.has_srp ? (stm ? 25.0 + 25.0 * dc.n_shadow : 12.0 + 8.0 * dc.n_shadow) : 0.0) + (dc.has_drag ? 10.0 : 0.0);
-        if (n_pert == 2) {
-            duties.push_back({DEV_ROLE_PERT, DEV_PERT_PM << 16, 0, pm_cost});
-            duties.push_back({DEV_ROLE_PERT, DEV_PERT_SRP << 16, 0, srp_cost});
-        } else {
-            duties.push_back({DEV_ROLE_PERT, all_pert, 0, pm_cost + srp_cost});
-        }
-        // Placement: wave w runs on SIMD w % 4, and a force evaluation is bound by the busiest SIMD's role work (the role code
-        // is VALU-heavy: sincos, Chebyshev chains, divisions).  Heaviest duty first onto the least loaded SIMD; the integrator
-        // (wave 0, ~50 units with its phases A and C) sits on SIMD 0.
-        double simd_load[4] = {stm ? 52.0 : 26.0, 0.0, 0.0, 0.0};
-        bool taken[DEV_MAX_WAVES] = {true};
-        std::sort(duties.begin(), duties.end(), [](const Duty &a, const Duty &b) { return a.cost > b.cost; });
-        bool placed_all = true;
-        for (const Duty &d : duties) {
-            int best_w = -1;
-            double best_load = 1e300;
-            for (int sd = 0; sd < 4; ++sd) {
-                int w = -1;
-                for (int k = sd; k < n_waves; k += 4) if (!taken[k]) { w = k; break; }
-                if (w >= 0 && simd_load[sd] < best_load) { best_load = simd_load[sd]; best_w = w; }
-            }
-            if (best_w < 0) { placed_all = false; break; }
-            taken[best_w] = true;
-            simd_load[best_w % 4] += d.cost;
-            dc.role_kind[best_w] = d.kind; dc.role_mask[best_w] = d.mask; dc.role_slot[best_w] = d.slot; hc[best_w] = d.cost;
-        }
-        if (placed_all) {
-            if (dc.pipe && !dc.has_grav && !stm && (ctx->tune.debug_flags & 0x800)) {  // (0x800: A/B switch, same results)
-                // pipelined, no column waves: the two lightest almanac shares take the two-body term and the head of the stage sums off
-                // the integrator wave (DevCfg.offload).  Rounds 3-4 default; OFF since round 5: the integrator's publish-first window
-                // (role_loop, `fastp`) is shorter than the offloaded one and the almanac SIMDs are the busiest of the workgroup
-                // (config 3: 46.7 -> 44.7 ms without it, same bits)
-                // (what an almanac wave has to spare depends on whom it shares its SIMD with: the integrator's SIMD last, then by the SIMD's load)
-                int w1 = -1, w2 = -1;
-                auto spare = [&](int w) { return (w % 4 == 0 ? 1e6 : 0.0) + simd_load[w % 4] + hc[w]; };
-                for (int w = 1; w < n_waves; ++w) {
-                    if (dc.role_kind[w] != DEV_ROLE_ALMANAC) continue;
-                    if (w1 < 0 || spare(w) < spare(w1)) { w2 = w1; w1 = w; }
-                    else if (w2 < 0 || spare(w) < spare(w2)) w2 = w;
-                }
-                if (w1 >= 0) {
-                    if (w2 < 0) w2 = w1;
-                    dc.role_mask[w1] |= DEV_ROLE_SUMS; hc[w1] += 4.0;
-                    dc.role_mask[w2] |= DEV_ROLE_TWOBODY; hc[w2] += 2.0;
-                    dc.offload = 1;
-                }
-            }
-            if (stm && ctx->sched_quad && !(ctx->tune.debug_flags & 0x4000000)) {  // (0x4000000: A/B switch, same results)
-                // quad STM layout: the position-only pieces of phase C (quad_pre, 4-5 k cycles of the integrator's window per evaluation)
-                // go to the almanac wave with the most time to spare - the integrator's chain is what bounds such a workgroup
-                // (the wave that holds the DCM when there is one: in the sixteen-wave shape it walks no columns, the segment waves do)
-                int wq = -1;
-                for (int w = 1; w < n_waves; ++w)
-                    if (dc.role_kind[w] == DEV_ROLE_ALMANAC && (dc.role_mask[w] & DEV_ROLE_DCM)) wq = w;
-                if (wq < 0)
-                    for (int w = 1; w < n_waves; ++w) {
-                        if (dc.role_kind[w] != DEV_ROLE_ALMANAC) continue;
-                        if (wq < 0 || simd_load[w % 4] + hc[w] < simd_load[wq % 4] + hc[wq]) wq = w;
-                    }
-                if (wq >= 0) { dc.role_mask[wq] |= DEV_ROLE_QPRE; hc[wq] += 18.0; simd_load[wq % 4] += 18.0; dc.qpre_off = 1; }
-            }
-            if (segment_units_fit(dc)) {  // the almanac shares above are distinct segments: tell the kernel where their vectors live
-                dc.seg_mode = 1;
-                dc.n_useg = distinct_segments(dc, dc.useg_seg);
-                dc.ed_seg_base = (dc.has_grav || dc.has_drag || dc.has_tides) ? 9 : 0;
-                for (int sl = 0; sl < dc.n_slots; ++sl)
-                    for (int k = 0; k < dc.slot[sl].n_chain; ++k)
-                        for (int u = 0; u < dc.n_useg; ++u)
-                            if (dc.useg_seg[u] == dc.slot[sl].seg[k]) dc.slot[sl].useg[k] = u;
-            }
-            return;
-        }
-        for (int w = 1; w < DEV_MAX_WAVES; ++w) { dc.role_kind[w] = DEV_ROLE_COLUMNS; dc.role_mask[w] = 0; dc.role_slot[w] = 0; hc[w] = 0.0; }
-        dc.n_alm = 1;
-    }
-    dc.role_kind[1] = DEV_ROLE_ALMANAC; dc.role_mask[1] = all_alm; hc[1] = rh[1];
-    dc.role_kind[2] = DEV_ROLE_PERT; dc.role_mask[2] = all_pert; hc[2] = rh[2];
-    // ONE almanac wave (the sixteen-wave column shapes): distinct-segment units pay here too - Earth -> EMB sits on the chain of
-    // every body of an Earth-centred run and was evaluated once per BODY per stage (five Chebyshev evaluations for Sun + Moon where
-    // four segments are distinct).  The wave evaluates every distinct segment once, the readers sum the chains (ed_body(): the same
-    // additions in the same order, bit-identical).
-    int chain_evals = 0;
-    for (int sl = 0; sl < dc.n_slots; ++sl) chain_evals += dc.slot[sl].n_chain;
-    if (segment_units_fit(dc) && distinct_segments(dc) < chain_evals) {
-        dc.seg_mode = 1;
-        dc.n_useg = distinct_segments(dc, dc.useg_seg);
-        dc.ed_seg_base = (dc.has_grav || dc.has_drag || dc.has_tides) ? 9 : 0;
-        for (int sl = 0; sl < dc.n_slots; ++sl)
-            for (int k = 0; k < dc.slot[sl].n_chain; ++k)
-                for (int u = 0; u < dc.n_useg; ++u)
-                    if (dc.useg_seg[u] == dc.slot[sl].seg[k]) dc.slot[sl].useg[k] = u;
-        dc.role_mask[1] = DEV_ROLE_DCM | ((1 << dc.n_useg) - 1);
-    }
-}
-
-// The balanced helper dealing (build_schedule): the speed of a helper column wave on a SIMD that hosts three of them (beside the
-// producer / the answering wave), and what the start of one more column on a helper wave is charged, in rows.
-static constexpr double kCoopFastWeight = 4.0 / 3.0;
-static constexpr double kCoopStartRows = 4.0;
-
-static void build_schedule(nyx_hip_ctx *ctx, int n_waves, bool quad = false) {
-    DevCfg &dc = ctx->host_cfg;
-    ctx->rs_dirty = true;  // (the run streams follow the schedules: rebuilt before the next launch that streams the table)
-    const int nc = dc.n_cols;
-    for (int k = 0; k < DEV_N_SCHED; ++k)
-        for (int w = 0; w < DEV_MAX_WAVES; ++w) dc.sched[k].n_ranges[w] = 0;
-    dc.n_waves = n_waves;
-    if (dc.has_grav2)  // the second field: every column, for whichever wave walks it (the perturbation wave with the point-mass share)
-        for (int w = 0; w < DEV_MAX_WAVES; ++w) {
-            dc.sched[DEV_SCHED_SECOND].n_ranges[w] = 1;
-            dc.sched[DEV_SCHED_SECOND].range_c0[w][0] = 1;
-            dc.sched[DEV_SCHED_SECOND].range_cnt[w][0] = dc.n_cols2;
-        }
-    dc.merge_roles = (ctx->tune.merge_roles && n_waves >= 8) ? 1 : 0;
-    // pipelined stage loop: sixteen-wave workgroups (the column waves go from one stage's harmonics into the next's), and - plain
-    // kernel - any workgroup of dynamics without a gravity field that has the integrator in a wave of its own: the perturbation
-    // waves need the POSITION of the next stage only, which the integrator publishes inside the window, so its phases A and C run
-    // beside the almanac / perturbation duties instead of in front of them
-    const bool stm_cfg = (dc.flags & NYX_HIP_FLAG_STM) != 0;
-    // (not with a non-central gravity field: its inputs need the body's position of the stage, which the almanac waves write late in the window)
-    dc.pipe = (!dc.merge_roles && ctx->tune.pipelined != 0 && !(dc.has_grav && dc.g_slot >= 0) &&
-               ((n_waves == DEV_MAX_WAVES && dc.has_grav) || (!dc.has_grav && !stm_cfg && n_waves >= 2 && n_waves <= 8))) ? 1 : 0;
-    // (a workgroup of more than eight waves WITHOUT a gravity field exists only when the caller forces it - nyx_hip_ctx_set_column_waves -
-    //  and runs the plain loop: the pipelined integrator of the sixteen-wave kernels is compiled for the gravity-field shape, INTEG_OOL)
-    // roles of this workgroup shape and their serial duties (merged roles when there are fewer than three waves)
-    double hc[DEV_MAX_WAVES] = {0};
-    assign_roles(ctx, n_waves, want_fanout(ctx, quad), hc);
-    // speculative stage 0 (role_loop): the pipelined plain kernel with ONE almanac wave and an even stage count (the last window
-    // then leaves the buffers of stage parity 0 free for the epoch data of t + h)
-    // (with a gravity field: one almanac wave; without: any fan-out, almanac and perturbation duties in waves of their own)
-    dc.spec = (dc.pipe && !(dc.flags & NYX_HIP_FLAG_STM) && dc.stages % 2 == 0 &&
-               (dc.has_grav ? dc.n_alm == 1 : (n_waves >= 3 && dc.role_kind[1] != DEV_ROLE_ALMANAC_PERT && (dc.n_slots > 0 || dc.has_drag || dc.has_tides))) &&
-               !dc.has_grav2 &&  // (the second field's wave reads the attempt's epoch at stage 0: it would have to wait for step control)
-               ctx->tune.chained_attempts != 0) ? 1 : 0;
-    dc.ed_reuse = (dc.spec || dc.seg_mode) ? 0 : ctx->ed_reuse_fit;  // (chained attempts need no copy of the stage-0 epoch data: a rejected lane keeps its k_0)
-    if (!dc.has_grav || nc == 0) return;
-    // with enough column workers the integrator keeps its window free: its serial phases A / C gate every other wave
-    // (pipelined loop: the integrator wave walks NO columns at all - role_loop skips its walk -, whatever duties the caller states:
-    //  round 5 found tuning.role_duties handing it 57 rows that nobody then evaluated)
-    if (n_waves >= 8 && (dc.pipe || !any_nonzero(ctx->tune.role_duties, 3))) hc[0] = 1e9;
-    std::vector<int> all;
-    for (int c = 1; c <= nc; ++c) all.push_back(c);
-    (void)fill_schedule(ctx, dc.sched[DEV_SCHED_SOLO], n_waves, all, hc, true);
-    // Cooperative mode (16-wave workgroups only).  The helper takes the LONGEST columns, at most one per column wave: its job
-    // time is then one long column (~18 batches), which is within 17 % of the ideal x * terms / 16 for x <= 0.35, and the
-    // owner keeps the many short columns that let it balance its fifteen waves.  (Interleaving the two sets column by
-    // column was measured 10-25 % slower: the helper's waves then hold a long AND a short column each.)
-    if (n_waves == DEV_MAX_WAVES && nc >= 8 && ctx->coop_fan) {
-        // FAN-OUT mode (launch(): the idle CUs outnumber the owners at least two to one - a shard of an ensemble, a small Monte Carlo).
-        // Every owner has K = coop_parts dedicated helper workgroups (propagate_kernel.hip, helper_body under NYX_COOP_FAN); the owner's
-        // period is then bounded by its integrator's chain, not by column work, so the helpers take everything but the shortest columns:
-        // the K * cpp longest, dealt round-robin over the parts (every part a mix of long and short: equal jobs), one column per wave,
-        // the waves of a part taken round-robin over the SIMDs (eight columns = two waves per SIMD, which finish in ~10 k cycles where
-        // four per SIMD need ~17 k).  The owner keeps at least two columns (its PRIMARY schedule must not be empty).
-        const int K = std::min(std::max(ctx->coop_parts, 2), DEV_FAN_MAX);
-        const int col_waves = DEV_MAX_WAVES - 2;
-        int cpp = std::min(col_waves, (nc - 2 + K - 1) / K);
-        if (ctx->tune.coop_max_columns > 0) cpp = std::max(1, std::min(cpp, (int)ctx->tune.coop_max_columns / K));
-        const int n_help = std::min(nc - 2, K * cpp);
-        std::vector<int> own;
-        for (int c = n_help + 1; c <= nc; ++c) own.push_back(c);
-        for (int k = 0; k < n_help; ++k) {
-            const int part = k % K, pos = k / K;       // (ascending column number = descending length)
-            const int w = 1 + pos;                      // waves 1 .. 14 sit on SIMDs 1 2 3 0 1 2 3 0 ...: any prefix is balanced
-            DevSched &hs = dc.sched[DEV_SCHED_FAN0 + part];
-            const int r = hs.n_ranges[w]++;
-            hs.range_c0[w][r] = 1 + k; hs.range_cnt[w][r] = 1;
-        }
-        if (n_help > 0 && !own.empty() && fill_schedule(ctx, dc.sched[DEV_SCHED_PRIMARY], n_waves, own, hc, false)) {
-            dc.coop_ok = 1;
-        } else {
-            dc.coop_ok = 0;
-            for (int k = 0; k < DEV_N_SCHED; ++k)
-                if (k == DEV_SCHED_PRIMARY || k >= DEV_SCHED_FAN0)
-                    for (int w = 0; w < DEV_MAX_WAVES; ++w) dc.sched[k].n_ranges[w] = 0;
-        }
-    } else
-    if (n_waves == DEV_MAX_WAVES && nc >= 8) {
-        double terms = 0.0, given = 0.0;
-        for (int c = 1; c <= nc; ++c) terms += ctx->col_len[c];
-        std::vector<int> own, help;
-        const int col_waves = DEV_MAX_WAVES - 2;  // a helper's wave 0 claims jobs, its last wave answers
-        // One column per helper wave is the rule for short evaluation periods (70x70: a second column makes the job longer than the
-        // owner can wait, 302 ms against 182 ms).  A large field turns that around: at 150x150 the owner's period is 140 k cycles,
-        // a job of one 150-row column 34 k + the hand-off, and fourteen columns are 18 % of the terms where the helpers could take
-        // half - so when the one-column rule leaves the helpers below HALF of their share, their waves take up to
-        // DEV_MAX_RANGES columns each (config 5: 12.05 s with 14 columns, 11.36 s with 21, 10.31 s with 28).
-        int max_cols = col_waves;
-        const int parts_cfg = ctx->coop_parts == 2 ? 2 : 1;
-        double share = dc.coop_frac;
-        {
-            double first = 0.0;
-            for (int c = 1; c <= std::min(nc, col_waves); ++c) first += ctx->col_len[c];
-            if (first < 0.5 * dc.coop_frac * terms) {
-                max_cols = DEV_MAX_RANGES * col_waves;
-                share = 0.92 * dc.coop_frac;  // (several columns per wave: a job is longer for the same share; 35 / 38 / 42 columns at 150x150: 9.24 / 9.04 / 9.72 s)
-            }
-        }
-        if (parts_cfg == 2 && max_cols > col_waves) max_cols = 2 * DEV_MAX_RANGES * col_waves;  // (each part has its own DEV_MAX_RANGES per wave)
-        if (ctx->tune.coop_max_columns > 0) max_cols = std::min(parts_cfg * DEV_MAX_RANGES * col_waves, (int)ctx->tune.coop_max_columns);
-        // Balanced dealing (round 5; one-part hand-off of a field whose helper jobs hold ONE long column per wave, i.e. 70x70):
-        // the column waves of a helper are not alike - the two SIMDs that host the producer and the answering wave run three of them,
-        // the other two four - and with the streamed table a helper is bound by its SIMDs' issue, so a wave of a three-wave SIMD walks
-        // 4/3 the rows of the others in the same time.  The longest columns still go one per wave; when the share asks for more than
-        // those, the FAST waves get a second, medium column each out of one contiguous block of the table (the owners keep contiguous
-        // runs on either side), chosen so that every SIMD of the helper finishes together.
-        const bool balanced = parts_cfg == 1 && max_cols == col_waves && nc > 3 * col_waves;
-        std::vector<int> topup;
-        if (balanced) {
-            double first = 0.0;
-            for (int c = 1; c <= col_waves; ++c) first += ctx->col_len[c];
-            const double extra = share * terms - first;
-            const int n_fast = 6;
-            const double per = extra / n_fast - kCoopStartRows;  // rows of the second column of a fast wave
-            if (per >= 6.0) {
-                // columns of `per` rows: col_len[c] = deg + 2 - c
-                int c_mid = dc.deg + 2 - (int)(per + 0.5);
-                int c_lo = c_mid - n_fast / 2, c_hi = c_lo + n_fast - 1;
-                if (c_lo <= col_waves) { c_lo = col_waves + 1; c_hi = c_lo + n_fast - 1; }
-                if (c_hi > nc - 2) { c_hi = nc - 2; c_lo = c_hi - n_fast + 1; }
-                if (c_lo > col_waves)
-                    for (int c = c_lo; c <= c_hi; ++c) topup.push_back(c);
-            }
-        }
-        int n_long = 0;  // columns taken from the head of the table (the longest)
-        for (int c = 1; c <= nc; ++c) {
-            const bool is_top = std::find(topup.begin(), topup.end(), c) != topup.end();
-            // (with a second column on the fast waves the long block is the full first round: one column per wave)
-            const bool long_ok = n_long < max_cols && c < nc - 1 && (!topup.empty() || given + 0.5 * ctx->col_len[c] <= share * terms) && (topup.empty() || c <= col_waves);
-            if (is_top || long_ok) {
-                help.push_back(c);
-                given += ctx->col_len[c];
-                if (!is_top) ++n_long;
-            } else {
-                own.push_back(c);
-            }
-        }
-        // helper: one column per wave, longest first; the two SIMDs that also host the producer and the answering wave have
-        // three column waves (4 8 12 / 3 7 11) and take the six longest, the other two SIMDs four each
-        static const int wave_order[DEV_MAX_WAVES - 2] = {4, 3, 8, 7, 12, 11, 1, 2, 5, 6, 9, 10, 13, 14};
-        // Two-part hand-off (ctx->coop_parts == 2, chosen by launch() when the idle CUs outnumber the owners and the helpers' jobs hold
-        // several columns per wave): the helpers' columns are dealt alternately into two sub-jobs that two DIFFERENT helper workgroups
-        // claim - half the job per helper, so the turnaround the owner waits for halves and twice the helpers find work.
-        const int parts = ctx->coop_parts == 2 ? 2 : 1;
-        for (int part = 0; part < 2; ++part) {
-            DevSched &hs = dc.sched[part ? DEV_SCHED_HELPER2 : DEV_SCHED_HELPER];
-            for (int w = 0; w < DEV_MAX_WAVES; ++w) hs.n_ranges[w] = 0;
-            if (part >= parts) continue;
-            std::vector<int> mine;
-            for (size_t k = 0; k < help.size(); ++k) if ((int)(k % (size_t)parts) == part) mine.push_back(help[k]);
-            if (balanced) {
-                // longest column first onto the wave that would finish it soonest: load / speed, speed = kCoopFastWeight on the SIMDs with
-                // three column waves (waves 4 8 12 beside the producer, 3 7 11 beside the answering wave)
-                double load[DEV_MAX_WAVES] = {0.0};
-                for (int c : mine) {  // (ascending column number = descending length)
-                    int best = -1;
-                    double best_t = 1e300;
-                    for (int q = 0; q < col_waves; ++q) {
-                        const int w = wave_order[q];
-                        if (hs.n_ranges[w] >= DEV_MAX_RANGES) continue;
-                        const double speed = (w % 4 == 0 || w % 4 == 3) ? kCoopFastWeight : 1.0;
-                        const double t = (load[w] + ctx->col_len[c] + (hs.n_ranges[w] > 0 ? kCoopStartRows : 0.0)) / speed;
-                        if (t < best_t - 1e-9) { best_t = t; best = w; }
-                    }
-                    if (best < 0) break;
-                    load[best] += ctx->col_len[c] + (hs.n_ranges[best] > 0 ? kCoopStartRows : 0.0);
-                    const int r = hs.n_ranges[best]++;
-                    hs.range_c0[best][r] = c; hs.range_cnt[best][r] = 1;
-                }
-                continue;
-            }
-            for (size_t k = 0; k < mine.size(); ++k) {
-                // further rounds are dealt in alternating directions: every wave's set has about the same length
-                const int round = (int)k / col_waves, pos = (int)k % col_waves;
-                const int w = (round & 1) ? wave_order[col_waves - 1 - pos] : wave_order[pos];
-                const int r = hs.n_ranges[w]++;
-                hs.range_c0[w][r] = mine[k]; hs.range_cnt[w][r] = 1;
-            }
-        }
-        if (!help.empty() && !own.empty() && fill_schedule(ctx, dc.sched[DEV_SCHED_PRIMARY], n_waves, own, hc, false)) {
-            dc.coop_ok = 1;
-        } else {
-            dc.coop_ok = 0;
-            for (int w = 0; w < DEV_MAX_WAVES; ++w) dc.sched[DEV_SCHED_PRIMARY].n_ranges[w] = dc.sched[DEV_SCHED_HELPER].n_ranges[w] = dc.sched[DEV_SCHED_HELPER2].n_ranges[w] = 0;
-        }
-    } else {
-        dc.coop_ok = 0;
-    }
-}
-
-// STM layout by ensemble size.  The quad layout spends 4 lanes per trajectory (1.6x the f64 issue slots of the D3 layout
-// per trajectory) to get 4x the workgroups and 4x the waves per workgroup: it wins while the D3 layout would leave most of
-// the chip without a workgroup, i.e. up to ~2 quad workgroups per CU.
-static bool pick_quad(const nyx_hip_ctx *ctx, int64_t n) {
-    if (!(ctx->host_cfg.flags & NYX_HIP_FLAG_STM)) return false;
-    if (ctx->host_cfg.flags & NYX_HIP_FLAG_STM_TEXTBOOK) return false;  // (the variational equations are integrated by the 64-lane layout: one trajectory's k-buffer column per lane)
-    if (ctx->forced_quad >= 0) return ctx->forced_quad != 0;
-    if (ctx->tune.stm_quad >= 0) return ctx->tune.stm_quad != 0;
-    // deterministic: the layout fixes the column split, hence the bits - it must not follow the batch size (a shard is a smaller batch)
-    if (ctx->tune.deterministic) return true;
-    const int64_t cus = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    return (n + 15) / 16 <= 2 * cus;
-}
-
-static int pick_waves(const nyx_hip_ctx *ctx, int64_t n) {
-    const bool stm = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
-    if (stm && pick_quad(ctx, n)) {  // quad layout: 128 VGPRs per wave like the plain kernel
-        if (ctx->forced_waves > 0) return std::min(ctx->forced_waves, DEV_MAX_WAVES);
-        if (!ctx->host_cfg.has_grav) return want_fanout(ctx, true) ? (fanout_role_waves(ctx) > 4 ? 8 : std::max(3, fanout_role_waves(ctx))) : 3;
-        return ctx->host_cfg.deg < 8 ? 8 : 16;
-    }
-    if (stm) {  // dual-number variant: 256 VGPRs per wave, at most DEV_MAX_WAVES_STM waves
-        if (ctx->forced_waves > 0) return std::min(ctx->forced_waves, DEV_MAX_WAVES_STM);
-        return ctx->host_cfg.has_grav ? DEV_MAX_WAVES_STM : 3;
-    }
-    if (ctx->forced_waves > 0) return std::min(ctx->forced_waves, DEV_MAX_WAVES);
-    // no harmonics: integrator + almanac + perturbation waves form a 3-stage pipeline
-    if (!ctx->host_cfg.has_grav) {
-        if (!(ctx->host_cfg.n_slots > 0 || ctx->host_cfg.has_drag || ctx->host_cfg.has_tides)) return 1;
-        return want_fanout(ctx, false) ? (fanout_role_waves(ctx) > 4 ? 8 : std::max(3, fanout_role_waves(ctx))) : 3;  // (8: two role waves per SIMD can be placed)
-    }
-    // Sixteen waves whatever the ensemble size: a workgroup's LDS (~150 KB) gives it a CU to itself, so the column split is what puts
-    // four waves on every SIMD.  (Rounds 1-3 went down to eight and four waves for >= 32 705 / >= 131 009 trajectories, sized when a
-    // workgroup was small enough to share a CU; measured in round 4 on configs[1]'s force model, 1 h: 32 768 trajectories 104.2 ms
-    // with eight waves against 69.1 with sixteen, 131 072: 521 (four) / 410 (eight) / 277 ms (sixteen) - 0.44 / 0.56 / 0.83 of the
-    // FP64 peak.)  The shape therefore depends on the configuration alone, which is also what tuning.deterministic promises.
-    (void)n;
-    const int deg = ctx->host_cfg.deg;
-    int want = 16;
-    if (deg < 8) want = std::min(want, 4);
-    else if (deg < 24) want = std::min(want, 8);
-    return want;
+// What the launch planner (launch_plan.h) reads of a context.
+static PlanInputs plan_inputs(const nyx_hip_ctx *ctx) {
+    return PlanInputs{ctx->tune, ctx->col_len, ctx->role_handicap, ctx->terms2, ctx->ed_reuse_fit, ctx->n_cu, ctx->forced_waves, ctx->forced_quad, ctx->weights};
 }
 
 extern "C" int32_t nyx_hip_ctx_set_column_waves(nyx_hip_ctx *ctx, int32_t waves) {
@@ -1273,9 +648,6 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
     nyx_hip_ctx *ctx = new nyx_hip_ctx();
     ctx->device = device;
     ctx->tune = tune;
-    ctx->block_schedule = (ctx->tune.debug_flags & 0x8000) == 0;  // (0x8000: the two-ended column fill of rounds 1-3 everywhere)
-    ctx->block_force = (ctx->tune.debug_flags & 0x10000) != 0;    // (0x10000: contiguous runs whatever the feed - the A/B partner of the streamed walk)
-    ctx->fit_partition = (ctx->tune.debug_flags & 0x2000000) == 0;  // (0x2000000: the linear partition of round 4 for the cooperative 70x70 shape too, fill_schedule)
     DevCfg &dc = ctx->host_cfg;
     std::memset(&dc, 0, sizeof dc);
     const NyxTableau &tb = NYX_TABLEAUX[o.method];
@@ -1517,7 +889,7 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
         hipDeviceProp_t prop;
         ctx->n_cu = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
     }
-    build_schedule(ctx, 1);
+    build_schedule(plan_inputs(ctx), dc, ctx->shape, 1);
 
     // ---- upload
     dc.hyb = 0;
@@ -1612,7 +984,7 @@ static int calibrate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, hipStream_t s
     std::vector<int32_t> cal_status((size_t)n);
     std::array<double, 2 * DEV_MAX_WAVES> w;
     bool have = false;
-    nyx_hip_ctx::WKey key(0, 0, 0, 0);
+    WKey key(0, 0, 0, 0);
     double spread = 0.0;
     std::vector<int64_t> prof(17 * 8);
     for (int it = 0; it < 4; ++it) {
@@ -1727,24 +1099,20 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
         return NYX_HIP_RC_OK;
     }
     if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // one launch of a context at a time on the device
-    const int nw = pick_waves(ctx, in->n);
+    // launch-shape dependent parts of the descriptor: waves per workgroup, column schedules and cooperative mode (launch_plan.h),
+    // and whether the ephemeris records fit in LDS next to this layout's buffers (the quad layout is smaller than the D3 one)
+    const LaunchPlan plan = plan_launch(plan_inputs(ctx), ctx->host_cfg, ctx->shape, in->n, ctx->sched_dirty);
+    const int nw = plan.n_waves;
+    const CoopPlan &cp = plan.coop;
+    ctx->sched_dirty = false;
     {
-        // launch-shape dependent parts of the descriptor: column schedule (waves per workgroup) and whether the ephemeris
-        // records fit in LDS next to this layout's buffers (the quad layout is smaller than the D3 one)
-        const bool stm_l = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
-        const int kind = stm_l ? (pick_quad(ctx, in->n) ? 2 : 1) : 0;
-        bool dirty = false;
-        if (nw != ctx->host_cfg.n_waves || (kind == 2) != ctx->sched_quad || ctx->sched_dirty) {
-            ctx->sched_quad = kind == 2;
-            build_schedule(ctx, nw, kind == 2);
-            ctx->sched_dirty = false;
-            dirty = true;
-        }
+        const int kind = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) ? (plan.quad ? 2 : 1) : 0;
         const int rd = ctx->host_cfg.rec_doubles;  // (after the schedule: chained attempts give the carried epoch data's LDS back)
         const int want_rec = ((size_t)rd * sizeof(double) <= 24 * 1024 &&
                               nyx_kernel_lds_bytes(DEV_MAX_WAVES, rd, kind, kind == 0 ? ctx->host_cfg.ed_reuse : 0) <= 160 * 1024) ? 1 : 0;
-        dirty = dirty || want_rec != ctx->host_cfg.rec_in_lds;
+        const bool dirty = plan.rebuilt || want_rec != ctx->host_cfg.rec_in_lds;
         ctx->host_cfg.rec_in_lds = want_rec;
+        if (plan.rebuilt) ctx->rs_dirty = true;  // (the run streams follow the schedules)
         if (dirty) HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
     }
     DevBatch bt;
@@ -1794,98 +1162,40 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
         bt.status = st->status; bt.last_step_ns = st->last_step_ns; bt.last_error = st->last_error;
         bt.last_attempts = st->last_attempts; bt.n_acc = st->n_accepted; bt.n_rej = st->n_rejected; bt.n_evals = st->n_evals;
     }
-    // Cooperative mode: when the trajectory-owning workgroups leave CUs idle, helper workgroups take over a share of
-    // the harmonics columns (propagate_kernel.hip).  Owners and helpers that talk to each other get block indices that
-    // agree modulo 8 (round-robin XCD dispatch: same L2); every owner needs a helper for the split to pay off.
+    // Cooperative mode (plan.coop): helper workgroups on the idle CUs take over a share of the harmonics columns
+    // (propagate_kernel.hip).  Owners and helpers that talk to each other get block indices that agree modulo 8 (round-robin XCD
+    // dispatch: same L2).
     ctx->last_coop_helpers = 0;
-    {
-        // on by default; tuning.cooperative = 0 (or .deterministic: the split follows the batch size) makes every workgroup work alone
-        const bool want = ctx->tune.cooperative != 0 && !ctx->tune.deterministic;
-        const int64_t n_own = (in->n + DEV_LANES - 1) / DEV_LANES;
-        // Helpers start right behind the owners and fill every CU that is left (round 4: 99 helpers instead of 96 for 157 owners is
-        // 3.9 % of the north-star run - the helpers' queues are what the owners wait in; rounds 1-3 rounded both to multiples of
-        // eight for XCD affinity, which buys nothing measurable).
-        const int64_t base = n_own;
-        const bool stm_ctx = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
-        if (want && !stm_ctx && ctx->host_cfg.has_grav && ctx->host_cfg.g_slot < 0 && nw == DEV_MAX_WAVES && ctx->host_cfg.coop_ok &&
-            base + 8 <= ctx->n_cu) {
-            // (more helpers than owners: the jobs are claimed, not assigned, so extra helpers shorten the queue of a set)
-            // Two-part hand-off: when the idle CUs outnumber the owners by a quarter and a helper job holds several columns per wave
-            // (large fields), every evaluation's hand-off is split in two sub-jobs for two helper workgroups (see build_schedule); the
-            // helper count then goes up to two per owner.  (debug_flags 0x80000 forces one part.)
-            const int64_t free_cus = ctx->n_cu - base;
-            int parts = (ctx->host_cfg.n_cols > 96 && 4 * free_cus >= 5 * n_own) ? 2 : 1;
-            if (ctx->tune.debug_flags & 0x80000) parts = 1;
-            // Fan-out mode (round 6): when the idle CUs outnumber the owners at least two to one - what a rank runs when ONE ensemble is
-            // cut over the GPUs of a node (configs[1] over 2 / 4 / 8 ranks: 79 / 40 / 20 owners), or a small Monte Carlo - every owner gets
-            // K = idle CUs / owners (<= DEV_FAN_MAX) DEDICATED helper workgroups and hands them all but its shortest columns.  Measured
-            // before it existed (round 6, profiles/round06_shard_sizes_before.log): 5 000 / 2 500 / 1 250 trajectories x 24 h ran
-            // 648 / 642 / 639 ms against 615 for 10 000 - a rank of 8 was no faster than one GPU alone.  Fields up to degree 95 (larger
-            // ones keep the two-part claim mode, whose jobs hold several columns per wave).  debug_flags 0x8000000 switches it off.
-            bool fan = ctx->host_cfg.n_cols <= 96 && free_cus >= 2 * n_own && n_own >= 1 && !(ctx->tune.debug_flags & 0x8000000) &&
-                       !(ctx->tune.debug_flags & 0x80000) && !(ctx->tune.coop_helper_ratio > 0.0);
-            if (fan) parts = (int)std::min<int64_t>(DEV_FAN_MAX, free_cus / n_own);
-            double h_ratio = parts == 2 ? 2.0 : 1.0;
-            if (ctx->tune.coop_helper_ratio > 0.0) h_ratio = std::min(3.0, std::max(0.25, ctx->tune.coop_helper_ratio));
-            const int64_t helpers = fan ? n_own * parts : std::min<int64_t>((int64_t)((double)n_own * h_ratio), free_cus);
-            if (parts != ctx->coop_parts || fan != ctx->coop_fan) {
-                ctx->coop_parts = parts;
-                ctx->coop_fan = fan;
-                build_schedule(ctx, nw, false);
-                HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
-            }
-            if (fan ? (ctx->host_cfg.coop_ok != 0) : (helpers >= 8 && 4 * helpers >= n_own)) {
-                // share of the terms the helpers take: owners keep (1 - x), each helper does x * owners / helpers jobs' worth
-                // per evaluation period, plus its hand-off overhead: x ~ 0.95 r / (1 + r) with r = helpers / owners
-                if (!fan && !(ctx->tune.coop_fraction > 0.0)) {
-                    const double r = (double)helpers / (double)n_own;
-                    // (two parts, measured on configs[4] with 158 helpers for 98 owners: 0.55 / 0.60 / 0.65 / 0.70 / 0.75 of the terms ->
-                    //  98.1 / 97.9 / 93.4 / 92.9 / 102.6 ms per hour of the ensemble - half a job per helper takes the knee further out)
-                    const double x = ctx->coop_parts == 2 ? std::min(0.68, std::max(0.10, 1.10 * r / (1.0 + r)))
-                                                          : std::min(0.55, std::max(0.10, 0.95 * r / (1.0 + r)));
-                    if (std::fabs(x - ctx->host_cfg.coop_frac) > 0.01) {
-                        ctx->host_cfg.coop_frac = x;
-                        build_schedule(ctx, nw, false);
-                        HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
-                    }
-                }
-                bool have_boxes = ctx->coop_cap >= n_own;
-                if (!have_boxes) {
-                    // the block goes back to the process-wide pool, where another context (another host thread) may take and clear it
-                    // at once: not before every launch of THIS context that uses it has finished (the device entry points are asynchronous)
-                    if (ctx->d_coop && ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
-                    mailbox_release(ctx->device, ctx->d_coop, ctx->coop_cap, !(ctx->tune.debug_flags & 0x100000));
-                    ctx->d_coop = nullptr;
-                    ctx->coop_cap = 0;
-                    // uncached device memory: the mailboxes are coherent across the XCDs' L2s without any cache
-                    // write-back / invalidate in the kernel (those would also flush the harmonics table out of L2)
-                    int64_t got = 0;
-                    ctx->d_coop = (CoopBox *)mailbox_acquire(ctx->device, std::max<int64_t>(n_own, 256), &got, !(ctx->tune.debug_flags & 0x100000));
-                    if (ctx->d_coop) {
-                        ctx->coop_cap = got;
-                        have_boxes = true;
-                    }  // (else: no such memory here, every workgroup works alone)
-                }
-                if (have_boxes && ctx->host_cfg.coop_ok) {
-                    // (only what this launch touches: n_own mailboxes, the scan words, and the part-1 answers when there are two parts)
-                    HIP_TRY(hipMemsetAsync(ctx->d_coop, 0, (size_t)n_own * sizeof(CoopBox), stream));
-                    HIP_TRY(hipMemsetAsync(ctx->d_coop + ctx->coop_cap, 0, 3 * (size_t)(ctx->coop_cap + 64) * sizeof(uint32_t), stream));
-                    CoopOut *out2 = (CoopOut *)((char *)(ctx->d_coop + ctx->coop_cap) + 3 * (size_t)(ctx->coop_cap + 64) * sizeof(uint32_t));
-                    // (the array behind the scan words holds coop_cap >= 256 answer blocks: part-1 answers of the two-part claim mode, one per
-                    //  owner; in the fan-out mode the answers of every (owner, part), owners * parts <= idle CUs < 256)
-                    if (ctx->coop_fan) HIP_TRY(hipMemsetAsync(out2, 0, (size_t)std::min<int64_t>(n_own * ctx->coop_parts, ctx->coop_cap) * sizeof(CoopOut), stream));
-                    else if (ctx->coop_parts == 2) HIP_TRY(hipMemsetAsync(out2, 0, (size_t)n_own * sizeof(CoopOut), stream));
-                    bt.coop_out2 = (ctx->coop_parts == 2 || ctx->coop_fan) ? out2 : nullptr;
-                    bt.coop_fan = ctx->coop_fan ? 1 : 0;
-                    bt.coop_helpers = (int32_t)helpers; bt.coop_base = (int32_t)base; bt.coop_box = ctx->d_coop;
-                    uint32_t *words = (uint32_t *)(ctx->d_coop + ctx->coop_cap);
-                    bt.coop_posted = words; bt.coop_claimed = words + (ctx->coop_cap + 64); bt.coop_finished = words + 2 * (ctx->coop_cap + 64);
-                    bt.coop_sets = (int32_t)((n_own + 15) / 16);
-                    bt.coop_parts = ctx->coop_parts;
-                    bt.coop_mute = ctx->tune.coop_mute ? 1 : 0;  // (bit 1, the retired speculative fetch of helper_body, stays clear)
-                    ctx->last_coop_helpers = (int)helpers;
-                }
-            }
+    if (cp.run) {
+        const bool pooled = !(ctx->tune.debug_flags & 0x100000);
+        if (ctx->coop_cap < cp.boxes || ctx->coop_cap < cp.answers) {
+            // the block goes back to the process-wide pool, where another context (another host thread) may take and clear it
+            // at once: not before every launch of THIS context that uses it has finished (the device entry points are asynchronous)
+            if (ctx->d_coop && ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
+            mailbox_release(ctx->device, ctx->d_coop, ctx->coop_cap, pooled);
+            ctx->d_coop = nullptr;
+            ctx->coop_cap = 0;
+            // uncached device memory: the mailboxes are coherent across the XCDs' L2s without any cache
+            // write-back / invalidate in the kernel (those would also flush the harmonics table out of L2)
+            int64_t got = 0;
+            ctx->d_coop = (CoopBox *)mailbox_acquire(ctx->device, std::max<int64_t>({cp.boxes, cp.answers, 256}), &got, pooled);
+            if (ctx->d_coop) ctx->coop_cap = got;  // (else: no such memory here, every workgroup works alone)
+        }
+        if (ctx->d_coop) {
+            // (only what this launch touches: its mailboxes, the scan words, and its answer blocks - coop_cap of them behind the scan words)
+            HIP_TRY(hipMemsetAsync(ctx->d_coop, 0, (size_t)cp.boxes * sizeof(CoopBox), stream));
+            HIP_TRY(hipMemsetAsync(ctx->d_coop + ctx->coop_cap, 0, 3 * (size_t)(ctx->coop_cap + 64) * sizeof(uint32_t), stream));
+            uint32_t *words = (uint32_t *)(ctx->d_coop + ctx->coop_cap);
+            CoopOut *out2 = (CoopOut *)(words + 3 * (ctx->coop_cap + 64));
+            if (cp.answers) HIP_TRY(hipMemsetAsync(out2, 0, (size_t)cp.answers * sizeof(CoopOut), stream));
+            bt.coop_out2 = cp.answers ? out2 : nullptr;
+            bt.coop_fan = cp.fan ? 1 : 0;
+            bt.coop_helpers = (int32_t)cp.helpers; bt.coop_base = (int32_t)cp.base; bt.coop_box = ctx->d_coop;
+            bt.coop_posted = words; bt.coop_claimed = words + (ctx->coop_cap + 64); bt.coop_finished = words + 2 * (ctx->coop_cap + 64);
+            bt.coop_sets = (int32_t)((cp.n_own + 15) / 16);
+            bt.coop_parts = cp.parts;
+            bt.coop_mute = ctx->tune.coop_mute ? 1 : 0;  // (bit 1, the retired speculative fetch of helper_body, stays clear)
+            ctx->last_coop_helpers = (int)cp.helpers;
         }
     }
     if (!ctx->h_tab.empty() && ctx->host_cfg.harm_feed != 0 && !(ctx->host_cfg.flags & NYX_HIP_FLAG_STM)) {
@@ -1921,9 +1231,7 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
     }
     {
         // the column weights of this launch's workgroup shape: measured once per context (see calibrate())
-        const bool stm_k = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
-        const nyx_hip_ctx::WKey key(nw, (ctx->host_cfg.pipe && (!stm_k || ctx->sched_quad)) ? 1 : 0, ctx->sched_quad ? 1 : 0,
-                                    bt.coop_helpers > 0 ? (int)(ctx->host_cfg.coop_frac * 10.0 + 0.5) : -1);
+        const WKey key = weight_key(ctx->host_cfg, nw, plan.quad, bt.coop_helpers > 0);
         ctx->last_key = key;
         const int64_t span = use_end ? INT64_MAX : (duration_ns < 0 ? -duration_ns : duration_ns);
         if (!calibrating && calibration_on(ctx) && ctx->host_cfg.has_grav && nw >= 8 && in->n >= 64 && !traj && !dur_ns && !ev &&
@@ -1938,7 +1246,7 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
         bt.prof = ctx->d_prof;
     }
     if (time_it) HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    const bool quad = pick_quad(ctx, in->n);
+    const bool quad = plan.quad;
     // (the LDS staging of the ephemeris records was decided at ctx_create for the D3 layout; the quad layout is smaller)
     HIP_TRY(nyx_launch_propagate(bt, ctx->d_cfg, ctx->d_htab, ctx->d_cols, ctx->d_records, nw,
                                  ctx->host_cfg.rec_in_lds ? ctx->host_cfg.rec_doubles : 0, ctx->host_cfg.ed_reuse, stream, quad ? 1 : 0,
@@ -2572,10 +1880,11 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     {
         // the segment launches carry a per-trajectory duration array and are too short to calibrate on themselves: measure
         // the column weights of their workgroup shape once per context, on the staged states (identity STM set above)
-        const int nw_c = pick_waves(ctx, n);
-        const bool quad_c = pick_quad(ctx, n);
+        const PlanInputs pin = plan_inputs(ctx);
+        const int nw_c = pick_waves(pin, ctx->host_cfg, n);
+        const bool quad_c = pick_quad(pin, ctx->host_cfg, n);
         const bool pipe_c = quad_c && nw_c == DEV_MAX_WAVES && ctx->tune.pipelined != 0;
-        const nyx_hip_ctx::WKey key(nw_c, pipe_c ? 1 : 0, quad_c ? 1 : 0, -1);
+        const WKey key(nw_c, pipe_c ? 1 : 0, quad_c ? 1 : 0, -1);
         if (calibration_on(ctx) && ctx->host_cfg.has_grav && nw_c >= 8 && n >= 16 && !ctx->weights.count(key)) {
             if (int rc = calibrate(ctx, &sg.din, stream)) return rc;
             HIP_TRY(hipEventRecord(ctx->ev0, stream));  // (the timed region is the segment loop, not the one-off calibration)
@@ -2591,7 +1900,7 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     // (quad layout only: sixteen waves share sixteen trajectories' updates; the 64-lane layout - four waves, sixty-four trajectories per
     //  workgroup - is the large-ensemble shape, where the per-launch cost is a small share and sixteen serial updates per wave cost more:
     //  measured 26.2 ms fused against 24.3 ms per segment at n = 1 000)
-    const bool fused = ctx->swap_n_chain == 0 && !(ctx->tune.debug_flags & 0x20000000) && pick_quad(ctx, n);
+    const bool fused = ctx->swap_n_chain == 0 && !(ctx->tune.debug_flags & 0x20000000) && pick_quad(plan_inputs(ctx), ctx->host_cfg, n);
     if (fused) {
         if (int rc = pa_dev.alloc(sizeof(PredictArgs))) return rc;
         HIP_TRY(hipMemcpyAsync(pa_dev.p, &a, sizeof(PredictArgs), hipMemcpyHostToDevice, stream));
@@ -2635,19 +1944,19 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     return NYX_HIP_RC_OK;
 }
 
-// Introspection for tests / DESIGN.md: column schedule of the current context.
-extern "C" int32_t nyx_hip_debug_schedule(nyx_hip_ctx *ctx, int32_t n_waves, int32_t *loads /* [8] */) {
-    if (!ctx || n_waves < 1 || n_waves > DEV_MAX_WAVES) return NYX_HIP_RC_BAD_ARG;
+// Introspection for tests / DESIGN.md: rows per wave of the SOLO column schedule an n_waves workgroup of this context would walk.
+// loads[16].  Planned on a copy of the descriptor: the context keeps the schedules its last launch uploaded.
+extern "C" int32_t nyx_hip_debug_schedule(nyx_hip_ctx *ctx, int32_t n_waves, int32_t *loads /* [16] */) {
+    if (!ctx || !loads || n_waves < 1 || n_waves > DEV_MAX_WAVES) return NYX_HIP_RC_BAD_ARG;
     CTX_LOCK(ctx);
-    const int keep = ctx->host_cfg.n_waves;
-    build_schedule(ctx, n_waves);
+    const std::unique_ptr<DevCfg> dc(new DevCfg(ctx->host_cfg));
+    build_schedule(plan_inputs(ctx), *dc, ctx->shape, n_waves);
+    const DevSched &sd = dc->sched[DEV_SCHED_SOLO];
     for (int w = 0; w < DEV_MAX_WAVES; ++w) {
         int l = 0;
-        const DevSched &sd = ctx->host_cfg.sched[DEV_SCHED_SOLO];
         for (int q = 0; q < sd.n_ranges[w]; ++q)
             for (int c = sd.range_c0[w][q]; c < sd.range_c0[w][q] + sd.range_cnt[w][q]; ++c) l += ctx->col_len[c];
         loads[w] = l;
     }
-    build_schedule(ctx, keep);
     return NYX_HIP_RC_OK;
 }

@@ -1,4 +1,4 @@
-// col_partition.h - placement of contiguous column runs along a column list in a FREE wave order (host only; fill_schedule in abi.cpp,
+// col_partition.h - placement of contiguous column runs along a column list in a FREE wave order (host only; fill_schedule in launch_plan.h,
 // tests/cxx/col_partition_check.cpp).
 //
 // A wave of a sixteen-wave owner workgroup walks ONE contiguous run of the (length-sorted) column list.  Cutting the list at the

@@ -1,4 +1,4 @@
-"""CPU: the free-order placement of the owner's column runs (nyx_amd/csrc/col_partition.h, used by fill_schedule in abi.cpp) as a
+"""CPU: the free-order placement of the owner's column runs (nyx_amd/csrc/col_partition.h, used by fill_schedule in launch_plan.h) as a
 stand-alone C++ check - g++ only, no HIP, no GPU: every column dealt exactly once, contiguous runs in list order, every wave inside
 the tolerance the search reports, the 70x70 cooperative shape placed at a tolerance the linear partition of round 4 misses by more
 than 2x, random shapes, refused inputs."""

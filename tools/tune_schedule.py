@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fits the per-wave speed weights of the column schedule on the GPU box (what the frozen tables model_coop / model_solo / ... of
-fill_schedule() in nyx_amd/csrc/abi.cpp hold): runs one BASELINE configuration with explicit weights and the in-kernel cycle
+fill_schedule() in nyx_amd/csrc/launch_plan.h hold): runs one BASELINE configuration with explicit weights and the in-kernel cycle
 accounting, reads every wave's window (role duty + its columns) and the rows it walked, solves for the row counts that would make
 all windows equal, and feeds them back as weights (damped); the best kernel time wins.  One process, a few seconds.
 usage: tools/tune_schedule.py <config 2|4|5> <n or 0> <hours or 0> [iterations] ['{"tuning": fields}'] [w0,w1,...,w15]"""
