@@ -28,6 +28,14 @@ ensemble is fixed (--n), `value` = all ranks' trajectories / max-over-ranks time
 `--gpus N` always measures N ranks: under torchrun WORLD_SIZE must equal N, without it the script starts the ranks itself
 (one process per GPU, rendezvous on 127.0.0.1, RCCL) and rank 0 prints the one JSON line with `n_gpus`, `rccl_ranks`,
 `per_rank_kernel_ms` and `all_gather_ms`.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs`, the JSON line.  `--full`
+(one rank) adds the measurements beside it, each a run of its own after the timed steps: `host_call` (the host-buffer entry),
+`dense_output` (the launch with the trajectories recorded), `other_configs` and `strong_scaling_projection` (one pass each of
+configs 3, 4, 5, the full-chip launch and the shard sizes, with CPU baselines) and `cpu_baseline` (the oracle on the host
+threads, with a parity check on its sample); the `--no-*` options leave parts of it out.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import ctypes as C
@@ -613,11 +621,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; with N ranks DIR/rank<r>/)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dense-output", action="store_true", help="skip the extra launch with the trajectories recorded")
-    ap.add_argument("--no-host-call", action="store_true", help="skip the PCIe-inclusive host-buffer call")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need (one rank): host_call, dense_output, "
+                         "other_configs with strong_scaling_projection, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-dense-output", action="store_true", help="--full: skip the extra launch with the trajectories recorded")
+    ap.add_argument("--no-host-call", action="store_true", help="--full: skip the PCIe-inclusive host-buffer call")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the one-pass measurements of configs 3, 4, 5 and of the full-chip launch that the headline run carries in `other_configs`")
+                    help="--full: skip the one-pass measurements of configs 3, 4, 5 and of the full-chip launch carried in `other_configs`")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -872,7 +883,8 @@ def main():
             ex_tf = n_evals * w["exec_flop"] / (k_ms * 1e-3) / 1e12
             line["roofline"]["executed_harmonics_flop_per_eval"] = w["exec_flop"]
             line["roofline"]["executed_frac"] = ex_tf / FP64_VECTOR_PEAK_TFLOPS
-        if world == 1 and not args.no_host_call:
+        full = world == 1 and args.full   # the measurements beside the headline (--full): one rank only
+        if full and not args.no_host_call:
             # SURVEY 8d "report both": the same batch through the HOST-buffer entry (H2D of the states, kernel, D2H of the
             # results inside the call; ctx_create excluded), timed once with the wall clock
             if not w["stm"]:
@@ -886,7 +898,7 @@ def main():
                              "note": "nyx_hip_predict_until takes host buffers: the timed steps ARE PCIe-inclusive; kernel_ms = the "
                                      "device time of the loop (round 6: ONE launch of the quad STM kernel for all sixty time updates)"}
             line["host_call"] = host_call
-        if world == 1 and not args.no_dense_output and not w["stm"] and args.config == 2:
+        if full and not args.no_dense_output and not w["stm"] and args.config == 2:
             # The reference's Monte Carlo runs `until_epoch_with_traj` (mc/montecarlo.rs:236-239): the same launch with the
             # dense output on (every accepted state of every run appended in HBM), timed once, reported beside the headline.
             cap = int(tst["n_accepted"].max().item()) + 2
@@ -910,7 +922,7 @@ def main():
                                     "states_written": n_states, "bytes_written": n_states * 56,
                                     "note": "one launch of nyx_hip_propagate_batch_with_traj_device (until_epoch_with_traj of every run)"}
             del t_ep, t_st, t_len
-        if world == 1 and args.config == 2 and not args.no_other_configs and not args.n and not args.hours and args.degree is None:
+        if full and args.config == 2 and not args.no_other_configs and not args.n and not args.hours and args.degree is None:
             # the other GPU configurations and the full-chip launch under the SAME driver clock, one timed pass each
             others = {}
             for key, kw in (("config3", dict(cfg_id=3, cpu=True)), ("config4", dict(cfg_id=4, cpu=True)), ("config5", dict(cfg_id=5, cpu=True)),
@@ -941,7 +953,7 @@ def main():
                 "config3_cut_8_ways_ms": others["config3_shard_625"]["ms_per_step"],
                 "headline_value_at_n_gt_1": "weak scaling: every rank propagates its own 10 000-trajectory ensemble (the task's contract for a path that shards: per-GPU work fixed); "
                                             "--scaling strong cuts ONE ensemble N ways"}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline:
             if not w["stm"]:
                 cb, sample, ref, samp_h = cpu_baseline(shard, compiled, n, hours)
                 if samp_h == hours:

@@ -113,6 +113,19 @@ def test_single_process_mode_drives_the_sharded_entry():
 
 
 @pytest.mark.gpu
+def test_plain_run_leaves_the_side_measurements_to_full():
+    """A plain run is the headline alone; `--full` adds the measurements beside it (here the two device ones)."""
+    base = [a for a in SMALL if not a.startswith("--no-")]
+    p, line = _run(["--gpus", "1", *base])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"host_call", "dense_output", "other_configs", "strong_scaling_projection", "cpu_baseline"} & set(line)
+    p, line = _run(["--gpus", "1", *base, "--full", "--no-cpu-baseline"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert line["host_call"]["value"] > 0 and line["dense_output"]["states_written"] > 0 and "cpu_baseline" not in line
+
+
+@pytest.mark.gpu
 def test_rccl_refuses_shared_device_with_a_message():
     import torch
     if torch.cuda.device_count() > 1:

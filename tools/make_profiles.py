@@ -27,7 +27,7 @@ for item in items:
     line = json.loads(open(os.path.join(src, "bench.json")).read().strip().splitlines()[-1])
     bench_out = os.path.join(ROOT, "profiles", f"{tag}_{name}_bench.json")
     shutil.copy(os.path.join(src, "kernel_trace_stats.md"), os.path.join(ROOT, "profiles", f"{tag}_{name}_kernel_trace_stats.md"))
-    if name == "cfg2" and os.path.exists(os.path.join(src, "bench_with_others.json")):   # the default run, `other_configs` included
+    if name == "cfg2" and os.path.exists(os.path.join(src, "bench_with_others.json")):   # the --full run, `other_configs` included
         full = json.loads(open(os.path.join(src, "bench_with_others.json")).read().strip().splitlines()[-1])
         json.dump(full, open(os.path.join(ROOT, "profiles", f"{tag}_cfg2_bench_with_other_configs.json"), "w"), indent=1)
     per = collections.defaultdict(list)

@@ -11,7 +11,7 @@ TAG=${TAG:-cfg$CFG}
 EXTRA="${EXTRA:-} --no-other-configs"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-if [ -z "${SKIP_BENCH:-}" ]; then timeout 900 python bench.py --config $CFG --steps $STEPS --warmup 1 $EXTRA > $OUT/bench.json 2> $OUT/bench.err; fi
+if [ -z "${SKIP_BENCH:-}" ]; then timeout 900 python bench.py --config $CFG --steps $STEPS --warmup 1 --full $EXTRA > $OUT/bench.json 2> $OUT/bench.err; fi
 tail -c 300 $OUT/bench.json; echo
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt --output-format rocpd -- python bench.py --config $CFG --steps $STEPS --warmup 1 --no-cpu-baseline --no-dense-output --no-host-call $EXTRA > $OUT/kt.log 2>&1
 DB=$(find $OUT/kt -name "*.db" | head -1)
