@@ -1,5 +1,5 @@
-// abi.cpp — host side of the C-ABI (include/nyx_hip.h): context creation (table building,
-// column scheduling, upload), batch staging and kernel launch.  Compiled with hipcc.
+// abi.cpp — host side of the C-ABI (include/nyx_hip.h): context creation (what it builds: ctx_build.h; the launch policy:
+// launch_plan.h; here the device, the uploads), batch staging and kernel launch.  Compiled with hipcc.
 
 #include <hip/hip_runtime.h>
 
@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../../include/nyx_hip.h"
-#include "butcher.h"
+#include "ctx_build.h"
 #include "devcfg.h"
 #include "launch_plan.h"
 #include "predict_args.h"
@@ -243,34 +243,6 @@ extern "C" int64_t nyx_hip_abi_sizeof(int32_t which) {
     }
 }
 
-// nyx_hip_rotation_t -> DevRot (validated by check_rotation() first)
-static void copy_rotation(DevRot &d, const nyx_hip_rotation_t &r) {
-    std::memset(&d, 0, sizeof d);
-    for (int k = 0; k < 3; ++k) { d.ra[k] = r.ra_deg[k]; d.dec[k] = r.dec_deg[k]; d.w[k] = r.w_deg[k]; }
-    d.kind = r.kind; d.n_np = r.n_nut_prec;
-    for (int k = 0; k < r.n_nut_prec; ++k) {
-        d.np_ang[k][0] = r.nut_prec_angle_deg[k][0]; d.np_ang[k][1] = r.nut_prec_angle_deg[k][1];
-        d.np_ra[k] = r.nut_prec_ra[k]; d.np_dec[k] = r.nut_prec_dec[k]; d.np_w[k] = r.nut_prec_w[k];
-    }
-    d.euler_seg = r.euler_segment;
-    for (int k = 0; k < 9; ++k) d.base[k] = r.base_dcm[k];
-}
-static const char *check_rotation(const nyx_hip_rotation_t &r, int n_segments) {
-    if (r.kind != NYX_HIP_ROT_IAU && r.kind != NYX_HIP_ROT_EULER_CHEBY) return "unknown orientation kind";
-    if (r.n_nut_prec < 0 || r.n_nut_prec > NYX_HIP_MAX_NUT_PREC) return "n_nut_prec outside 0..NYX_HIP_MAX_NUT_PREC";
-    if (r.kind == NYX_HIP_ROT_EULER_CHEBY && (r.euler_segment < 0 || r.euler_segment >= n_segments)) return "euler_segment is not one of config.segments";
-    return nullptr;
-}
-
-static double ns_to_seconds_host(int64_t ns) {  // Duration::to_seconds for |ns| < 1 century, ns >= 0
-    int64_t q = ns / 1000000000LL, r = ns % 1000000000LL;
-    return (double)q + (double)r * 1e-9;
-}
-
-// tuning.debug_flags that still select something (nyx_hip.h); nyx_hip_ctx_create refuses every other bit
-static constexpr uint32_t kLiveDebugFlags = 0x100 | 0x200 | 0x400 | 0x800 | 0x4000 | 0x8000 | 0x10000 | 0x80000 | 0x100000 | 0x2000000 |
-                                            0x4000000 | 0x8000000 | 0x20000000;
-
 // config.tuning -> the context's copy.  The process environment is consulted ONLY when NYX_HIP_TUNING_ENV is set (the A/B
 // tools of this repository: tools/*.py, tools/*.sh): a library behind a C-ABI takes its switches through its config struct.
 static nyx_hip_tuning_t resolve_tuning(const nyx_hip_tuning_t *t) {
@@ -308,101 +280,6 @@ static nyx_hip_tuning_t resolve_tuning(const nyx_hip_tuning_t *t) {
         r.schedule = NYX_HIP_SCHED_EXPLICIT;
     }
     return r;
-}
-static bool any_nonzero(const double *v, int n) { for (int k = 0; k < n; ++k) if (v[k] != 0.0) return true; return false; }
-
-// GravityField::new (reference dynamics/gravity_field.rs:52-132) re-expressed as the per-column
-// entry table the kernel streams (see HarmEntry in devcfg.h).
-static void build_harmonics(const nyx_hip_gravity_field_t *g, std::vector<HarmEntry> &tab, std::vector<ColHdr> &cols,
-                            std::vector<int32_t> &col_len, int &n_cols) {
-    const int N = g->degree, M = std::min(g->order, g->degree);
-    auto C = [&](int n, int m) -> double { return (n < 0 || m < 0 || n > N || m > n || m > M) ? 0.0 : g->c_nm[(size_t)n * (n + 1) / 2 + m]; };
-    auto S = [&](int n, int m) -> double { return (n < 0 || m < 0 || n > N || m > n || m > M) ? 0.0 : g->s_nm[(size_t)n * (n + 1) / 2 + m]; };
-    auto vr01 = [&](int n, int m) -> double {
-        double nf = n, mf = m;
-        double v = std::sqrt((nf - mf) * (nf + mf + 1.0));
-        return m == 0 ? v / std::sqrt(2.0) : v;
-    };
-    auto vr11 = [&](int n, int m) -> double {
-        double nf = n, mf = m;
-        double v = std::sqrt(((2.0 * nf + 1.0) * (nf + mf + 2.0) * (nf + mf + 1.0)) / (2.0 * nf + 3.0));
-        return m == 0 ? v / std::sqrt(2.0) : v;
-    };
-    auto bnm = [&](int n, int m) -> double {
-        double nf = n, mf = m;
-        return std::sqrt(((2.0 * nf + 1.0) * (2.0 * nf - 1.0)) / ((nf + mf) * (nf - mf)));
-    };
-    auto cnm = [&](int n, int m) -> double {
-        double nf = n, mf = m;
-        return std::sqrt(((2.0 * nf + 1.0) * (nf + mf - 1.0) * (nf - mf - 1.0)) / ((nf - mf) * (nf + mf) * (2.0 * nf - 3.0)));
-    };
-    // diagonal A[n][n]
-    std::vector<double> diag(N + 3);
-    diag[0] = 1.0;
-    for (int n = 1; n <= N + 2; ++n) diag[n] = std::sqrt(1.0 + 1.0 / (2.0 * (double)n)) * diag[n - 1];
-    // column c carries x/y terms of order m = c (c <= M) and z/w terms of order m = c - 1 (c - 1 <= M)
-    n_cols = std::min(N + 1, M + 1);
-    const double SQ2 = std::sqrt(2.0);
-    ColHdr zero_hdr;
-    std::memset(&zero_hdr, 0, sizeof zero_hdr);
-    cols.assign(n_cols + 3, zero_hdr);  // spare tail entries: the kernel prefetches header c + 1
-    col_len.assign(n_cols + 2, 0);
-    tab.clear();
-    for (int c = 1; c <= n_cols; ++c) {
-        const int rows = N + 2 - c;
-        const int nb = rows / HARM_BATCH, rem = rows % HARM_BATCH;  // full batches, then `rem` rows one at a time
-        cols[c].start = (int32_t)tab.size();
-        cols[c].nb = nb | (rem << 16);
-        cols[c].rows = rows;
-        cols[c].scale = (double)c * SQ2;
-        cols[c].diag = diag[c];
-        col_len[c] = rows;
-        double B = 1.0;  // prod of b[k][c], k = c+1 .. n: the scale of the carried recursion variable (see HarmEntry)
-        for (int n = c; n <= N + 1; ++n) {
-            HarmEntry e;
-            if (n == c) {
-                e.g = -1.0;
-            } else if (n == c + 1) {
-                e.g = 0.0;
-                B *= bnm(n, c);
-            } else {
-                e.g = cnm(n, c) / (bnm(n, c) * bnm(n - 1, c));
-                B *= bnm(n, c);
-            }
-            e.t1 = B * C(n, c);
-            e.t2 = B * S(n, c);
-            // z: (n, m = c-1), n in 1..N
-            const bool zok = (n >= 1 && n <= N);
-            e.t3 = zok ? B * (SQ2 * vr01(n, c - 1) * C(n, c - 1)) : 0.0;
-            e.t4 = zok ? B * (SQ2 * vr01(n, c - 1) * S(n, c - 1)) : 0.0;
-            // w: (n-1, m = c-1), n-1 in 1..N
-            const bool wok = (n - 1 >= 1 && n - 1 <= N && n - 1 >= c - 1);
-            e.t5 = wok ? B * (SQ2 * vr11(n - 1, c - 1) * C(n - 1, c - 1)) : 0.0;
-            e.t6 = wok ? B * (SQ2 * vr11(n - 1, c - 1) * S(n - 1, c - 1)) : 0.0;
-            tab.push_back(e);
-        }
-    }
-}
-
-// The same table as ONE stream for the hybrid feed (devcfg.h, HYB_*): stream row r = entry r of `tab` (the columns' rows back to
-// back).  Scalar side: {g, t1, t2}, 24 bytes per row; vector side, behind it: groups of sixteen rows, [t3..t6][16].
-static void build_hybrid(const std::vector<HarmEntry> &tab, std::vector<double> &hyb, int64_t &vec_off) {
-    // whole groups, plus two more: the walk fetches one batch / one group past its last row
-    const size_t n = tab.size(), padded = (n + 15) / 16 * 16 + 2 * 16;
-    const HarmEntry z = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    hyb.clear();
-    for (size_t r = 0; r < padded; ++r) {
-        const HarmEntry &e = r < n ? tab[r] : z;
-        hyb.push_back(e.g); hyb.push_back(e.t1); hyb.push_back(e.t2);
-    }
-    vec_off = (int64_t)hyb.size();  // 3 * padded doubles = a multiple of 48: the vector side starts 128-byte aligned
-    for (size_t g = 0; g < padded / 16; ++g)
-        for (int j = 0; j < 4; ++j)
-            for (int l = 0; l < 16; ++l) {
-                const size_t r = g * 16 + l;
-                const HarmEntry &e = r < n ? tab[r] : z;
-                hyb.push_back(j == 0 ? e.t3 : j == 1 ? e.t4 : j == 2 ? e.t5 : e.t6);
-            }
 }
 
 // A run stream (DevCfg.rs_*): the rows of the schedules `ids`, every range of every wave laid out as one contiguous piece that
@@ -587,313 +464,35 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
     if (!cfg || !out) { nyx_set_error("null argument"); return NYX_HIP_RC_BAD_ARG; }
     *out = nullptr;
     if (cfg->abi_version != NYX_HIP_ABI_VERSION) { nyx_set_error("ABI version mismatch"); return NYX_HIP_RC_BAD_ARG; }
-    const nyx_hip_integ_opts_t &o = cfg->opts;
-    if (o.method < 0 || o.method > 5 || o.error_ctrl < 0 || o.error_ctrl > 6) { nyx_set_error("bad method / error_ctrl"); return NYX_HIP_RC_BAD_ARG; }
-    if ((cfg->flags & NYX_HIP_FLAG_STM) && o.error_ctrl != NYX_HIP_RSS_CARTESIAN_STEP && o.error_ctrl != NYX_HIP_RSS_CARTESIAN_STATE) {
-        nyx_set_error("STM propagation on the device supports the RSSCartesianStep / RSSCartesianState error controls only");
-        return NYX_HIP_RC_UNSUPPORTED;
-    }
-    if ((cfg->flags & NYX_HIP_FLAG_STM_TEXTBOOK) && !(cfg->flags & NYX_HIP_FLAG_STM)) { nyx_set_error("NYX_HIP_FLAG_STM_TEXTBOOK without NYX_HIP_FLAG_STM"); return NYX_HIP_RC_BAD_ARG; }
-    if (cfg->drag && (cfg->flags & NYX_HIP_FLAG_STM)) {  // PartialsUndefined in the reference too (drag.rs:286-294)
-        nyx_set_error("drag has no partials: STM propagation with drag is undefined");
-        return NYX_HIP_RC_UNSUPPORTED;
-    }
-    if (cfg->drag && cfg->gravity && std::memcmp(&cfg->drag->rotation, &cfg->gravity->rotation, sizeof(nyx_hip_rotation_t)) != 0) {
-        nyx_set_error("device path: the drag frame must be the gravity-field frame when both are present");
-        return NYX_HIP_RC_UNSUPPORTED;
-    }
-    if (cfg->tides) {
-        const nyx_hip_rotation_t *other = cfg->gravity ? &cfg->gravity->rotation : (cfg->drag ? &cfg->drag->rotation : nullptr);
-        if (other && std::memcmp(&cfg->tides->rotation, other, sizeof(nyx_hip_rotation_t)) != 0) {
-            nyx_set_error("device path: the tidal frame must be the gravity-field / drag frame when they are present");
-            return NYX_HIP_RC_UNSUPPORTED;
-        }
-        if (cfg->tides->n_perturbers < 0 || cfg->tides->n_perturbers > NYX_HIP_MAX_BODIES || !(cfg->tides->mu_km3_s2 > 0.0) ||
-            !(cfg->tides->eq_radius_km > 0.0)) {
-            nyx_set_error("bad solid-tides model");
-            return NYX_HIP_RC_BAD_ARG;
-        }
-    }
-    // ---- plain-data validation: nothing below may index past what the device code assumes
-    if (cfg->n_bodies < 0 || cfg->n_bodies > NYX_HIP_MAX_BODIES || (cfg->n_bodies > 0 && !cfg->bodies) || cfg->n_segments < 0 ||
-        (cfg->n_segments > 0 && !cfg->segments) || cfg->n_point_masses < 0 || cfg->n_point_masses > NYX_HIP_MAX_BODIES) {
-        nyx_set_error("bad body / segment / point-mass counts"); return NYX_HIP_RC_BAD_ARG;
-    }
-    for (int b = 0; b < cfg->n_bodies; ++b)
-        if (cfg->bodies[b].n_chain < 0 || cfg->bodies[b].n_chain > NYX_HIP_MAX_CHAIN) {
-            nyx_set_error("body %d: n_chain %d outside 0..%d", b, cfg->bodies[b].n_chain, NYX_HIP_MAX_CHAIN); return NYX_HIP_RC_BAD_ARG;
-        }
-    for (int i = 0; i < cfg->n_segments; ++i) {
-        const nyx_hip_cheby_segment_t &sg = cfg->segments[i];
-        if (sg.n_coeffs < 1 || sg.n_records < 1 || !(sg.interval_s > 0.0) || !sg.records) {
-            nyx_set_error("segment %d: n_coeffs >= 1, n_records >= 1, interval_s > 0 and records are required", i); return NYX_HIP_RC_BAD_ARG;
-        }
-        if (sg.n_coeffs > NYX_HIP_MAX_CHEBY_COEFFS) {  // (cheby_eval: a 16-wide register window, a rolled loop up to this limit)
-            nyx_set_error("segment %d: %d Chebyshev coefficients per component, the device path evaluates at most %d", i, sg.n_coeffs, NYX_HIP_MAX_CHEBY_COEFFS);
-            return NYX_HIP_RC_UNSUPPORTED;
-        }
-    }
-    for (const nyx_hip_rotation_t *r : {cfg->gravity ? &cfg->gravity->rotation : nullptr, cfg->drag ? &cfg->drag->rotation : nullptr,
-                                        cfg->tides ? &cfg->tides->rotation : nullptr, cfg->gravity2 ? &cfg->gravity2->rotation : nullptr})
-        if (r)
-            if (const char *why = check_rotation(*r, cfg->n_segments)) { nyx_set_error("body-fixed orientation: %s", why); return NYX_HIP_RC_BAD_ARG; }
     const nyx_hip_tuning_t tune = resolve_tuning(cfg->tuning);
-    if (const uint32_t retired = (uint32_t)tune.debug_flags & ~kLiveDebugFlags) {
-        nyx_set_error("tuning.debug_flags 0x%x: not a debug switch of this library (the A/B path it selected was retired)", retired & (0u - retired));
-        return NYX_HIP_RC_BAD_ARG;
-    }
+    CtxBuild b;  // validation, descriptor, records and tables (ctx_build.h): nothing touches a device before it has passed
+    if (build_context(*cfg, tune, nyx_kernel_lds_bytes, b) != NYX_HIP_RC_OK) { nyx_set_error("%s", b.error.c_str()); return b.rc; }
     if (nyx_hip_device_count() <= device || device < 0) { nyx_set_error("no HIP device %d", device); return NYX_HIP_RC_NO_DEVICE; }
     HIP_TRY(hipSetDevice(device));
 
-    nyx_hip_ctx *ctx = new nyx_hip_ctx();
+    // the owner of a context under construction: every failure below (HIP_TRY included) frees what was allocated so far
+    std::unique_ptr<nyx_hip_ctx, void (*)(nyx_hip_ctx *)> ctx(new nyx_hip_ctx(), nyx_hip_ctx_destroy);
     ctx->device = device;
     ctx->tune = tune;
     DevCfg &dc = ctx->host_cfg;
-    std::memset(&dc, 0, sizeof dc);
-    const NyxTableau &tb = NYX_TABLEAUX[o.method];
-    dc.stages = tb.stages; dc.order = tb.order;
-    dc.fixed_step = o.fixed_step; dc.error_ctrl = o.error_ctrl; dc.attempts = o.attempts; dc.flags = (int32_t)cfg->flags;
-    dc.flags |= ctx->tune.debug_flags & 0xff00;  // timing-only switches
-    dc.tol = o.tolerance;
-    dc.init_step_ns = o.init_step_ns; dc.min_step_ns = o.min_step_ns; dc.max_step_ns = o.max_step_ns;
-    dc.min_step_s = ns_to_seconds_host(o.min_step_ns);
-    dc.max_step_s = ns_to_seconds_host(o.max_step_ns);
-    dc.inv_order = 1.0 / (double)tb.order;
-    dc.inv_order_m1 = 1.0 / (double)(tb.order - 1);
-    {
-        int a_idx = 0;
-        dc.c[0] = 0.0;
-        for (int i = 0; i < tb.stages - 1; ++i) {  // c_i = running sum of row i (reference instance.rs:379-387)
-            double ci = 0.0;
-            for (int j = 0; j <= i; ++j) { dc.a[a_idx] = tb.a[a_idx]; ci += tb.a[a_idx]; ++a_idx; }
-            dc.c[i + 1] = ci;
-        }
-        for (int i = 0; i < tb.stages; ++i) { dc.b[i] = tb.b[i]; dc.bdiff[i] = tb.b[i] - tb.b[i + tb.stages]; }
-    }
-    dc.mu_central = cfg->central_mu_km3_s2;
-    dc.g_slot = -1;
-
-    // ---- bodies -> slots (every non-central body referenced by a model)
-    std::vector<int> slot_of(cfg->n_bodies, -1);
-    auto slot_for = [&](int b) -> int {
-        if (b < 0 || b >= cfg->n_bodies) return -2;
-        if (cfg->bodies[b].n_chain == 0) return -1;  // the integration centre
-        if (slot_of[b] >= 0) return slot_of[b];
-        if (dc.n_slots >= DEV_MAX_SLOTS) return -2;
-        const nyx_hip_body_t &bd = cfg->bodies[b];
-        DevSlot &s = dc.slot[dc.n_slots];
-        s.mu = bd.mu_km3_s2; s.radius = bd.mean_radius_km; s.n_chain = bd.n_chain;
-        for (int k = 0; k < bd.n_chain; ++k) { s.seg[k] = bd.chain_segment[k]; s.sign[k] = (double)bd.chain_sign[k]; }
-        slot_of[b] = dc.n_slots++;
-        return slot_of[b];
-    };
-    for (int b = 0; b < cfg->n_bodies; ++b)
-        if (cfg->bodies[b].n_chain == 0) dc.central_radius = cfg->bodies[b].mean_radius_km;
-    if (cfg->state_frame_body != 0) {  // opts.integration_frame: the body the states are centred on
-        const int b = cfg->state_frame_body;
-        if (b < 0 || b >= cfg->n_bodies || cfg->bodies[b].n_chain > 4) { delete ctx; nyx_set_error("state_frame_body: not a body of this configuration"); return NYX_HIP_RC_BAD_ARG; }
-        ctx->swap_n_chain = cfg->bodies[b].n_chain;
-        for (int k = 0; k < ctx->swap_n_chain; ++k) {
-            const int sgi = cfg->bodies[b].chain_segment[k];
-            if (sgi < 0 || sgi >= cfg->n_segments) { delete ctx; nyx_set_error("state_frame_body: bad chain segment index"); return NYX_HIP_RC_BAD_ARG; }
-            ctx->swap_seg[k] = sgi;
-            ctx->swap_sign[k] = (double)cfg->bodies[b].chain_sign[k];
-        }
-    }
-    for (int k = 0; k < cfg->n_point_masses; ++k) {
-        int s = slot_for(cfg->point_mass_body[k]);
-        if (s == -2) { delete ctx; nyx_set_error("too many / invalid point-mass bodies"); return NYX_HIP_RC_BAD_ARG; }
-        if (s == -1) continue;  // central body is skipped by PointMasses::eom (orbital.rs:219-222)
-        dc.pm_slot[dc.n_pm++] = s;
-    }
-    if (cfg->srp) {
-        dc.has_srp = 1;
-        dc.srp_estimate = cfg->srp->estimate;
-        dc.phi = cfg->srp->phi_w_m2;
-        dc.c_m_s = cfg->speed_of_light_km_s * 1e3;
-        int s = slot_for(cfg->srp->sun_body);
-        if (s < 0) { delete ctx; nyx_set_error("SRP light source must be a non-central body with an ephemeris"); return NYX_HIP_RC_BAD_ARG; }
-        dc.sun_slot = s;
-        dc.n_shadow = cfg->srp->n_shadow_bodies;
-        if (dc.n_shadow > DEV_MAX_SLOTS) { delete ctx; nyx_set_error("too many shadow bodies"); return NYX_HIP_RC_BAD_ARG; }
-        for (int k = 0; k < dc.n_shadow; ++k) {
-            int sb = slot_for(cfg->srp->shadow_body[k]);
-            if (sb == -2) { delete ctx; nyx_set_error("invalid shadow body"); return NYX_HIP_RC_BAD_ARG; }
-            dc.shadow_slot[k] = sb;
-        }
-    }
-    if (cfg->tides) {
-        const nyx_hip_solid_tides_t *td = cfg->tides;
-        dc.has_tides = 1;
-        dc.t_k2_5 = td->k2 / (2.0 * 2.0 + 1.0);
-        dc.t_k3_7 = td->k3 / (2.0 * 3.0 + 1.0);
-        dc.t_mu = td->mu_km3_s2; dc.t_re = td->eq_radius_km;
-        copy_rotation(dc.t_rot, td->rotation);
-        for (int j = 0; j < td->n_perturbers; ++j) {
-            const int b = td->perturber_body[j];
-            const int sl = slot_for(b);
-            if (sl < 0) { delete ctx; nyx_set_error("tidal perturbers must be non-central bodies with an ephemeris (and fit the %d slots)", DEV_MAX_SLOTS); return NYX_HIP_RC_BAD_ARG; }
-            dc.t_slot[dc.t_n] = sl;
-            dc.t_deg3[dc.t_n] = td->compute_degree_3[j] ? 1 : 0;
-            dc.t_gm_ratio[dc.t_n] = cfg->bodies[b].mu_km3_s2 / td->mu_km3_s2;
-            dc.t_n++;
-        }
-    }
-    // ---- segments
-    if (cfg->n_segments > DEV_MAX_SEG) { delete ctx; nyx_set_error("too many ephemeris segments"); return NYX_HIP_RC_BAD_ARG; }
-    std::vector<double> records;
-    dc.n_seg = cfg->n_segments;
-    // Device layout of the records.  cheby_eval() works on a sixteen-coefficient register window and has to blank the entries past a
-    // segment's own count (two v_cndmask per coefficient on the almanac wave, every stage).  When the whole table stays small the
-    // records of segments with <= 16 coefficients are therefore laid out SIXTEEN wide, zero-padded: the zeros are in the table, the
-    // selects go (DevSeg.stride = 50 tells the kernel; same values, same bits).
-    const int kChebWin = 16;
-    bool pad16 = true;
-    {
-        size_t packed = 0, padded = 0;
-        for (int i = 0; i < cfg->n_segments; ++i) {
-            const nyx_hip_cheby_segment_t &sg = cfg->segments[i];
-            packed += (size_t)sg.n_records * (size_t)(2 + 3 * sg.n_coeffs);
-            padded += (size_t)sg.n_records * (size_t)(2 + 3 * (sg.n_coeffs <= kChebWin ? kChebWin : sg.n_coeffs));
-        }
-        auto fits_lds = [&](size_t doubles) {  // the staging rule further down (rec_in_lds), for this context's kernel family
-            const int rd = (int)doubles + 16;
-            if ((size_t)rd * sizeof(double) > 24 * 1024) return false;
-            return (cfg->flags & NYX_HIP_FLAG_STM) ? nyx_kernel_lds_bytes(DEV_MAX_WAVES_STM, rd, 1, 0) <= 160 * 1024
-                                                   : nyx_kernel_lds_bytes(DEV_MAX_WAVES, rd, 0, 0) <= 160 * 1024;
-        };
-        if (fits_lds(packed) && !fits_lds(padded)) pad16 = false;  // (never push the table out of LDS)
-        if (padded * sizeof(double) > (size_t)8 << 20) pad16 = false;
-    }
-    for (int i = 0; i < cfg->n_segments; ++i) {
-        const nyx_hip_cheby_segment_t &sg = cfg->segments[i];
-        DevSeg &d = dc.seg[i];
-        d.init_et = sg.init_et_s; d.interval = sg.interval_s; d.n_rec = sg.n_records; d.n_coef = sg.n_coeffs;
-        d.end_et = sg.init_et_s + sg.interval_s * (double)sg.n_records;
-        const int src_stride = 2 + 3 * sg.n_coeffs;
-        d.offset = (int32_t)records.size();
-        if (pad16 && sg.n_coeffs < kChebWin) {
-            d.stride = 2 + 3 * kChebWin;
-            for (int r = 0; r < sg.n_records; ++r) {
-                const double *src = sg.records + (size_t)r * src_stride;
-                records.push_back(src[0]); records.push_back(src[1]);
-                for (int c = 0; c < 3; ++c)
-                    for (int j = 0; j < kChebWin; ++j) records.push_back(j < sg.n_coeffs ? src[2 + c * sg.n_coeffs + j] : 0.0);
-            }
-        } else {
-            d.stride = src_stride;
-            records.insert(records.end(), sg.records, sg.records + (size_t)sg.n_records * d.stride);
-        }
-    }
-    for (int s = 0; s < dc.n_slots; ++s)
-        for (int k = 0; k < dc.slot[s].n_chain; ++k)
-            if (dc.slot[s].seg[k] < 0 || dc.slot[s].seg[k] >= dc.n_seg) { delete ctx; nyx_set_error("bad chain segment index"); return NYX_HIP_RC_BAD_ARG; }
-
-    // ---- gravity field
-    std::vector<HarmEntry> tab;
-    std::vector<ColHdr> cols;
-    if (cfg->gravity) {
-        const nyx_hip_gravity_field_t *g = cfg->gravity;
-        if (g->degree < 1 || !g->c_nm || !g->s_nm) { delete ctx; nyx_set_error("bad gravity field"); return NYX_HIP_RC_BAD_ARG; }
-        dc.has_grav = 1; dc.deg = g->degree; dc.ord = std::min(g->order, g->degree);
-        dc.g_slot = -1;
-        if (g->offset_body != 0) {  // the field of another body than the integration centre (gravity_field.rs:150-154)
-            const int sl = slot_for(g->offset_body - 1);
-            if (sl == -2) { delete ctx; nyx_set_error("gravity field: offset_body is not a body of this configuration (or the %d body slots are taken)", DEV_MAX_SLOTS); return NYX_HIP_RC_BAD_ARG; }
-            dc.g_slot = sl;  // (-1: offset_body names the integration centre itself)
-            if (sl >= 0)
-                for (int k = 0; k < dc.slot[sl].n_chain; ++k)
-                    if (dc.slot[sl].seg[k] < 0 || dc.slot[sl].seg[k] >= dc.n_seg) { delete ctx; nyx_set_error("bad chain segment index"); return NYX_HIP_RC_BAD_ARG; }
-        }
-        dc.g_mu = g->mu_km3_s2; dc.g_re = g->eq_radius_km; dc.g_inv_re = 1.0 / g->eq_radius_km;
-        copy_rotation(dc.g_rot, g->rotation);
-        int n_cols = 0;
-        build_harmonics(g, tab, cols, ctx->col_len, n_cols);
-        dc.n_cols = n_cols;
-        ctx->h_tab = tab;
-        ctx->h_cols = cols;
-    }
-    std::vector<HarmEntry> tab2;
-    std::vector<ColHdr> cols2;
-    int terms2 = 0;
-    if (cfg->gravity2) {
-        const nyx_hip_gravity_field_t *g = cfg->gravity2;
-        if (!cfg->gravity) { delete ctx; nyx_set_error("gravity2 without gravity: a single field goes into `gravity`"); return NYX_HIP_RC_BAD_ARG; }
-        if (g->degree < 1 || !g->c_nm || !g->s_nm) { delete ctx; nyx_set_error("bad second gravity field"); return NYX_HIP_RC_BAD_ARG; }
-        dc.has_grav2 = 1;
-        dc.g2_mu = g->mu_km3_s2; dc.g2_re = g->eq_radius_km; dc.g2_inv_re = 1.0 / g->eq_radius_km;
-        copy_rotation(dc.g2_rot, g->rotation);
-        dc.g2_slot = -1;
-        if (g->offset_body != 0) {
-            const int sl = slot_for(g->offset_body - 1);
-            if (sl == -2) { delete ctx; nyx_set_error("second gravity field: offset_body is not a body of this configuration (or the %d body slots are taken)", DEV_MAX_SLOTS); return NYX_HIP_RC_BAD_ARG; }
-            dc.g2_slot = sl;
-            if (sl >= 0)
-                for (int k = 0; k < dc.slot[sl].n_chain; ++k)
-                    if (dc.slot[sl].seg[k] < 0 || dc.slot[sl].seg[k] >= dc.n_seg) { delete ctx; nyx_set_error("bad chain segment index"); return NYX_HIP_RC_BAD_ARG; }
-        }
-        std::vector<int32_t> len2;
-        int n_cols2 = 0;
-        build_harmonics(g, tab2, cols2, len2, n_cols2);
-        dc.n_cols2 = n_cols2;
-        for (int32_t l : len2) terms2 += l;
-        ctx->terms2 = terms2;
-    }
-    if (cfg->drag) {
-        const nyx_hip_drag_t *dg = cfg->drag;
-        if (dg->density < 0 || dg->density > 2) { delete ctx; nyx_set_error("bad drag density model"); return NYX_HIP_RC_BAD_ARG; }
-        dc.has_drag = 1; dc.drag_density = dg->density;
-        dc.drag_rho0 = dg->rho0; dc.drag_r0 = dg->r0; dc.drag_ref_alt_m = dg->ref_alt_m; dc.drag_max_alt_m = dg->max_alt_m;
-        dc.drag_re = dg->eq_radius_km;
-        copy_rotation(dc.d_rot, dg->rotation);
-    }
-    // serial duties of the role waves per force evaluation, in units of one harmonics term (~10 f64 ops):
-    // integrator: stage combination, body-fixed transform, fold of the partials; almanac: 3 sincos + Chebyshev
-    // chains; perturbations: third-body and SRP/eclipse terms.
-    {
-        int nseg_eval = 0;
-        for (int s = 0; s < dc.n_slots; ++s) nseg_eval += dc.slot[s].n_chain;
-        // (refitted in round 3 to the duties the calibration measures on the BASELINE workloads: 70x70 + Sun / Moon + SRP gives
-        //  integrator 66, almanac 140, perturbations 52 harmonics-term units - the first formulas were 2.2x too low)
-        ctx->role_handicap[0] = 60.0;
-        ctx->role_handicap[1] = 26.0 * nseg_eval + (dc.has_grav ? 38.0 : 0.0);
-        ctx->role_handicap[2] = (dc.has_grav2 ? 38.0 + 1.1 * terms2 : 0.0) + 13.0 * dc.n_pm + (dc.has_srp ? 13.0 + 13.0 * dc.n_shadow : 0.0) + (dc.has_drag ? 22.0 : 0.0) +
-                                (dc.has_tides ? 30.0 + 17.0 * dc.t_n : 0.0);
-        if (any_nonzero(ctx->tune.role_duties, 3))
-            for (int k = 0; k < 3; ++k) ctx->role_handicap[k] = ctx->tune.role_duties[k];
-    }
-    {
-        // the body-fixed frame of the epoch data (the kernel's choice: gravity field, else drag, else tides): a polynomial IAU
-        // orientation is advanced from a base epoch instead of being evaluated with three full-range sincos per stage
-        const DevRot &er = dc.has_grav ? dc.g_rot : (dc.has_drag ? dc.d_rot : dc.t_rot);
-        // (plain kernels only: the STM tests hold the device to the oracle's step sequence, bit for bit)
-        dc.dcm_incr = ((dc.has_grav || dc.has_drag || dc.has_tides) && er.kind == NYX_HIP_ROT_IAU && er.n_np == 0 && !(cfg->flags & NYX_HIP_FLAG_STM) &&
-                       !(ctx->tune.debug_flags & 0x4000)) ? 1 : 0;
-    }
-    records.resize(records.size() + 16, 0.0);  // padding for the 16-wide coefficient window
-    dc.rec_doubles = (int32_t)records.size();
-    dc.rec_in_lds = (records.size() * sizeof(double) <= 24 * 1024) ? 1 : 0;
-    if ((cfg->flags & NYX_HIP_FLAG_STM) && nyx_kernel_lds_bytes(DEV_MAX_WAVES_STM, dc.rec_doubles, 1, 0) > 160 * 1024) dc.rec_in_lds = 0;
-    if (!(cfg->flags & NYX_HIP_FLAG_STM) && nyx_kernel_lds_bytes(DEV_MAX_WAVES, dc.rec_doubles, 0, 0) > 160 * 1024) dc.rec_in_lds = 0;
-    // stage-0 epoch data carried between attempts (see role_loop): needs an even stage count (the last stage's window
-    // then leaves buffer 0 free) and 9 + 3 * n_slots doubles + 20 bytes of LDS per lane
-    dc.ed_reuse = 0;
-    if (!(cfg->flags & NYX_HIP_FLAG_STM) && dc.stages % 2 == 0 && ctx->tune.epoch_data_reuse != 0) {
-        const int nf = 9 + 3 * dc.n_slots;
-        if (nyx_kernel_lds_bytes(DEV_MAX_WAVES, dc.rec_in_lds ? dc.rec_doubles : 0, 0, nf) <= 160 * 1024) dc.ed_reuse = nf;
-    }
-    ctx->ed_reuse_fit = dc.ed_reuse;
-    dc.coop_frac = 0.30;  // measured optimum with two owners per helper (10 000 trajectories, 70x70): 0.28-0.33 is flat
-    if (ctx->tune.coop_fraction > 0.0) dc.coop_frac = std::min(0.9, std::max(0.05, ctx->tune.coop_fraction));
+    std::memcpy(&dc, &b.dc, sizeof dc);
+    ctx->swap_n_chain = b.swap_n_chain;
+    std::memcpy(ctx->swap_seg, b.swap_seg, sizeof b.swap_seg);
+    std::memcpy(ctx->swap_sign, b.swap_sign, sizeof b.swap_sign);
+    std::memcpy(ctx->role_handicap, b.role_handicap, sizeof b.role_handicap);
+    ctx->terms2 = b.terms2;
+    ctx->ed_reuse_fit = b.ed_reuse_fit;
+    ctx->col_len = b.col_len;
+    ctx->h_tab = b.tab;
+    ctx->h_cols = b.cols;
     {
         hipDeviceProp_t prop;
         ctx->n_cu = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
     }
-    build_schedule(plan_inputs(ctx), dc, ctx->shape, 1);
+    plan_first_schedule(plan_inputs(ctx.get()), dc, ctx->shape, b.harm_feed);
 
     // ---- upload
-    dc.hyb = 0;
-    dc.harm_feed = 0;
+    std::vector<HarmEntry> &tab = b.tab, &tab2 = b.tab2;
     if (!tab.empty()) {
         std::vector<double> hyb;
         int64_t vec_off = 0;
@@ -902,20 +501,13 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
         HIP_TRY(hipMemcpy(ctx->d_hyb, hyb.data(), hyb.size() * sizeof(double), hipMemcpyHostToDevice));
         dc.hyb = (uint64_t)ctx->d_hyb;
         dc.hyb_v = (uint64_t)(ctx->d_hyb + vec_off);
-        // measured (same box, calibrated): 150x150 cooperative 373 -> 334 ms per 6 250 x 3 h (1.12x); 70x70 alone 1.02-1.11x;
-        // 70x70 cooperative (one column per helper wave and job: the walk's start-up weighs more) 0-2 % slower
-        // (DevCfg.harm_feed: bit 0 = the trajectory-owning workgroups, bit 1 = the helpers and the owner's fallback for them)
-        // Round 4: the trajectory-owning workgroups stream the table from degree 40 on (with ONE contiguous run of columns per wave,
-        // fill_schedule: the start-up of a run is what the walk costs at 70x70), the helpers - one column per wave and job - above 95
-        dc.harm_feed = dc.n_cols > 96 ? 3 : (dc.n_cols > 40 ? 1 : 0);
-        if (ctx->tune.harmonics_feed >= 0) dc.harm_feed = ctx->tune.harmonics_feed == 0 ? 0 : (ctx->tune.harmonics_feed == 2 ? 1 : (ctx->tune.harmonics_feed == 3 ? 2 : 3));
     }
     if (!tab2.empty()) {
         tab2.resize(tab2.size() + 4 * HARM_BATCH, HarmEntry{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
         HIP_TRY(hipMalloc(&ctx->d_htab2, tab2.size() * sizeof(HarmEntry)));
         HIP_TRY(hipMemcpy(ctx->d_htab2, tab2.data(), tab2.size() * sizeof(HarmEntry), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&ctx->d_cols2, cols2.size() * sizeof(ColHdr)));
-        HIP_TRY(hipMemcpy(ctx->d_cols2, cols2.data(), cols2.size() * sizeof(ColHdr), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&ctx->d_cols2, b.cols2.size() * sizeof(ColHdr)));
+        HIP_TRY(hipMemcpy(ctx->d_cols2, b.cols2.data(), b.cols2.size() * sizeof(ColHdr), hipMemcpyHostToDevice));
         dc.htab2 = (uint64_t)ctx->d_htab2;
         dc.cols2 = (uint64_t)ctx->d_cols2;
     }
@@ -925,15 +517,15 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
         tab.resize(tab.size() + 4 * HARM_BATCH, HarmEntry{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0});  // the kernel touches a few batches ahead
         HIP_TRY(hipMalloc(&ctx->d_htab, tab.size() * sizeof(HarmEntry)));
         HIP_TRY(hipMemcpy(ctx->d_htab, tab.data(), tab.size() * sizeof(HarmEntry), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&ctx->d_cols, cols.size() * sizeof(ColHdr)));
-        HIP_TRY(hipMemcpy(ctx->d_cols, cols.data(), cols.size() * sizeof(ColHdr), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&ctx->d_cols, b.cols.size() * sizeof(ColHdr)));
+        HIP_TRY(hipMemcpy(ctx->d_cols, b.cols.data(), b.cols.size() * sizeof(ColHdr), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc(&ctx->d_records, records.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(ctx->d_records, records.data(), records.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&ctx->d_records, b.records.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(ctx->d_records, b.records.data(), b.records.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipEventCreate(&ctx->ev0));
     HIP_TRY(hipEventCreate(&ctx->ev1));
     HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
-    *out = ctx;
+    *out = ctx.release();
     return NYX_HIP_RC_OK;
 }
 
@@ -1108,8 +700,7 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
     {
         const int kind = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) ? (plan.quad ? 2 : 1) : 0;
         const int rd = ctx->host_cfg.rec_doubles;  // (after the schedule: chained attempts give the carried epoch data's LDS back)
-        const int want_rec = ((size_t)rd * sizeof(double) <= 24 * 1024 &&
-                              nyx_kernel_lds_bytes(DEV_MAX_WAVES, rd, kind, kind == 0 ? ctx->host_cfg.ed_reuse : 0) <= 160 * 1024) ? 1 : 0;
+        const int want_rec = records_fit_lds(nyx_kernel_lds_bytes, rd, DEV_MAX_WAVES, kind, kind == 0 ? ctx->host_cfg.ed_reuse : 0) ? 1 : 0;
         const bool dirty = plan.rebuilt || want_rec != ctx->host_cfg.rec_in_lds;
         ctx->host_cfg.rec_in_lds = want_rec;
         if (plan.rebuilt) ctx->rs_dirty = true;  // (the run streams follow the schedules)

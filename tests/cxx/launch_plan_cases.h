@@ -1,25 +1,128 @@
 // launch_plan_cases.h - the launch shapes tests/cxx/launch_plan_check.cpp plans (nyx_amd/csrc/launch_plan.h), and the one-line text
-// form of a plan that tests/golden/launch_plans.txt holds.  Force-model part of the DevCfg of the BASELINE workloads, built by hand the
-// way nyx_hip_ctx_create builds it (slots in the order the models name their bodies; the segments of nyx_amd/ephem.py:
-// 0 Sun / SSB (11 coefficients), 1 EMB / SSB, 2 Earth / EMB, 3 Moon / EMB (13 each), 4 Jupiter barycentre / SSB (8)).
+// form of a plan that tests/golden/launch_plans.txt holds.  The shapes are the configurations of the BASELINE workloads as
+// nyx_hip_config_t, built into a DevCfg by nyx_amd/csrc/ctx_build.h as nyx_hip_ctx_create builds them.  Bodies with the chains of
+// nyx_amd/ephem.py through its segments 0 Sun / SSB (11 coefficients), 1 EMB / SSB, 2 Earth / EMB, 3 Moon / EMB (13 each),
+// 4 Jupiter barycentre / SSB (8); synthetic records and Stokes coefficients (a plan depends on their counts only).
 #pragma once
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "../../include/nyx_hip.h"
 #include "../../nyx_amd/csrc/devcfg.h"
 
 namespace lpc {
 
+// A nyx_hip_config_t and the storage it points into (not copyable: it points into itself).
+struct Config {
+    nyx_hip_config_t cfg{};
+    nyx_hip_body_t bodies[NYX_HIP_MAX_BODIES]{};
+    nyx_hip_cheby_segment_t segments[NYX_HIP_MAX_SEGMENTS]{};
+    std::vector<double> records[NYX_HIP_MAX_SEGMENTS];
+    nyx_hip_gravity_field_t field[2]{};
+    std::vector<double> stokes[4];  // C, S of field[0], then of field[1]
+    nyx_hip_srp_t srp{};
+    nyx_hip_drag_t drag{};
+    nyx_hip_solid_tides_t tides{};
+    Config() = default;
+    Config(const Config &) = delete;
+    Config &operator=(const Config &) = delete;
+};
+
+// bodies of ephem_config(): Earth-centred (build_almanac) and Moon-centred (build_moon_centered_almanac)
+enum { EARTH = 0, SUN = 1, MOON = 2, JUPITER = 3 };
+enum { MC_MOON = 0, MC_EARTH = 1, MC_SUN = 2 };
+
+inline void add_segment(Config &c, int n_coeffs, int n_records = 2) {
+    const int i = c.cfg.n_segments++;
+    std::vector<double> &r = c.records[i];
+    r.resize((size_t)n_records * (2 + 3 * n_coeffs));
+    for (size_t k = 0; k < r.size(); ++k) r[k] = 1e3 * (i + 1) / (1.0 + (double)k) - 7.0 * (double)(k % 5);
+    c.segments[i] = nyx_hip_cheby_segment_t{7.6e8, 16 * 86400.0, n_records, n_coeffs, r.data()};
+}
+
+inline void add_body(Config &c, double mu, double radius, std::initializer_list<int> chain, std::initializer_list<int> signs) {
+    nyx_hip_body_t &b = c.bodies[c.cfg.n_bodies++];
+    b.naif_id = 10 * c.cfg.n_bodies;
+    b.mu_km3_s2 = mu; b.mean_radius_km = radius;
+    for (int g : chain) b.chain_segment[b.n_chain++] = g;
+    int k = 0;
+    for (int s : signs) b.chain_sign[k++] = s;
+}
+
+inline nyx_hip_rotation_t iau_rotation(int n_nut_prec = 0) {  // an IAU orientation (Earth-like), optionally with nutation terms
+    nyx_hip_rotation_t r{};
+    r.kind = NYX_HIP_ROT_IAU;
+    r.ra_deg[1] = -0.641; r.dec_deg[0] = 90.0; r.dec_deg[1] = -0.557; r.w_deg[0] = 190.147; r.w_deg[1] = 360.9856235;
+    r.n_nut_prec = n_nut_prec;
+    for (int k = 0; k < n_nut_prec; ++k) { r.nut_prec_angle_deg[k][0] = 125.0 + k; r.nut_prec_angle_deg[k][1] = -0.05 * (k + 1); r.nut_prec_ra[k] = 1e-3 * (k + 1); }
+    return r;
+}
+
+// field k (0: config.gravity, 1: config.gravity2): degree x degree, synthetic Stokes coefficients
+inline void set_field(Config &c, int k, int degree, int offset_body = 0) {
+    nyx_hip_gravity_field_t &f = c.field[k];
+    const size_t n = (size_t)(degree + 1) * (degree + 2) / 2;
+    std::vector<double> &C = c.stokes[2 * k], &S = c.stokes[2 * k + 1];
+    C.resize(n); S.resize(n);
+    for (size_t q = 0; q < n; ++q) { C[q] = q == 0 ? 1.0 : 1e-6 / (1.0 + (double)q); S[q] = q % 3 ? -5e-7 / (2.0 + (double)q) : 0.0; }
+    f.degree = degree; f.order = degree; f.offset_body = offset_body;
+    f.mu_km3_s2 = k ? 4902.8 : 398600.4415; f.eq_radius_km = k ? 1738.0 : 6378.1363;
+    f.c_nm = C.data(); f.s_nm = S.data();
+    f.rotation = iau_rotation();
+    (k ? c.cfg.gravity2 : c.cfg.gravity) = &f;
+}
+
+// the five segments and the bodies of one almanac; integration options of the BASELINE runs
+inline std::unique_ptr<Config> ephem_config(int method, uint32_t flags, bool moon_centred = false) {
+    std::unique_ptr<Config> p(new Config);
+    Config &c = *p;
+    c.cfg.abi_version = NYX_HIP_ABI_VERSION;
+    c.cfg.flags = flags;
+    c.cfg.opts = nyx_hip_integ_opts_t{60000000000LL, 1000000LL, 2700000000000LL, 1e-12, 50, 0, NYX_HIP_RSS_CARTESIAN_STEP, method};
+    c.cfg.speed_of_light_km_s = 299792.458;
+    c.cfg.segments = c.segments;
+    c.cfg.bodies = c.bodies;
+    for (int n : {11, 13, 13, 13, 8}) add_segment(c, n);
+    if (moon_centred) {
+        c.cfg.central_mu_km3_s2 = 4902.8;
+        add_body(c, 4902.8, 1737.4, {}, {});
+        add_body(c, 398600.4415, 6378.1363, {2, 3}, {+1, -1});
+        add_body(c, 1.32712440018e11, 695700.0, {0, 1, 3}, {+1, -1, -1});
+    } else {
+        c.cfg.central_mu_km3_s2 = 398600.4415;
+        add_body(c, 398600.4415, 6378.1363, {}, {});
+        add_body(c, 1.32712440018e11, 695700.0, {0, 1, 2}, {+1, -1, -1});
+        add_body(c, 4902.8, 1737.4, {3, 2}, {+1, -1});
+        add_body(c, 1.26712764e8, 71492.0, {4, 1, 2}, {+1, -1, -1});
+    }
+    return p;
+}
+
+inline void point_masses(Config &c, std::initializer_list<int> bodies) { for (int b : bodies) c.cfg.point_mass_body[c.cfg.n_point_masses++] = b; }
+
+inline void add_srp(Config &c, int sun, std::initializer_list<int> shadows) {
+    c.srp.phi_w_m2 = 1367.0; c.srp.sun_body = sun;
+    for (int b : shadows) c.srp.shadow_body[c.srp.n_shadow_bodies++] = b;
+    c.cfg.srp = &c.srp;
+}
+
+// configs[1]'s force model (bench --config 2) on a degree x degree field: Sun / Moon point masses + SRP with the Earth's shadow, RK89
+inline std::unique_ptr<Config> earth_sun_moon(int degree, uint32_t flags = 0) {
+    std::unique_ptr<Config> p = ephem_config(NYX_HIP_RK89, flags);
+    point_masses(*p, {SUN, MOON});
+    add_srp(*p, SUN, {EARTH});
+    set_field(*p, 0, degree);
+    return p;
+}
+
 struct Shape {
     std::string name;
-    std::unique_ptr<DevCfg> dc;     // force-model part; harm_feed = 0, as when nyx_hip_ctx_create builds the first schedule
-    int harm_feed = 0;              // set after that first schedule (nyx_hip_ctx_create)
-    std::vector<int32_t> col_len;
-    int terms2 = 0;
+    std::unique_ptr<Config> cfg;
 };
 
 struct Variant {
@@ -28,91 +131,35 @@ struct Variant {
     bool inject_weights = false;    // a calibrated-weights entry for every workgroup shape
 };
 
-inline void add_slot(DevCfg &dc, std::initializer_list<int> segs) {
-    DevSlot &s = dc.slot[dc.n_slots++];
-    s.n_chain = 0;
-    for (int g : segs) s.seg[s.n_chain++] = g;
-}
-
-inline void add_field(DevCfg &dc, std::vector<int32_t> &col_len, int deg) {
-    dc.has_grav = 1; dc.deg = deg; dc.ord = deg; dc.n_cols = deg + 1;
-    col_len.assign(dc.n_cols + 2, 0);
-    for (int c = 1; c <= dc.n_cols; ++c) col_len[c] = deg + 2 - c;  // (build_harmonics: rows of column c)
-}
-
-// what nyx_hip_ctx_create derives: the harmonics feed by field size, the role duties
-inline int auto_harm_feed(const DevCfg &dc) { return dc.n_cols > 96 ? 3 : (dc.n_cols > 40 ? 1 : 0); }
+// the LDS of the shapes here always has room for their records and the carried epoch data
+inline size_t lds_room(int, int, int, int) { return 0; }
 
 inline std::vector<Shape> shapes() {
     std::vector<Shape> v;
-    auto mk = [&](const char *name, int stages, uint32_t flags) -> Shape & {
-        v.emplace_back();
-        Shape &s = v.back();
-        s.name = name;
-        s.dc.reset(new DevCfg);
-        std::memset(s.dc.get(), 0, sizeof(DevCfg));
-        s.dc->stages = stages; s.dc->flags = (int32_t)flags; s.dc->g_slot = -1; s.dc->g2_slot = -1;
-        s.dc->n_seg = 5;
-        const int coef[5] = {11, 13, 13, 13, 8};
-        for (int k = 0; k < 5; ++k) s.dc->seg[k].n_coef = coef[k];
-        return s;
-    };
-    auto earth_sun_moon = [](DevCfg &dc) {  // PointMasses(Sun, Moon) + SRP with the Earth's shadow
-        add_slot(dc, {0, 1, 2}); add_slot(dc, {3, 2});
-        dc.n_pm = 2; dc.pm_slot[0] = 0; dc.pm_slot[1] = 1;
-        dc.has_srp = 1; dc.sun_slot = 0; dc.n_shadow = 1; dc.shadow_slot[0] = -1;
-    };
-    {   // configs[1] (bench --config 2): 70x70 + Sun / Moon + SRP, RK89
-        Shape &s = mk("cfg2_70x70", 16, 0);
-        earth_sun_moon(*s.dc); add_field(*s.dc, s.col_len, 70);
-    }
+    // configs[1] (bench --config 2): 70x70 + Sun / Moon + SRP, RK89
+    v.push_back(Shape{"cfg2_70x70", earth_sun_moon(70)});
     {   // config 3: JWST, Moon / Sun / Jupiter point masses + SRP (Earth and Moon shadows), no field
-        Shape &s = mk("cfg3_jwst", 16, 0);
-        add_slot(*s.dc, {3, 2}); add_slot(*s.dc, {0, 1, 2}); add_slot(*s.dc, {4, 1, 2});
-        s.dc->n_pm = 3; for (int k = 0; k < 3; ++k) s.dc->pm_slot[k] = k;
-        s.dc->has_srp = 1; s.dc->sun_slot = 1; s.dc->n_shadow = 2; s.dc->shadow_slot[0] = -1; s.dc->shadow_slot[1] = 0;
+        std::unique_ptr<Config> p = ephem_config(NYX_HIP_RK89, 0);
+        point_masses(*p, {MOON, SUN, JUPITER});
+        add_srp(*p, SUN, {EARTH, MOON});
+        v.push_back(Shape{"cfg3_jwst", std::move(p)});
     }
-    {   // config 4: STM on a 21x21 field + Sun / Moon + SRP (quad or D3 layout by ensemble size)
-        Shape &s = mk("cfg4_stm21", 16, NYX_HIP_FLAG_STM);
-        earth_sun_moon(*s.dc); add_field(*s.dc, s.col_len, 21);
-    }
+    // config 4: STM on a 21x21 field + Sun / Moon + SRP (quad or D3 layout by ensemble size)
+    v.push_back(Shape{"cfg4_stm21", earth_sun_moon(21, NYX_HIP_FLAG_STM)});
     {   // config 5: 150x150 lunar field + Earth / Sun point masses, DP78, Moon-centred chains
-        Shape &s = mk("cfg5_150x150", 13, 0);
-        add_slot(*s.dc, {2, 3}); add_slot(*s.dc, {0, 1, 3});
-        s.dc->n_pm = 2; s.dc->pm_slot[0] = 0; s.dc->pm_slot[1] = 1;
-        add_field(*s.dc, s.col_len, 150);
+        std::unique_ptr<Config> p = ephem_config(NYX_HIP_DP78, 0, true);
+        point_masses(*p, {MC_EARTH, MC_SUN});
+        set_field(*p, 0, 150);
+        v.push_back(Shape{"cfg5_150x150", std::move(p)});
     }
-    {   // a 21x21 field without the STM: eight-wave workgroups
-        Shape &s = mk("deg21", 16, 0);
-        earth_sun_moon(*s.dc); add_field(*s.dc, s.col_len, 21);
-    }
+    // a 21x21 field without the STM: eight-wave workgroups
+    v.push_back(Shape{"deg21", earth_sun_moon(21)});
     {   // a second field (a 10x10 lunar field beside the 70x70 Earth field)
-        Shape &s = mk("grav2_70+10", 16, 0);
-        earth_sun_moon(*s.dc); add_field(*s.dc, s.col_len, 70);
-        s.dc->has_grav2 = 1; s.dc->n_cols2 = 11; s.dc->g2_slot = 1;
-        for (int c = 1; c <= 11; ++c) s.terms2 += 12 - c;
+        std::unique_ptr<Config> p = earth_sun_moon(70);
+        set_field(*p, 1, 10, MOON + 1);
+        v.push_back(Shape{"grav2_70+10", std::move(p)});
     }
-    for (Shape &s : v) s.harm_feed = auto_harm_feed(*s.dc);
     return v;
-}
-
-// nyx_hip_ctx_create: integrator, almanac, perturbation duties in harmonics-term units
-inline void role_handicap(const DevCfg &dc, const nyx_hip_tuning_t &t, int terms2, double *rh) {
-    int nseg_eval = 0;
-    for (int s = 0; s < dc.n_slots; ++s) nseg_eval += dc.slot[s].n_chain;
-    rh[0] = 60.0;
-    rh[1] = 26.0 * nseg_eval + (dc.has_grav ? 38.0 : 0.0);
-    rh[2] = (dc.has_grav2 ? 38.0 + 1.1 * terms2 : 0.0) + 13.0 * dc.n_pm + (dc.has_srp ? 13.0 + 13.0 * dc.n_shadow : 0.0) + (dc.has_drag ? 22.0 : 0.0) +
-            (dc.has_tides ? 30.0 + 17.0 * dc.t_n : 0.0);
-    if (t.role_duties[0] != 0.0 || t.role_duties[1] != 0.0 || t.role_duties[2] != 0.0)
-        for (int k = 0; k < 3; ++k) rh[k] = t.role_duties[k];
-}
-// nyx_hip_ctx_create: the stage-0 epoch data an unchained loop may carry (the LDS always has room for the shapes here)
-inline int ed_reuse_fit(const DevCfg &dc, const nyx_hip_tuning_t &t) {
-    return (!(dc.flags & NYX_HIP_FLAG_STM) && dc.stages % 2 == 0 && t.epoch_data_reuse != 0) ? 9 + 3 * dc.n_slots : 0;
-}
-inline double initial_coop_frac(const nyx_hip_tuning_t &t) {
-    return t.coop_fraction > 0.0 ? (t.coop_fraction < 0.05 ? 0.05 : (t.coop_fraction > 0.9 ? 0.9 : t.coop_fraction)) : 0.30;
 }
 
 inline std::vector<Variant> variants() {

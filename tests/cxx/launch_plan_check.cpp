@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "../../nyx_amd/csrc/launch_plan.h"
+#include "../../nyx_amd/csrc/ctx_build.h"
 #include "launch_plan_cases.h"
 
 static int g_fail = 0;
@@ -32,20 +32,20 @@ struct Ctx {  // what nyx_hip_ctx keeps for the planner
 // nyx_hip_ctx_create, as far as the planner is concerned
 static void create(Ctx &c, const lpc::Shape &sh, const nyx_hip_tuning_t &tune, bool inject, int n_cu) {
     c.tune = tune;
-    std::memcpy(c.dc.get(), sh.dc.get(), sizeof(DevCfg));
-    DevCfg &dc = *c.dc;
-    dc.flags |= tune.debug_flags & 0xff00;
-    c.col_len = sh.col_len;
-    c.terms2 = sh.terms2;
-    lpc::role_handicap(dc, tune, sh.terms2, c.rh);
-    c.ed_reuse_fit = lpc::ed_reuse_fit(dc, tune);
-    dc.ed_reuse = c.ed_reuse_fit;
-    dc.coop_frac = lpc::initial_coop_frac(tune);
+    CtxBuild b;
+    if (build_context(sh.cfg->cfg, tune, lpc::lds_room, b) != NYX_HIP_RC_OK) {
+        std::printf("FAIL %s: %s\n", sh.name.c_str(), b.error.c_str());
+        std::exit(1);
+    }
+    std::memcpy(c.dc.get(), &b.dc, sizeof(DevCfg));
+    c.col_len = b.col_len;
+    c.terms2 = b.terms2;
+    std::memcpy(c.rh, b.role_handicap, sizeof c.rh);
+    c.ed_reuse_fit = b.ed_reuse_fit;
     c.n_cu = n_cu;
     c.shape = SchedShape();
     c.weights.clear();
-    build_schedule(c.in(), dc, c.shape, 1);
-    dc.harm_feed = sh.harm_feed;
+    plan_first_schedule(c.in(), *c.dc, c.shape, b.harm_feed);
     if (inject) lpc::inject_weights(c.weights);
 }
 
@@ -156,11 +156,7 @@ int main(int argc, char **argv) {
     {
         long builds = 0;
         for (int deg = 8; deg <= 150; ++deg) {
-            lpc::Shape sh;
-            sh.name = "deg" + std::to_string(deg);
-            sh.dc.reset(new DevCfg(*shapes[0].dc));
-            lpc::add_field(*sh.dc, sh.col_len, deg);
-            sh.harm_feed = lpc::auto_harm_feed(*sh.dc);
+            const lpc::Shape sh{"deg" + std::to_string(deg), lpc::earth_sun_moon(deg)};  // (configs[1]'s force model)
             for (int64_t n : lpc::kSizes) {
                 create(c, sh, NYX_HIP_TUNING_DEFAULT, false, 256);
                 const LaunchPlan p = plan_launch(c.in(), *c.dc, c.shape, n, false);

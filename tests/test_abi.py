@@ -119,7 +119,8 @@ def _create_rc(cc):
 
 def test_ctx_create_refuses_what_the_device_code_cannot_represent():
     """Plain-data validation happens before any device is touched: a segment the 16-wide Clenshaw window would truncate,
-    degenerate segments and over-long body chains are errors, never silently clipped."""
+    degenerate segments, over-long body chains, chains through missing segments, bodies a model cannot use, too many segments
+    and bad model parameters are errors, never silently clipped."""
     from nyx_amd import ephem
     day = 86400.0
     prop, _, central = leo_full_setup(degree=4)
@@ -148,6 +149,37 @@ def test_ctx_create_refuses_what_the_device_code_cannot_represent():
     for nc in (16, 32):
         rc, msg = _create_rc(prop.compile(almanac_with(nc), central))
         assert rc in (0, _abi.RC_NO_DEVICE), msg
+
+    # the refusals of the model and body checks come before the device check too: the same answer with and without a GPU
+    def refused(cc, why):
+        rc, msg = _create_rc(cc)
+        assert rc == _abi.RC_BAD_ARG and why in msg, (rc, msg)
+
+    prop, almanac, central = leo_full_setup(degree=4)
+    cc = prop.compile(almanac, central)
+    cc.cfg.bodies[1].chain_segment[0] = 99
+    refused(cc, "bad chain segment index")
+    cc = prop.compile(almanac, central)
+    cc.cfg.srp.contents.sun_body = 0
+    refused(cc, "SRP light source must be a non-central body")
+    cc = prop.compile(almanac, central)
+    cc.cfg.gravity2 = cc.cfg.gravity
+    cc.cfg.gravity = C.POINTER(_abi.GravityField)()
+    refused(cc, "gravity2 without gravity")
+    cc = prop.compile(almanac, central)
+    cc.cfg.gravity.contents.offset_body = 9
+    refused(cc, "gravity field: offset_body is not a body of this configuration")
+    cc = prop.compile(almanac, central)
+    cc.cfg.state_frame_body = 7
+    refused(cc, "state_frame_body: not a body of this configuration")
+    al = almanac_with(13)
+    for _ in range(8):
+        al.add_segment(ephem.fit_segment(ephem.sun_geocentric, 7.6e8, 16 * day, 3, 13))
+    refused(prop.compile(al, central), "too many ephemeris segments")
+    prop, almanac, central = leo_full_setup(degree=4, drag="exp")
+    cc = prop.compile(almanac, central)
+    cc.cfg.drag.contents.density = 3
+    refused(cc, "bad drag density model")
 
 
 LIVE_DEBUG_FLAGS = (0x100, 0x200, 0x400, 0x800, 0x4000, 0x8000, 0x10000, 0x80000, 0x100000, 0x2000000, 0x4000000, 0x8000000, 0x20000000)
