@@ -1,5 +1,6 @@
 // abi.cpp — host side of the C-ABI (include/nyx_hip.h): context creation (what it builds: ctx_build.h; the launch policy:
-// launch_plan.h; here the device, the uploads), batch staging and kernel launch.  Compiled with hipcc.
+// launch_plan.h; how a batch's arrays reach a launch: batch_bind.h; here the device, the uploads), batch staging and kernel launch.
+// Compiled with hipcc.
 
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/nyx_hip.h"
+#include "batch_bind.h"
 #include "ctx_build.h"
 #include "devcfg.h"
 #include "launch_plan.h"
@@ -181,6 +183,15 @@ static void mailbox_release(int device, void *ptr, int64_t cap, bool pooled = tr
     g_mailbox_free.push_back(MailboxBlock{device, ptr, cap});
 }
 
+static int ensure_stm(DevArrays &a, int64_t n) {  // (the STMs of the first n trajectories)
+    if (a.stm_cap >= n) return NYX_HIP_RC_OK;
+    (void)hipFree(a.stm);
+    a.stm = nullptr;
+    HIP_TRY(hipMalloc(&a.stm, (size_t)std::max<int64_t>(n, 1024) * 81 * sizeof(double)));
+    a.stm_cap = std::max<int64_t>(n, 1024);
+    return NYX_HIP_RC_OK;
+}
+
 static void free_arrays(DevArrays &a) {
     (void)hipFree(a.dblock);
     (void)hipHostFree(a.hblock);
@@ -323,17 +334,20 @@ extern "C" int32_t nyx_hip_ctx_set_column_waves(nyx_hip_ctx *ctx, int32_t waves)
 
 extern "C" int32_t nyx_hip_last_coop_helpers(nyx_hip_ctx *ctx) { return ctx ? ctx->last_coop_helpers : 0; }
 
-// Introspection: the per-wave column weights of the last launch's workgroup shape and the spread (max - min) / mean of the
-// per-wave windows measured when they were calibrated (-1 = structural default weights, never calibrated).  out[17].
-extern "C" int32_t nyx_hip_debug_weights(nyx_hip_ctx *ctx, double *out) {
+// The first `count` column weights of the last launch's workgroup shape (WeightMap), then the spread (max - min) / mean of the
+// per-wave windows measured when they were calibrated (-1 = structural default weights, never calibrated).
+static int32_t last_weights(nyx_hip_ctx *ctx, double *out, int count) {
     if (!ctx || !out) return NYX_HIP_RC_BAD_ARG;
     CTX_LOCK(ctx);
     const auto it = ctx->weights.find(ctx->last_key);
-    for (int w = 0; w < DEV_MAX_WAVES; ++w) out[w] = it != ctx->weights.end() ? it->second[w] : 0.0;  // (speed weights; the duties follow in the table)
+    for (int w = 0; w < count; ++w) out[w] = it != ctx->weights.end() ? it->second[w] : 0.0;
     const auto sp = ctx->weight_spread.find(ctx->last_key);
-    out[DEV_MAX_WAVES] = sp != ctx->weight_spread.end() ? sp->second : -1.0;
+    out[count] = sp != ctx->weight_spread.end() ? sp->second : -1.0;
     return NYX_HIP_RC_OK;
 }
+
+// Introspection: the speed weights and the spread, out[17].
+extern "C" int32_t nyx_hip_debug_weights(nyx_hip_ctx *ctx, double *out) { return last_weights(ctx, out, DEV_MAX_WAVES); }
 
 // Shape of the last launch's workgroups (tools): waves, pipelined loop, carried epoch-data fields, chained attempts, ephemeris
 // records in LDS, their size in doubles, almanac waves, LDS bytes of the plain kernel.
@@ -387,14 +401,14 @@ extern "C" int32_t nyx_hip_ctx_set_tuning(nyx_hip_ctx *ctx, const nyx_hip_tuning
 }
 
 // Speed weights [0..16), duties [16..32) and the window spread [32] of the last launch's workgroup shape (tools).
-extern "C" int32_t nyx_hip_debug_schedule_weights(nyx_hip_ctx *ctx, double *out) {
-    if (!ctx || !out) return NYX_HIP_RC_BAD_ARG;
-    CTX_LOCK(ctx);
-    const auto it = ctx->weights.find(ctx->last_key);
-    for (int w = 0; w < 2 * DEV_MAX_WAVES; ++w) out[w] = it != ctx->weights.end() ? it->second[w] : 0.0;
-    const auto sp = ctx->weight_spread.find(ctx->last_key);
-    out[2 * DEV_MAX_WAVES] = sp != ctx->weight_spread.end() ? sp->second : -1.0;
-    return NYX_HIP_RC_OK;
+extern "C" int32_t nyx_hip_debug_schedule_weights(nyx_hip_ctx *ctx, double *out) { return last_weights(ctx, out, 2 * DEV_MAX_WAVES); }
+
+// Table rows wave w walks under `sd` (a column outside the table counts nothing).
+static int rows_of(const nyx_hip_ctx *ctx, const DevSched &sd, int w) {
+    int rows = 0;
+    for (int q = 0; q < sd.n_ranges[w]; ++q)
+        for (int c = sd.range_c0[w][q]; c < sd.range_c0[w][q] + sd.range_cnt[w][q]; ++c) rows += (c >= 0 && c < (int)ctx->col_len.size()) ? ctx->col_len[c] : 0;
+    return rows;
 }
 
 // Table rows each wave walks under schedule `sched` (DEV_SCHED_*) of the current descriptor, and the role duties the water-filling
@@ -402,14 +416,7 @@ extern "C" int32_t nyx_hip_debug_schedule_weights(nyx_hip_ctx *ctx, double *out)
 extern "C" int32_t nyx_hip_debug_schedule_rows(nyx_hip_ctx *ctx, int32_t sched, int32_t *rows16, double *duties3) {
     if (!ctx || !rows16 || sched < 0 || sched >= DEV_N_SCHED) return NYX_HIP_RC_BAD_ARG;
     CTX_LOCK(ctx);
-    const DevSched &sd = ctx->host_cfg.sched[sched];
-    for (int w = 0; w < DEV_MAX_WAVES; ++w) {
-        int rows = 0;
-        for (int q = 0; q < sd.n_ranges[w]; ++q)
-            for (int c = sd.range_c0[w][q]; c < sd.range_c0[w][q] + sd.range_cnt[w][q]; ++c)
-                rows += (c >= 0 && c < (int)ctx->col_len.size()) ? ctx->col_len[c] : 0;
-        rows16[w] = rows;
-    }
+    for (int w = 0; w < DEV_MAX_WAVES; ++w) rows16[w] = rows_of(ctx, ctx->host_cfg.sched[sched], w);
     if (duties3) for (int k = 0; k < 3; ++k) duties3[k] = ctx->role_handicap[k];
     return NYX_HIP_RC_OK;
 }
@@ -422,14 +429,18 @@ extern "C" int32_t nyx_hip_debug_set_stm_layout(nyx_hip_ctx *ctx, int32_t quad) 
     return NYX_HIP_RC_OK;
 }
 
+// The time of the last timed kernel (ev0 -> ev1) into ctx->last_ms: -1 when it cannot be read.
+static double read_kernel_ms(nyx_hip_ctx *ctx) {
+    float ms = 0.f;
+    ctx->last_ms = (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ? ms : -1.0;
+    return ctx->last_ms;
+}
+
 extern "C" double nyx_hip_last_kernel_ms(nyx_hip_ctx *ctx) {
     if (!ctx || !ctx->ev1) return -1.0;
     CTX_LOCK(ctx);
     if (hipEventSynchronize(ctx->ev1) != hipSuccess) return -1.0;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) != hipSuccess) return -1.0;
-    ctx->last_ms = ms;
-    return ms;
+    return read_kernel_ms(ctx);
 }
 
 // Cycle accounting of workgroup 0 of the last launch (NYX_HIP_PROFILE=1): out[17][8], see the kernel (row 16: mailbox counters).
@@ -535,161 +546,67 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
 
 static bool calibration_on(const nyx_hip_ctx *ctx) { return ctx->tune.schedule == NYX_HIP_SCHED_CALIBRATED; }
 
-static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t *out, nyx_hip_step_stats_t *st,
-                  int64_t duration_ns, int64_t end_epoch_ns, int use_end, hipStream_t stream, bool time_it,
-                  const nyx_hip_traj_t *traj, const int64_t *dur_ns, const DevBatch *ev, bool calibrating, bool swapped = false);
+static int launch(nyx_hip_ctx *ctx, const LaunchReq &r);
 
 // Device views of a DevArrays block (outputs + stats).
 static void views_of(DevArrays &d, int64_t n, bool stm, nyx_hip_states_t &so, nyx_hip_step_stats_t &ss) {
     std::memset(&so, 0, sizeof so);
     so.n = n; so.epoch_ns = d.epoch;
-    double **f[13] = {&so.x_km, &so.y_km, &so.z_km, &so.vx_km_s, &so.vy_km_s, &so.vz_km_s, &so.cr, &so.cd,
-                      &so.prop_mass_kg, &so.dry_mass_kg, &so.extra_mass_kg, &so.srp_area_m2, &so.drag_area_m2};
-    for (int k = 0; k < 13; ++k) *f[k] = d.f[k];
+    for (int k = 0; k < kStateRows; ++k) so.*kStateRow[k].s = d.f[k];
     so.step_ns = d.step;
     so.stm = stm ? d.stm : nullptr;
     ss = {d.status, d.last_step, d.last_error, d.last_attempts, d.n_acc, d.n_rej, d.n_evals};
 }
 
-// On-device calibration of the column schedule of the shape the NEXT launch of `in` will have (replaces tables fitted
-// offline to one force model, and the guessed role handicaps).  Up to four short launches of the workload's own first
-// steps (30 steps; 4 with the STM) into scratch outputs, with the in-kernel cycle accounting on.  Per wave of workgroup 0:
-// duty[w] = cycles of role work inside the window, harm[w] = cycles in its columns, hence c[w] = harm / table entries = what
-// a table entry costs THIS wave (the four waves of a SIMD are arbitrated oldest first: the young ones are slower).  The
-// water-filling then gets the speed weight cbar / c[w] and the handicap duty[w] / c[w] (in entries), which makes
-// duty + columns equal across the waves; iterated with damping because the shares interact through the shared SIMDs.
-// Rounded to 1/64 and kept for the life of the context: launches of one context are deterministic.
+// On-device calibration of the column schedule of the shape the NEXT launch of `in` will have: up to four short launches of the
+// workload's own first steps (30 steps; 4 with the STM) into scratch outputs with the in-kernel cycle accounting on, each fitted by
+// calibration_fit (launch_plan.h), until the windows agree.  Kept for the life of the context: its launches are deterministic.
 static int calibrate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, hipStream_t stream, bool backward = false) {
     const bool stm = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
     const int64_t n = in->n;
     if (int rc = ensure_arrays(ctx->cal, n, true)) return rc;
-    if (stm && ctx->cal.stm_cap < n) {
-        (void)hipFree(ctx->cal.stm);
-        ctx->cal.stm = nullptr;
-        HIP_TRY(hipMalloc(&ctx->cal.stm, (size_t)std::max<int64_t>(n, 1024) * 81 * sizeof(double)));
-        ctx->cal.stm_cap = std::max<int64_t>(n, 1024);
-    }
+    if (int rc = stm ? ensure_stm(ctx->cal, n) : NYX_HIP_RC_OK) return rc;
     nyx_hip_states_t so;
     nyx_hip_step_stats_t ss;
     views_of(ctx->cal, n, stm, so, ss);
-    const int64_t dur = (backward ? -1 : 1) * (stm ? 4 : 30) * ctx->host_cfg.init_step_ns;  // the direction of the real request: the ephemerides may end either way
+    LaunchReq r;
+    r.in = in; r.out = &so; r.stats = &ss; r.stream = stream; r.calibrating = true;
+    r.duration_ns = (backward ? -1 : 1) * (stm ? 4 : 30) * ctx->host_cfg.init_step_ns;  // the direction of the real request: the ephemerides may end either way
     std::vector<int32_t> cal_status((size_t)n);
-    std::array<double, 2 * DEV_MAX_WAVES> w;
-    bool have = false;
+    CalibrationFit fit;  // the last usable one
     WKey key(0, 0, 0, 0);
-    double spread = 0.0;
     std::vector<int64_t> prof(17 * 8);
     for (int it = 0; it < 4; ++it) {
-        if (have) { ctx->weights[key] = w; ctx->sched_dirty = true; }
-        if (int rc = launch(ctx, in, &so, &ss, dur, 0, 0, stream, false, nullptr, nullptr, nullptr, true)) return rc;
+        if (fit.usable) { ctx->weights[key] = fit.w; ctx->sched_dirty = true; }
+        if (int rc = launch(ctx, r)) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(prof.data(), ctx->d_prof, prof.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         if (ss.status) {  // lanes that died early produce garbage cycle counts: keep the model's weights then
             HIP_TRY(hipMemcpy(cal_status.data(), ss.status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
             bool bad = false;
             for (int64_t q = 0; q < n && !bad; ++q) bad = cal_status[(size_t)q] != NYX_HIP_OK;
-            if (bad) { have = false; ctx->weights.erase(ctx->last_key); ctx->sched_dirty = true; break; }
+            if (bad) { fit.usable = false; ctx->weights.erase(ctx->last_key); ctx->sched_dirty = true; break; }
         }
         key = ctx->last_key;
-        const int nw = std::get<0>(key);
         const DevSched &sd = ctx->host_cfg.sched[std::get<3>(key) >= 0 ? DEV_SCHED_PRIMARY : DEV_SCHED_SOLO];
-        // what the launch measured, per wave of workgroup 0: duty = role work inside the window, harm = its columns
-        double duty[DEV_MAX_WAVES], harm[DEV_MAX_WAVES], ent[DEV_MAX_WAVES], cpe[DEV_MAX_WAVES];
-        double csum = 0.0, lo = 1e300, hi = 0.0, tmean = 0.0;
-        int ccnt = 0, tcnt = 0;
-        for (int q = 0; q < nw; ++q) {
-            duty[q] = (double)prof[q * 8 + 1];
-            harm[q] = (double)prof[q * 8 + 2];
-            ent[q] = 0.0;
-            for (int r = 0; r < sd.n_ranges[q]; ++r)
-                for (int c = sd.range_c0[q][r]; c < sd.range_c0[q][r] + sd.range_cnt[q][r]; ++c) ent[q] += ctx->col_len[c];
-            cpe[q] = (ent[q] > 0.0 && harm[q] > 0.0) ? harm[q] / ent[q] : 0.0;   // cycles per table entry, as this wave sees them
-            if (cpe[q] > 0.0) { csum += cpe[q]; ++ccnt; }
-            if (q > 0 || nw < 8) {
-                const double t = duty[q] + (ent[q] > 0.0 ? harm[q] : 0.0);
-                if (t > 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); tmean += t; ++tcnt; }
-            }
-        }
-        if (ccnt < 2 || tcnt < 2) break;
-        const double cbar = csum / ccnt;
-        spread = (hi - lo) / (tmean / tcnt);
-        std::array<double, 2 * DEV_MAX_WAVES> nwgt;
-        for (int q = 0; q < DEV_MAX_WAVES; ++q) {
-            // a wave that carried no columns this time is given the speed of its SIMD age class (waves q, q+4, q+8, q+12 share a SIMD)
-            double c = q < nw ? cpe[q] : 0.0;
-            if (!(c > 0.0)) {
-                double a = 0.0; int an = 0;
-                for (int k = (q / 4) * 4; k < (q / 4) * 4 + 4 && k < nw; ++k) if (cpe[k] > 0.0) { a += cpe[k]; ++an; }
-                c = an ? a / an : cbar;
-            }
-            nwgt[q] = cbar / c;
-            nwgt[DEV_MAX_WAVES + q] = q < nw ? duty[q] / c : 0.0;
-        }
-        for (int q = 0; q < 2 * DEV_MAX_WAVES; ++q) {
-            const double v = have ? 0.5 * (w[q] + nwgt[q]) : nwgt[q];  // damped: the shares interact through the shared SIMDs
-            w[q] = std::round(v * 64.0) / 64.0;
-        }
-        have = true;
-        if (it > 0 && spread < 0.08) break;
+        const CalibrationFit f = calibration_fit(prof.data(), sd, ctx->col_len, std::get<0>(key), fit.usable ? &fit.w : nullptr);
+        if (!f.usable) break;
+        fit = f;
+        if (it > 0 && fit.spread < 0.08) break;
     }
-    if (have) {
-        ctx->weights[key] = w;
-        ctx->weight_spread[key] = spread;
+    if (fit.usable) {
+        ctx->weights[key] = fit.w;
+        ctx->weight_spread[key] = fit.spread;
         ctx->sched_dirty = true;
     }
     return NYX_HIP_RC_OK;
 }
 
-static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t *out, nyx_hip_step_stats_t *st,
-                  int64_t duration_ns, int64_t end_epoch_ns, int use_end, hipStream_t stream, bool time_it,
-                  const nyx_hip_traj_t *traj = nullptr, const int64_t *dur_ns = nullptr, const DevBatch *ev = nullptr, bool calibrating = false,
-                  bool swapped) {
+// One launch, in the frame the context integrates in.
+static int launch_here(nyx_hip_ctx *ctx, const LaunchReq &r) {
     CTX_LOCK(ctx);
-    if (ctx->swap_n_chain > 0 && !swapped && !calibrating) {
-        // opts.integration_frame (instance.rs:117-142, 211-220): translate a COPY of the Cartesian state into the integration frame
-        // at the start epochs, propagate that, translate the final states back at their own epochs
-        // Dense output and per-trajectory durations go through (round 4).  What the reference's `Traj` holds then (instance.rs:297-326
-        // around :117-142): the START state as it was handed in - its own frame -, every published state in the INTEGRATION frame (the
-        // channel is fed inside the loop, the translation back is applied to the returned state only, :211-220).  Reproduced as is:
-        // entry 0 of the dense output is rewritten with the caller's state below.  The event search is still refused: there the
-        // reference returns from inside the loop without translating back (:243-250) - a state whose frame depends on how the run ended.
-        if (ev) {
-            nyx_set_error("integration-frame swap: the event search does not take states of another frame");
-            return NYX_HIP_RC_UNSUPPORTED;
-        }
-        if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // (the copy below is shared by the launches of this context)
-        if (ctx->swap_cap < in->n) {
-            (void)hipFree(ctx->d_swap);
-            ctx->d_swap = nullptr; ctx->swap_cap = 0;
-            HIP_TRY(hipMalloc(&ctx->d_swap, (size_t)7 * (size_t)in->n * sizeof(double)));  // (row 6: the forward shift's status words)
-            ctx->swap_cap = in->n;
-        }
-        nyx_hip_states_t in2 = *in;
-        double *rows[6];
-        const double *src[6] = {in->x_km, in->y_km, in->z_km, in->vx_km_s, in->vy_km_s, in->vz_km_s};
-        for (int q = 0; q < 6; ++q) {
-            rows[q] = ctx->d_swap + (size_t)q * (size_t)ctx->swap_cap;
-            HIP_TRY(hipMemcpyAsync(rows[q], src[q], (size_t)in->n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        }
-        in2.x_km = rows[0]; in2.y_km = rows[1]; in2.z_km = rows[2]; in2.vx_km_s = rows[3]; in2.vy_km_s = rows[4]; in2.vz_km_s = rows[5];
-        // a start epoch outside the swap body's ephemeris gives a clamped, i.e. WRONG, translation: its status is kept aside and
-        // merged into the run's status by the back-translation (the propagation launch rewrites the status array in between)
-        int32_t *fwd_status = (int32_t *)(ctx->d_swap + (size_t)6 * (size_t)ctx->swap_cap);
-        HIP_TRY(hipMemsetAsync(fwd_status, 0, (size_t)in->n * sizeof(int32_t), stream));
-        HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg, ctx->d_records, ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, in->epoch_ns,
-                                       rows[0], rows[1], rows[2], rows[3], rows[4], rows[5], +1.0, fwd_status, nullptr, dur_ns, stream));
-        if (int rc = launch(ctx, &in2, out, st, duration_ns, end_epoch_ns, use_end, stream, time_it, traj, dur_ns, nullptr, false, true)) return rc;
-        if (traj && traj->capacity > 0) {  // entry 0 (step-major: the first n elements of every array) = the state in the caller's frame
-            double *dst[6] = {traj->x_km, traj->y_km, traj->z_km, traj->vx_km_s, traj->vy_km_s, traj->vz_km_s};
-            for (int q = 0; q < 6; ++q)
-                if (dst[q]) HIP_TRY(hipMemcpyAsync(dst[q], src[q], (size_t)in->n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        }
-        HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg, ctx->d_records, ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, out->epoch_ns,
-                                       out->x_km, out->y_km, out->z_km, out->vx_km_s, out->vy_km_s, out->vz_km_s, -1.0, st ? st->status : nullptr,
-                                       fwd_status, dur_ns, stream));
-        HIP_TRY(hipEventRecord(ctx->ev_done, stream));
-        return NYX_HIP_RC_OK;
-    }
+    const hipStream_t stream = (hipStream_t)r.stream;
+    const nyx_hip_states_t *in = r.in;
     if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // one launch of a context at a time on the device
     // launch-shape dependent parts of the descriptor: waves per workgroup, column schedules and cooperative mode (launch_plan.h),
     // and whether the ephemeris records fit in LDS next to this layout's buffers (the quad layout is smaller than the D3 one)
@@ -706,52 +623,20 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
         if (plan.rebuilt) ctx->rs_dirty = true;  // (the run streams follow the schedules)
         if (dirty) HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
     }
-    DevBatch bt;
-    std::memset(&bt, 0, sizeof bt);
-    bt.n = in->n;
-    bt.duration_ns = duration_ns; bt.end_epoch_ns = end_epoch_ns; bt.use_end_epoch = use_end;
-    bt.epoch_ns = in->epoch_ns;
-    bt.x = in->x_km; bt.y = in->y_km; bt.z = in->z_km; bt.vx = in->vx_km_s; bt.vy = in->vy_km_s; bt.vz = in->vz_km_s;
-    bt.cr = in->cr; bt.cd = in->cd; bt.mprop = in->prop_mass_kg; bt.mdry = in->dry_mass_kg; bt.mextra = in->extra_mass_kg;
-    bt.asrp = in->srp_area_m2; bt.adrag = in->drag_area_m2; bt.step_in = in->step_ns;
-    bt.dur_ns = dur_ns;
-    bt.pred = ctx->fused_pred;
-    if (ev) {  // stop condition: only the ev_* fields of `ev` are read
-        bt.ev_on = 1; bt.ev = ev->ev; bt.ev_mu = ev->ev_mu;
-        bt.ev_prev = ev->ev_prev; bt.ev_count = ev->ev_count; bt.ev_found = ev->ev_found;
-    }
-    if (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) {
-        if (!in->stm || !out->stm) { nyx_set_error("STM context: in->stm and out->stm are mandatory"); return NYX_HIP_RC_BAD_ARG; }
-        bt.stm = in->stm; bt.o_stm = out->stm;
-        if (ctx->host_cfg.flags & NYX_HIP_FLAG_STM_TEXTBOOK) {
-            if (ctx->stm_hist_cap < in->n) {
-                if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
-                (void)hipFree(ctx->d_stm_hist);
-                ctx->d_stm_hist = nullptr; ctx->stm_hist_cap = 0;
-                const int64_t cap = (in->n + 63) / 64 * 64;
-                HIP_TRY(hipMalloc(&ctx->d_stm_hist, (size_t)DEV_MAX_STAGES * 12 * (size_t)cap * sizeof(double)));
-                ctx->stm_hist_cap = cap;
-            }
-            bt.stm_hist = ctx->d_stm_hist;
-            bt.stm_hist_stride = ctx->stm_hist_cap;
+    BoundBatch b = bind_batch(r, (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0, ctx->fused_pred);
+    if (b.rc != NYX_HIP_RC_OK) { nyx_set_error("%s", b.error); return b.rc; }
+    DevBatch &bt = b.bt;
+    if (ctx->host_cfg.flags & NYX_HIP_FLAG_STM_TEXTBOOK) {
+        if (ctx->stm_hist_cap < in->n) {
+            if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
+            (void)hipFree(ctx->d_stm_hist);
+            ctx->d_stm_hist = nullptr; ctx->stm_hist_cap = 0;
+            const int64_t cap = (in->n + 63) / 64 * 64;
+            HIP_TRY(hipMalloc(&ctx->d_stm_hist, (size_t)DEV_MAX_STAGES * 12 * (size_t)cap * sizeof(double)));
+            ctx->stm_hist_cap = cap;
         }
-    }
-    bt.o_epoch_ns = out->epoch_ns;
-    bt.o_x = out->x_km; bt.o_y = out->y_km; bt.o_z = out->z_km; bt.o_vx = out->vx_km_s; bt.o_vy = out->vy_km_s; bt.o_vz = out->vz_km_s;
-    bt.o_cr = out->cr; bt.o_cd = out->cd; bt.o_mprop = out->prop_mass_kg; bt.o_mdry = out->dry_mass_kg;
-    bt.o_mextra = out->extra_mass_kg; bt.o_asrp = out->srp_area_m2; bt.o_adrag = out->drag_area_m2; bt.o_step = out->step_ns;
-    if (traj && traj->capacity > 0) {
-        if (!traj->epoch_ns || !traj->x_km || !traj->y_km || !traj->z_km || !traj->vx_km_s || !traj->vy_km_s || !traj->vz_km_s || !traj->len) {
-            nyx_set_error("traj: every array is mandatory");
-            return NYX_HIP_RC_BAD_ARG;
-        }
-        bt.traj_cap = traj->capacity; bt.t_epoch = traj->epoch_ns; bt.t_len = traj->len;
-        bt.t_state[0] = traj->x_km; bt.t_state[1] = traj->y_km; bt.t_state[2] = traj->z_km;
-        bt.t_state[3] = traj->vx_km_s; bt.t_state[4] = traj->vy_km_s; bt.t_state[5] = traj->vz_km_s;
-    }
-    if (st) {
-        bt.status = st->status; bt.last_step_ns = st->last_step_ns; bt.last_error = st->last_error;
-        bt.last_attempts = st->last_attempts; bt.n_acc = st->n_accepted; bt.n_rej = st->n_rejected; bt.n_evals = st->n_evals;
+        bt.stm_hist = ctx->d_stm_hist;
+        bt.stm_hist_stride = ctx->stm_hist_cap;
     }
     // Cooperative mode (plan.coop): helper workgroups on the idle CUs take over a share of the harmonics columns
     // (propagate_kernel.hip).  Owners and helpers that talk to each other get block indices that agree modulo 8 (round-robin XCD
@@ -824,27 +709,74 @@ static int launch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t
         // the column weights of this launch's workgroup shape: measured once per context (see calibrate())
         const WKey key = weight_key(ctx->host_cfg, nw, plan.quad, bt.coop_helpers > 0);
         ctx->last_key = key;
-        const int64_t span = use_end ? INT64_MAX : (duration_ns < 0 ? -duration_ns : duration_ns);
-        if (!calibrating && calibration_on(ctx) && ctx->host_cfg.has_grav && nw >= 8 && in->n >= 64 && !traj && !dur_ns && !ev &&
+        const int64_t span = r.use_end ? INT64_MAX : (r.duration_ns < 0 ? -r.duration_ns : r.duration_ns);
+        if (!r.calibrating && calibration_on(ctx) && ctx->host_cfg.has_grav && nw >= 8 && in->n >= 64 && !r.traj && !r.dur_ns && !r.ev &&
             span >= 100 * ctx->host_cfg.init_step_ns && !ctx->weights.count(key)) {
-            if (int rc = calibrate(ctx, in, stream, !use_end && duration_ns < 0)) return rc;
-            return launch(ctx, in, out, st, duration_ns, end_epoch_ns, use_end, stream, time_it, traj, dur_ns, ev, false, swapped);
+            if (int rc = calibrate(ctx, in, stream, !r.use_end && r.duration_ns < 0)) return rc;
+            return launch_here(ctx, r);
         }
     }
-    if (ctx->tune.profile || calibrating) {
+    if (ctx->tune.profile || r.calibrating) {
         if (!ctx->d_prof) HIP_TRY(hipMalloc(&ctx->d_prof, 36 * 8 * sizeof(int64_t)));  // rows 0-15 owner workgroup 0, 16 mailbox counts, 17-32 the first helper workgroup
         HIP_TRY(hipMemsetAsync(ctx->d_prof, 0, 36 * 8 * sizeof(int64_t), stream));
         bt.prof = ctx->d_prof;
     }
-    if (time_it) HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    if (r.timed) HIP_TRY(hipEventRecord(ctx->ev0, stream));
     const bool quad = plan.quad;
     // (the LDS staging of the ephemeris records was decided at ctx_create for the D3 layout; the quad layout is smaller)
     HIP_TRY(nyx_launch_propagate(bt, ctx->d_cfg, ctx->d_htab, ctx->d_cols, ctx->d_records, nw,
                                  ctx->host_cfg.rec_in_lds ? ctx->host_cfg.rec_doubles : 0, ctx->host_cfg.ed_reuse, stream, quad ? 1 : 0,
                                  (!ctx->host_cfg.has_grav && !ctx->host_cfg.has_drag && !ctx->host_cfg.has_tides && !ctx->host_cfg.has_grav2) ? 1 : 0));
-    if (time_it) HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    if (r.timed) HIP_TRY(hipEventRecord(ctx->ev1, stream));
     HIP_TRY(hipEventRecord(ctx->ev_done, stream));
     ctx->launched = true;
+    return NYX_HIP_RC_OK;
+}
+
+static int launch(nyx_hip_ctx *ctx, const LaunchReq &r) {
+    CTX_LOCK(ctx);
+    if (ctx->swap_n_chain == 0 || r.calibrating) return launch_here(ctx, r);
+    // opts.integration_frame (instance.rs:117-142, 211-220): translate a COPY of the Cartesian state into the integration frame
+    // at the start epochs, propagate that, translate the final states back at their own epochs
+    // Dense output and per-trajectory durations go through (round 4).  What the reference's `Traj` holds then (instance.rs:297-326
+    // around :117-142): the START state as it was handed in - its own frame -, every published state in the INTEGRATION frame (the
+    // channel is fed inside the loop, the translation back is applied to the returned state only, :211-220).  Reproduced as is:
+    // entry 0 of the dense output is rewritten with the caller's state below.  The event search is still refused: there the
+    // reference returns from inside the loop without translating back (:243-250) - a state whose frame depends on how the run ended.
+    if (r.ev) {
+        nyx_set_error("integration-frame swap: the event search does not take states of another frame");
+        return NYX_HIP_RC_UNSUPPORTED;
+    }
+    const hipStream_t stream = (hipStream_t)r.stream;
+    const nyx_hip_states_t *in = r.in, *out = r.out;
+    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // (the copy below is shared by the launches of this context)
+    if (ctx->swap_cap < in->n) {
+        (void)hipFree(ctx->d_swap);
+        ctx->d_swap = nullptr; ctx->swap_cap = 0;
+        HIP_TRY(hipMalloc(&ctx->d_swap, (size_t)7 * (size_t)in->n * sizeof(double)));  // (row 6: the forward shift's status words)
+        ctx->swap_cap = in->n;
+    }
+    nyx_hip_states_t in2 = *in;
+    for (int q = 0; q < kCartRows; ++q) {
+        double *row = in2.*kStateRow[q].s = ctx->d_swap + (size_t)q * (size_t)ctx->swap_cap;
+        HIP_TRY(hipMemcpyAsync(row, in->*kStateRow[q].s, (size_t)in->n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    }
+    // a start epoch outside the swap body's ephemeris gives a clamped, i.e. WRONG, translation: its status is kept aside and
+    // merged into the run's status by the back-translation (the propagation launch rewrites the status array in between)
+    int32_t *fwd_status = (int32_t *)(ctx->d_swap + (size_t)6 * (size_t)ctx->swap_cap);
+    HIP_TRY(hipMemsetAsync(fwd_status, 0, (size_t)in->n * sizeof(int32_t), stream));
+    HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg, ctx->d_records, ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, in->epoch_ns,
+                                   in2.x_km, in2.y_km, in2.z_km, in2.vx_km_s, in2.vy_km_s, in2.vz_km_s, +1.0, fwd_status, nullptr, r.dur_ns, stream));
+    LaunchReq r2 = r;
+    r2.in = &in2;
+    if (int rc = launch_here(ctx, r2)) return rc;
+    if (r.traj && r.traj->capacity > 0)  // entry 0 (step-major: the first n elements of every array) = the state in the caller's frame
+        for (int q = 0; q < kCartRows; ++q)
+            if (double *dst = r.traj->*kTrajRow[q]) HIP_TRY(hipMemcpyAsync(dst, in->*kStateRow[q].s, (size_t)in->n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg, ctx->d_records, ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, out->epoch_ns,
+                                   out->x_km, out->y_km, out->z_km, out->vx_km_s, out->vy_km_s, out->vz_km_s, -1.0, r.stats ? r.stats->status : nullptr,
+                                   fwd_status, r.dur_ns, stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
     return NYX_HIP_RC_OK;
 }
 
@@ -856,28 +788,30 @@ static int check_states(const nyx_hip_states_t *s, const char *what) {
     return NYX_HIP_RC_OK;
 }
 
-extern "C" int32_t nyx_hip_propagate_batch_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
-                                                  nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, void *hip_stream) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
+// The device entry points: the caller's device arrays, on the caller's stream.
+static int propagate_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns, nyx_hip_states_t *out,
+                            nyx_hip_step_stats_t *stats, const nyx_hip_traj_t *traj, void *hip_stream) {
     if (int rc = check_states(in, "in")) return rc;
     if (int rc = check_states(out, "out")) return rc;
     if (in->n == 0) return NYX_HIP_RC_OK;
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = launch(ctx, in, out, stats, duration_ns, 0, 0, (hipStream_t)hip_stream, true);
-    return rc;
+    LaunchReq r;
+    r.in = in; r.out = out; r.stats = stats; r.duration_ns = duration_ns; r.traj = traj; r.stream = hip_stream; r.timed = true;
+    return launch(ctx, r);
+}
+
+extern "C" int32_t nyx_hip_propagate_batch_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
+                                                  nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, void *hip_stream) {
+    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
+    return propagate_device(ctx, in, duration_ns, out, stats, nullptr, hip_stream);
 }
 
 extern "C" int32_t nyx_hip_propagate_batch_with_traj_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
                                                             nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj,
                                                             void *hip_stream) {
     if (!ctx || !traj) { nyx_set_error("null ctx / traj"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_states(in, "in")) return rc;
-    if (int rc = check_states(out, "out")) return rc;
-    if (in->n == 0) return NYX_HIP_RC_OK;
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    return launch(ctx, in, out, stats, duration_ns, 0, 0, (hipStream_t)hip_stream, true, traj);
+    return propagate_device(ctx, in, duration_ns, out, stats, traj, hip_stream);
 }
 
 // Device views of a staged host batch: `din` lives in ctx->in, `dout` / `dst` in ctx->out.
@@ -894,43 +828,23 @@ static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_h
     if (int rc = ensure_arrays(ctx->in, n, false)) return rc;
     if (int rc = ensure_arrays(ctx->out, n, true)) return rc;
     DevArrays &di = ctx->in, &dq = ctx->out;
-    const double *hin[13] = {in->x_km, in->y_km, in->z_km, in->vx_km_s, in->vy_km_s, in->vz_km_s, in->cr, in->cd,
-                             in->prop_mass_kg, in->dry_mass_kg, in->extra_mass_kg, in->srp_area_m2, in->drag_area_m2};
+    nyx_hip_states_t &din = sg.din;  // (rows the caller left null stay null)
+    std::memset(&din, 0, sizeof din);
+    din.n = n; din.epoch_ns = di.epoch;
     std::memcpy(di.host(di.epoch), in->epoch_ns, n * sizeof(int64_t));
-    for (int k = 0; k < 13; ++k)
-        if (hin[k]) std::memcpy(di.host(di.f[k]), hin[k], n * sizeof(double));
-    if (in->step_ns) std::memcpy(di.host(di.step), in->step_ns, n * sizeof(int64_t));
-    HIP_TRY(hipMemcpy(di.dblock, di.hblock, (size_t)((char *)(di.f[12] + di.cap) - di.dblock), hipMemcpyHostToDevice));
+    for (int k = 0; k < kStateRows; ++k)
+        if (const double *h = in->*kStateRow[k].s) std::memcpy(di.host(din.*kStateRow[k].s = di.f[k]), h, n * sizeof(double));
+    if (in->step_ns) std::memcpy(di.host(din.step_ns = di.step), in->step_ns, n * sizeof(int64_t));
+    HIP_TRY(hipMemcpy(di.dblock, di.hblock, (size_t)((char *)(di.f[kStateRows - 1] + di.cap) - di.dblock), hipMemcpyHostToDevice));
     sg.stm = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
     if (sg.stm) {
         if (upload_stm && (!in->stm || !out->stm)) { nyx_set_error("STM context: in->stm and out->stm are mandatory"); return NYX_HIP_RC_BAD_ARG; }
-        for (DevArrays *d : {&di, &dq}) {
-            if (d->stm_cap < n) {
-                hipFree(d->stm);
-                d->stm = nullptr;
-                HIP_TRY(hipMalloc(&d->stm, (size_t)std::max<int64_t>(n, 1024) * 81 * sizeof(double)));
-                d->stm_cap = std::max<int64_t>(n, 1024);
-            }
-        }
+        for (DevArrays *d : {&di, &dq})
+            if (int rc = ensure_stm(*d, n)) return rc;
         if (upload_stm) HIP_TRY(hipMemcpy(di.stm, in->stm, (size_t)n * 81 * sizeof(double), hipMemcpyHostToDevice));
     }
-    nyx_hip_states_t &din = sg.din;
-    std::memset(&din, 0, sizeof din);
-    din.n = n; din.epoch_ns = di.epoch;
-    double **dinf[13] = {&din.x_km, &din.y_km, &din.z_km, &din.vx_km_s, &din.vy_km_s, &din.vz_km_s, &din.cr, &din.cd,
-                         &din.prop_mass_kg, &din.dry_mass_kg, &din.extra_mass_kg, &din.srp_area_m2, &din.drag_area_m2};
-    for (int k = 0; k < 13; ++k) *dinf[k] = hin[k] ? di.f[k] : nullptr;
-    din.step_ns = in->step_ns ? di.step : nullptr;
     din.stm = sg.stm ? di.stm : nullptr;
-    nyx_hip_states_t &dout = sg.dout;
-    std::memset(&dout, 0, sizeof dout);
-    dout.n = n; dout.epoch_ns = dq.epoch;
-    double **doutf[13] = {&dout.x_km, &dout.y_km, &dout.z_km, &dout.vx_km_s, &dout.vy_km_s, &dout.vz_km_s, &dout.cr, &dout.cd,
-                          &dout.prop_mass_kg, &dout.dry_mass_kg, &dout.extra_mass_kg, &dout.srp_area_m2, &dout.drag_area_m2};
-    for (int k = 0; k < 13; ++k) *doutf[k] = dq.f[k];
-    dout.step_ns = dq.step;
-    dout.stm = sg.stm ? dq.stm : nullptr;
-    sg.dst = {dq.status, dq.last_step, dq.last_error, dq.last_attempts, dq.n_acc, dq.n_rej, dq.n_evals};
+    views_of(dq, n, sg.stm, sg.dout, sg.dst);
     return NYX_HIP_RC_OK;
 }
 
@@ -938,26 +852,48 @@ static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_h
 static int fetch_batch(nyx_hip_ctx *ctx, int64_t n, bool stm, nyx_hip_states_t *out, nyx_hip_step_stats_t *stats) {
     DevArrays &dq = ctx->out;
     HIP_TRY(hipMemcpy(dq.hblock, dq.dblock, dq.bytes, hipMemcpyDeviceToHost));
-    double *hout[13] = {out->x_km, out->y_km, out->z_km, out->vx_km_s, out->vy_km_s, out->vz_km_s, out->cr, out->cd,
-                        out->prop_mass_kg, out->dry_mass_kg, out->extra_mass_kg, out->srp_area_m2, out->drag_area_m2};
-    std::memcpy(out->epoch_ns, dq.host(dq.epoch), n * sizeof(int64_t));
-    for (int k = 0; k < 13; ++k)
-        if (hout[k]) std::memcpy(hout[k], dq.host(dq.f[k]), n * sizeof(double));
-    if (out->step_ns) std::memcpy(out->step_ns, dq.host(dq.step), n * sizeof(int64_t));
+    auto get = [&](auto *h, auto *dev) { if (h) std::memcpy(h, dq.host(dev), n * sizeof *h); };
+    get(out->epoch_ns, dq.epoch);
+    for (int k = 0; k < kStateRows; ++k) get(out->*kStateRow[k].s, dq.f[k]);
+    get(out->step_ns, dq.step);
     if (stm && out->stm) HIP_TRY(hipMemcpy(out->stm, dq.stm, (size_t)n * 81 * sizeof(double), hipMemcpyDeviceToHost));
     if (stats) {
-        if (stats->status) std::memcpy(stats->status, dq.host(dq.status), n * sizeof(int32_t));
-        if (stats->last_step_ns) std::memcpy(stats->last_step_ns, dq.host(dq.last_step), n * sizeof(int64_t));
-        if (stats->last_error) std::memcpy(stats->last_error, dq.host(dq.last_error), n * sizeof(double));
-        if (stats->last_attempts) std::memcpy(stats->last_attempts, dq.host(dq.last_attempts), n * sizeof(int32_t));
-        if (stats->n_accepted) std::memcpy(stats->n_accepted, dq.host(dq.n_acc), n * sizeof(int64_t));
-        if (stats->n_rejected) std::memcpy(stats->n_rejected, dq.host(dq.n_rej), n * sizeof(int64_t));
-        if (stats->n_evals) std::memcpy(stats->n_evals, dq.host(dq.n_evals), n * sizeof(int64_t));
+        get(stats->status, dq.status); get(stats->last_step_ns, dq.last_step); get(stats->last_error, dq.last_error);
+        get(stats->last_attempts, dq.last_attempts); get(stats->n_accepted, dq.n_acc); get(stats->n_rejected, dq.n_rej); get(stats->n_evals, dq.n_evals);
     }
     return NYX_HIP_RC_OK;
 }
 
-static int host_propagate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns, int64_t end_epoch_ns, int use_end,
+// A nyx_hip_traj_t whose arrays are one device allocation (RAII), laid out by traj_in_block (batch_bind.h).
+struct DevTraj {
+    nyx_hip_traj_t t;
+    void *block = nullptr;
+    size_t slots = 0;
+    int64_t n = 0;
+    ~DevTraj() { if (block) (void)hipFree(block); }
+    int alloc(int64_t capacity, int64_t n_) {
+        n = n_;
+        slots = (size_t)capacity * (size_t)n;
+        if (hipMalloc(&block, traj_block_bytes(capacity, n)) != hipSuccess) {
+            block = nullptr;
+            nyx_set_error("hipMalloc of the trajectory staging block failed");
+            return NYX_HIP_RC_HIP_ERROR;
+        }
+        t = traj_in_block(block, capacity, n);
+        return NYX_HIP_RC_OK;
+    }
+    int upload(const nyx_hip_traj_t *h) const { return copy(*h, t, hipMemcpyHostToDevice); }
+    int download(nyx_hip_traj_t *h) const { return copy(t, *h, hipMemcpyDeviceToHost); }
+    int copy(const nyx_hip_traj_t &from, const nyx_hip_traj_t &to, hipMemcpyKind kind) const {
+        HIP_TRY(hipMemcpy(to.len, from.len, (size_t)n * sizeof(int32_t), kind));
+        if (!slots) return NYX_HIP_RC_OK;
+        HIP_TRY(hipMemcpy(to.epoch_ns, from.epoch_ns, slots * sizeof(int64_t), kind));
+        for (int c = 0; c < kCartRows; ++c) HIP_TRY(hipMemcpy(to.*kTrajRow[c], from.*kTrajRow[c], slots * sizeof(double), kind));
+        return NYX_HIP_RC_OK;
+    }
+};
+
+static int host_propagate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns, int64_t end_epoch_ns, bool use_end,
                           nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj = nullptr) {
     if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
     if (int rc = check_states(in, "in")) return rc;
@@ -972,88 +908,45 @@ static int host_propagate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t 
     Staged sg;
     if (int rc = stage_batch(ctx, in, out, sg)) return rc;
     if (trace) std::fprintf(stderr, "[nyx_hip] staged, launching\n");
-
-    nyx_hip_traj_t dtraj;
-    std::memset(&dtraj, 0, sizeof dtraj);
-    void *traj_block = nullptr;
-    if (traj && traj->capacity > 0) {
-        const size_t slots = (size_t)traj->capacity * (size_t)n;
-        HIP_TRY(hipMalloc(&traj_block, slots * 7 * sizeof(double) + (size_t)n * sizeof(int32_t)));
-        dtraj.capacity = traj->capacity;
-        dtraj.epoch_ns = (int64_t *)traj_block;
-        double *base = (double *)traj_block + slots;
-        dtraj.x_km = base; dtraj.y_km = base + slots; dtraj.z_km = base + 2 * slots;
-        dtraj.vx_km_s = base + 3 * slots; dtraj.vy_km_s = base + 4 * slots; dtraj.vz_km_s = base + 5 * slots;
-        dtraj.len = (int32_t *)(base + 6 * slots);
-    }
-    if (int rc = launch(ctx, &sg.din, &sg.dout, &sg.dst, duration_ns, end_epoch_ns, use_end, nullptr, true, traj_block ? &dtraj : nullptr)) {
-        if (traj_block) (void)hipFree(traj_block);
-        return rc;
-    }
+    const bool dense = traj && traj->capacity > 0;
+    DevTraj dtraj;
+    if (int rc = dense ? dtraj.alloc(traj->capacity, n) : NYX_HIP_RC_OK) return rc;
+    LaunchReq r;
+    r.in = &sg.din; r.out = &sg.dout; r.stats = &sg.dst; r.timed = true;
+    r.duration_ns = duration_ns; r.end_epoch_ns = end_epoch_ns; r.use_end = use_end; r.traj = dense ? &dtraj.t : nullptr;
+    if (int rc = launch(ctx, r)) return rc;
     if (trace) std::fprintf(stderr, "[nyx_hip] launched (%d helpers, %d waves), synchronising\n", ctx->last_coop_helpers, ctx->host_cfg.n_waves);
     HIP_TRY(hipDeviceSynchronize());
     if (trace) std::fprintf(stderr, "[nyx_hip] kernel done\n");
-    if (traj_block) {
-        const size_t slots = (size_t)traj->capacity * (size_t)n;
-        HIP_TRY(hipMemcpy(traj->len, dtraj.len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(traj->epoch_ns, dtraj.epoch_ns, slots * sizeof(int64_t), hipMemcpyDeviceToHost));
-        double *hdst[6] = {traj->x_km, traj->y_km, traj->z_km, traj->vx_km_s, traj->vy_km_s, traj->vz_km_s};
-        double *dsrc[6] = {dtraj.x_km, dtraj.y_km, dtraj.z_km, dtraj.vx_km_s, dtraj.vy_km_s, dtraj.vz_km_s};
-        for (int k = 0; k < 6; ++k) HIP_TRY(hipMemcpy(hdst[k], dsrc[k], slots * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipFree(traj_block));
-    }
-    {
-        float ms = 0.f;
-        ctx->last_ms = (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ? ms : -1.0;
-    }
+    if (int rc = dense ? dtraj.download(traj) : NYX_HIP_RC_OK) return rc;
+    read_kernel_ms(ctx);
     return fetch_batch(ctx, n, sg.stm, out, stats);
 }
 
 extern "C" int32_t nyx_hip_propagate_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
                                            nyx_hip_states_t *out, nyx_hip_step_stats_t *stats) {
-    return host_propagate(ctx, in, duration_ns, 0, 0, out, stats);
+    return host_propagate(ctx, in, duration_ns, 0, false, out, stats);
 }
 
 extern "C" int32_t nyx_hip_propagate_batch_with_traj(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
                                                      nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj) {
     if (!traj || traj->capacity < 1) { nyx_set_error("traj with capacity >= 1 required"); return NYX_HIP_RC_BAD_ARG; }
-    return host_propagate(ctx, in, duration_ns, 0, 0, out, stats, traj);
+    return host_propagate(ctx, in, duration_ns, 0, false, out, stats, traj);
 }
 
 extern "C" int32_t nyx_hip_propagate_until_epoch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t end_epoch_ns,
                                                  nyx_hip_states_t *out, nyx_hip_step_stats_t *stats) {
-    return host_propagate(ctx, in, 0, end_epoch_ns, 1, out, stats);
+    return host_propagate(ctx, in, 0, end_epoch_ns, true, out, stats);
 }
 
 // ---------------------------------------------------------------------------------------------
 // One batch over several contexts = several devices of one node, from ONE process (what replaces the rayon par_iter of
-// mc/montecarlo.rs:233-253 when the host is not sharded by rank): contiguous index shards (shard k of m holds
-// [k n / m, (k + 1) n / m), the rule of nyx_amd.shard_bounds), one host thread per context so that the staging copies
-// and the kernels of the devices overlap, results written in place at the shard's offset - the "gather" is free because the
-// arrays are structure-of-arrays.  With a trajectory the shards record into private buffers (the step-major layout has the
-// batch size as its stride) and are scattered afterwards.  Trajectories are independent: no device-to-device traffic at all.
+// mc/montecarlo.rs:233-253 when the host is not sharded by rank): contiguous index shards (shard_begin, batch_bind.h), one host
+// thread per context so that the staging copies and the kernels of the devices overlap, results written in place at the shard's
+// offset - the "gather" is free because the arrays are structure-of-arrays.  With a trajectory the shards record into private
+// buffers (the step-major layout has the batch size as its stride) and are scattered afterwards.  Trajectories are independent:
+// no device-to-device traffic at all.
 // ---------------------------------------------------------------------------------------------
-static nyx_hip_states_t states_at(const nyx_hip_states_t &s, int64_t lo, int64_t n) {
-    nyx_hip_states_t v = s;
-    v.n = n;
-    auto off = [&](auto *p) { return p ? p + lo : p; };
-    v.epoch_ns = off(s.epoch_ns);
-    v.x_km = off(s.x_km); v.y_km = off(s.y_km); v.z_km = off(s.z_km);
-    v.vx_km_s = off(s.vx_km_s); v.vy_km_s = off(s.vy_km_s); v.vz_km_s = off(s.vz_km_s);
-    v.cr = off(s.cr); v.cd = off(s.cd); v.prop_mass_kg = off(s.prop_mass_kg); v.dry_mass_kg = off(s.dry_mass_kg);
-    v.extra_mass_kg = off(s.extra_mass_kg); v.srp_area_m2 = off(s.srp_area_m2); v.drag_area_m2 = off(s.drag_area_m2);
-    v.stm = s.stm ? s.stm + lo * 81 : nullptr;
-    v.step_ns = off(s.step_ns);
-    return v;
-}
-static nyx_hip_step_stats_t stats_at(const nyx_hip_step_stats_t &s, int64_t lo) {
-    nyx_hip_step_stats_t v = s;
-    auto off = [&](auto *p) { return p ? p + lo : p; };
-    v.status = off(s.status); v.last_step_ns = off(s.last_step_ns); v.last_error = off(s.last_error);
-    v.last_attempts = off(s.last_attempts); v.n_accepted = off(s.n_accepted); v.n_rejected = off(s.n_rejected); v.n_evals = off(s.n_evals);
-    return v;
-}
-
 extern "C" int32_t nyx_hip_propagate_batch_sharded(nyx_hip_ctx *const *ctxs, int32_t n_ctx, const nyx_hip_states_t *in, int64_t duration_ns,
                                                    nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj) {
     if (!ctxs || n_ctx < 1 || !in || !out) { nyx_set_error("sharded: null argument or no context"); return NYX_HIP_RC_BAD_ARG; }
@@ -1064,11 +957,10 @@ extern "C" int32_t nyx_hip_propagate_batch_sharded(nyx_hip_ctx *const *ctxs, int
     const int64_t n = in->n, cap = traj ? traj->capacity : 0;
     std::vector<int32_t> rcs((size_t)n_ctx, NYX_HIP_RC_OK);
     std::vector<std::string> errs((size_t)n_ctx);
-    struct ShardTraj { std::vector<int64_t> ep; std::vector<double> f[6]; std::vector<int32_t> len; };
-    std::vector<ShardTraj> st((size_t)n_ctx);
+    std::vector<std::vector<double>> blocks((size_t)n_ctx);  // the shards' trajectory blocks (traj_in_block)
     std::vector<std::thread> threads;
     for (int32_t k = 0; k < n_ctx; ++k) {
-        const int64_t lo = n * k / n_ctx, hi = n * (k + 1) / n_ctx;
+        const int64_t lo = shard_begin(n, k, n_ctx), hi = shard_begin(n, k + 1, n_ctx);
         if (hi == lo) continue;
         threads.emplace_back([&, k, lo, hi]() {
             const nyx_hip_states_t vi = states_at(*in, lo, hi - lo);
@@ -1077,11 +969,9 @@ extern "C" int32_t nyx_hip_propagate_batch_sharded(nyx_hip_ctx *const *ctxs, int
             if (stats) vs = stats_at(*stats, lo);
             int32_t rc;
             if (traj) {
-                ShardTraj &t = st[(size_t)k];
-                const size_t cells = (size_t)((hi - lo) * cap);
-                t.ep.resize(cells); t.len.assign((size_t)(hi - lo), 0);
-                for (auto &f : t.f) f.resize(cells);
-                nyx_hip_traj_t vt{cap, t.ep.data(), t.f[0].data(), t.f[1].data(), t.f[2].data(), t.f[3].data(), t.f[4].data(), t.f[5].data(), t.len.data()};
+                std::vector<double> &b = blocks[(size_t)k];
+                b.assign((traj_block_bytes(cap, hi - lo) + sizeof(double) - 1) / sizeof(double), 0.0);
+                nyx_hip_traj_t vt = traj_in_block(b.data(), cap, hi - lo);
                 rc = nyx_hip_propagate_batch_with_traj(ctxs[k], &vi, duration_ns, &vo, stats ? &vs : nullptr, &vt);
             } else {
                 rc = nyx_hip_propagate_batch(ctxs[k], &vi, duration_ns, &vo, stats ? &vs : nullptr);
@@ -1093,18 +983,11 @@ extern "C" int32_t nyx_hip_propagate_batch_sharded(nyx_hip_ctx *const *ctxs, int
     for (auto &t : threads) t.join();
     for (int32_t k = 0; k < n_ctx; ++k)
         if (rcs[(size_t)k] != NYX_HIP_RC_OK) { nyx_set_error("shard %d: %s", k, errs[(size_t)k].c_str()); return rcs[(size_t)k]; }
-    if (traj) {  // scatter the shards' step-major blocks (stride = shard size) into the batch's (stride = n)
+    if (traj)  // the shards' step-major blocks (stride = shard size) into the batch's (stride = n)
         for (int32_t k = 0; k < n_ctx; ++k) {
-            const int64_t lo = n * k / n_ctx, hi = n * (k + 1) / n_ctx, m = hi - lo;
-            const ShardTraj &t = st[(size_t)k];
-            for (int64_t i = 0; i < m; ++i) traj->len[lo + i] = t.len[(size_t)i];
-            for (int64_t s2 = 0; s2 < cap; ++s2) {
-                std::memcpy(traj->epoch_ns + s2 * n + lo, t.ep.data() + s2 * m, (size_t)m * sizeof(int64_t));
-                double *dst[6] = {traj->x_km, traj->y_km, traj->z_km, traj->vx_km_s, traj->vy_km_s, traj->vz_km_s};
-                for (int c = 0; c < 6; ++c) std::memcpy(dst[c] + s2 * n + lo, t.f[c].data() + s2 * m, (size_t)m * sizeof(double));
-            }
+            const int64_t lo = shard_begin(n, k, n_ctx), m = shard_begin(n, k + 1, n_ctx) - lo;
+            if (m) scatter_traj(traj_in_block(blocks[(size_t)k].data(), cap, m), lo, m, *traj, n);
         }
-    }
     return NYX_HIP_RC_OK;
 }
 
@@ -1171,8 +1054,7 @@ static int moments_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *s, const int
     MomArgs a;
     std::memset(&a, 0, sizeof a);
     a.n = s->n;
-    const double *f[9] = {s->x_km, s->y_km, s->z_km, s->vx_km_s, s->vy_km_s, s->vz_km_s, s->cr, s->cd, s->prop_mass_kg};
-    for (int k = 0; k < 9; ++k) { a.f[k] = f[k]; a.x0[k] = x0 ? x0[k] : 0.0; }
+    for (int k = 0; k < kMomentRows; ++k) { a.f[k] = s->*kStateRow[k].s; a.x0[k] = x0 ? x0[k] : 0.0; }
     a.status = status;
     a.partial = ctx->d_mom;
     if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // (the scratch is the context's: one reduction at a time)
@@ -1201,21 +1083,20 @@ extern "C" int32_t nyx_hip_ensemble_moments(nyx_hip_ctx *ctx, const nyx_hip_stat
     // host arrays: one device block of 9 rows (+ the status words), copied row by row; the reduction itself is two small launches
     char *blk = nullptr;
     const size_t row = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
-    HIP_TRY(hipMalloc((void **)&blk, 9 * row + (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&blk, kMomentRows * row + (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
     nyx_hip_states_t d;
     std::memset(&d, 0, sizeof d);
     d.n = n;
-    const double *h[9] = {states->x_km, states->y_km, states->z_km, states->vx_km_s, states->vy_km_s, states->vz_km_s, states->cr, states->cd, states->prop_mass_kg};
-    double **dp[9] = {&d.x_km, &d.y_km, &d.z_km, &d.vx_km_s, &d.vy_km_s, &d.vz_km_s, &d.cr, &d.cd, &d.prop_mass_kg};
     int rc = NYX_HIP_RC_OK;
-    for (int k = 0; k < 9 && rc == NYX_HIP_RC_OK; ++k) {
-        if (!h[k]) continue;
-        *dp[k] = (double *)(blk + (size_t)k * row);
-        if (n > 0 && hipMemcpy(*dp[k], h[k], (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
+    for (int k = 0; k < kMomentRows && rc == NYX_HIP_RC_OK; ++k) {
+        const double *h = states->*kStateRow[k].s;
+        if (!h) continue;
+        double *dk = d.*kStateRow[k].s = (double *)(blk + (size_t)k * row);
+        if (n > 0 && hipMemcpy(dk, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
     }
     int32_t *dst = nullptr;
     if (rc == NYX_HIP_RC_OK && status) {
-        dst = (int32_t *)(blk + 9 * row);
+        dst = (int32_t *)(blk + kMomentRows * row);
         if (n > 0 && hipMemcpy(dst, status, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
     }
     if (rc == NYX_HIP_RC_OK) {
@@ -1227,50 +1108,6 @@ extern "C" int32_t nyx_hip_ensemble_moments(nyx_hip_ctx *ctx, const nyx_hip_stat
     (void)hipFree(blk);
     return rc;
 }
-
-// A nyx_hip_traj_t whose arrays are one device allocation (RAII).
-struct DevTraj {
-    nyx_hip_traj_t t;
-    void *block = nullptr;
-    size_t slots = 0;
-    int64_t n = 0;
-    ~DevTraj() { if (block) (void)hipFree(block); }
-    int alloc(int64_t capacity, int64_t n_) {
-        n = n_;
-        slots = (size_t)capacity * (size_t)n;
-        std::memset(&t, 0, sizeof t);
-        if (hipMalloc(&block, std::max<size_t>(slots, 1) * 7 * sizeof(double) + (size_t)n * sizeof(int32_t)) != hipSuccess) {
-            block = nullptr;
-            nyx_set_error("hipMalloc of the trajectory staging block failed");
-            return NYX_HIP_RC_HIP_ERROR;
-        }
-        t.capacity = capacity;
-        t.epoch_ns = (int64_t *)block;
-        double *base = (double *)block + std::max<size_t>(slots, 1);
-        t.x_km = base; t.y_km = base + slots; t.z_km = base + 2 * slots;
-        t.vx_km_s = base + 3 * slots; t.vy_km_s = base + 4 * slots; t.vz_km_s = base + 5 * slots;
-        t.len = (int32_t *)(base + 6 * std::max<size_t>(slots, 1));
-        return NYX_HIP_RC_OK;
-    }
-    int upload(const nyx_hip_traj_t *h) {
-        HIP_TRY(hipMemcpy(t.len, h->len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (!slots) return NYX_HIP_RC_OK;
-        HIP_TRY(hipMemcpy(t.epoch_ns, h->epoch_ns, slots * sizeof(int64_t), hipMemcpyHostToDevice));
-        const double *hsrc[6] = {h->x_km, h->y_km, h->z_km, h->vx_km_s, h->vy_km_s, h->vz_km_s};
-        double *ddst[6] = {t.x_km, t.y_km, t.z_km, t.vx_km_s, t.vy_km_s, t.vz_km_s};
-        for (int k = 0; k < 6; ++k) HIP_TRY(hipMemcpy(ddst[k], hsrc[k], slots * sizeof(double), hipMemcpyHostToDevice));
-        return NYX_HIP_RC_OK;
-    }
-    int download(nyx_hip_traj_t *h) const {
-        HIP_TRY(hipMemcpy(h->len, t.len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (!slots) return NYX_HIP_RC_OK;
-        HIP_TRY(hipMemcpy(h->epoch_ns, t.epoch_ns, slots * sizeof(int64_t), hipMemcpyDeviceToHost));
-        double *hdst[6] = {h->x_km, h->y_km, h->z_km, h->vx_km_s, h->vy_km_s, h->vz_km_s};
-        const double *dsrc[6] = {t.x_km, t.y_km, t.z_km, t.vx_km_s, t.vy_km_s, t.vz_km_s};
-        for (int k = 0; k < 6; ++k) HIP_TRY(hipMemcpy(hdst[k], dsrc[k], slots * sizeof(double), hipMemcpyDeviceToHost));
-        return NYX_HIP_RC_OK;
-    }
-};
 
 static int traj_eval_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query, int64_t m,
                           int64_t step_ns, nyx_hip_traj_t *out, int32_t *status, int mode) {
@@ -1299,8 +1136,7 @@ static int traj_eval_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t 
     if (!rc) rc = traj_eval_device(ctx, &src.t, n, d_query, m, step_ns, &dst.t, d_status, mode, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) { nyx_set_error("trajectory evaluation kernel failed"); rc = NYX_HIP_RC_HIP_ERROR; }
     if (!rc) {
-        float ms = 0.f;
-        ctx->last_ms = (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ? ms : -1.0;
+        read_kernel_ms(ctx);
         rc = dst.download(out);
     }
     if (!rc && d_status && hipMemcpy(status, d_status, (size_t)m * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
@@ -1381,19 +1217,17 @@ extern "C" int32_t nyx_hip_propagate_until_event(nyx_hip_ctx *ctx, const nyx_hip
     ev.ev_count = (int32_t *)(evbuf.as<double>() + n);
     ev.ev_found = ev.ev_count + n;
     HIP_TRY(hipMemset(evbuf.p, 0, (size_t)n * 16));
-    if (int rc = launch(ctx, &sg.din, &sg.dout, &sg.dst, max_duration_ns, 0, 0, nullptr, true, &dtraj.t, nullptr, &ev)) return rc;
+    LaunchReq r;
+    r.in = &sg.din; r.out = &sg.dout; r.stats = &sg.dst; r.duration_ns = max_duration_ns; r.traj = &dtraj.t; r.ev = &ev; r.timed = true;
+    if (int rc = launch(ctx, r)) return rc;
     EventSearchArgs a;
     std::memset(&a, 0, sizeof a);
     a.traj = dtraj.t; a.n = n; a.ev = *event; a.mu = ctx->host_cfg.mu_central;
     a.found = ev.ev_found; a.status = sg.dst.status; a.epoch_ns = sg.dout.epoch_ns;
-    double *st6[6] = {sg.dout.x_km, sg.dout.y_km, sg.dout.z_km, sg.dout.vx_km_s, sg.dout.vy_km_s, sg.dout.vz_km_s};
-    for (int c = 0; c < 6; ++c) a.state[c] = st6[c];
+    for (int c = 0; c < kCartRows; ++c) a.state[c] = sg.dout.*kStateRow[c].s;
     HIP_TRY(nyx_launch_event_search(&a, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    {
-        float ms = 0.f;
-        ctx->last_ms = (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ? ms : -1.0;
-    }
+    read_kernel_ms(ctx);
     if (int rc = fetch_batch(ctx, n, sg.stm, out, stats)) return rc;
     if (int rc = dtraj.download(traj)) return rc;
     if (crossings) HIP_TRY(hipMemcpy(crossings, ev.ev_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1446,9 +1280,7 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     std::memset(&a, 0, sizeof a);
     a.n = n; a.cfg = *cfg;
     a.epoch = sg.dout.epoch_ns;
-    const double *s9[9] = {sg.dout.x_km, sg.dout.y_km, sg.dout.z_km, sg.dout.vx_km_s, sg.dout.vy_km_s, sg.dout.vz_km_s,
-                           sg.dout.cr, sg.dout.cd, sg.dout.prop_mass_kg};
-    for (int k = 0; k < 9; ++k) a.s9[k] = s9[k];
+    for (int k = 0; k < kMomentRows; ++k) a.s9[k] = sg.dout.*kStateRow[k].s;
     a.seg_status = sg.dst.status; a.seg_n_acc = sg.dst.n_accepted; a.seg_n_rej = sg.dst.n_rejected; a.seg_n_evals = sg.dst.n_evals;
     a.covar = covar.as<double>(); a.state_dev = sdev.as<double>();
     int64_t *w64 = work.as<int64_t>();
@@ -1471,12 +1303,12 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     {
         // the segment launches carry a per-trajectory duration array and are too short to calibrate on themselves: measure
         // the column weights of their workgroup shape once per context, on the staged states (identity STM set above)
-        const PlanInputs pin = plan_inputs(ctx);
-        const int nw_c = pick_waves(pin, ctx->host_cfg, n);
-        const bool quad_c = pick_quad(pin, ctx->host_cfg, n);
-        const bool pipe_c = quad_c && nw_c == DEV_MAX_WAVES && ctx->tune.pipelined != 0;
-        const WKey key(nw_c, pipe_c ? 1 : 0, quad_c ? 1 : 0, -1);
-        if (calibration_on(ctx) && ctx->host_cfg.has_grav && nw_c >= 8 && n >= 16 && !ctx->weights.count(key)) {
+        // (the shape of their launches, planned on a copy of the descriptor: each launch plans for itself)
+        const std::unique_ptr<DevCfg> dc(new DevCfg(ctx->host_cfg));
+        SchedShape shape = ctx->shape;
+        const LaunchPlan p = plan_launch(plan_inputs(ctx), *dc, shape, n, true);
+        const WKey key = weight_key(*dc, p.n_waves, p.quad, p.coop.run);
+        if (calibration_on(ctx) && ctx->host_cfg.has_grav && p.n_waves >= 8 && n >= 16 && !ctx->weights.count(key)) {
             if (int rc = calibrate(ctx, &sg.din, stream)) return rc;
             HIP_TRY(hipEventRecord(ctx->ev0, stream));  // (the timed region is the segment loop, not the one-off calibration)
         }
@@ -1487,6 +1319,8 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     // launch cost ~30 us beyond its force evaluations (tools/seg_cost.py), a fifth of BASELINE config 4's loop.  The launch-per-segment
     // loop of rounds 2-5 stays for the integration-frame swap (translated in and out per segment, od/process/mod.rs:453-468) and as
     // the A/B reference (debug_flags 0x20000000): same states, STMs and covariances.
+    LaunchReq seg;  // (per-trajectory durations; segment 0 reads the staged states, the later ones run in place)
+    seg.in = &sg.din; seg.out = &sg.dout; seg.stats = &sg.dst; seg.dur_ns = a.dur; seg.stream = stream;
     DevBuf pa_dev;
     // (quad layout only: sixteen waves share sixteen trajectories' updates; the 64-lane layout - four waves, sixty-four trajectories per
     //  workgroup - is the large-ensemble shape, where the per-launch cost is a small share and sixteen serial updates per wave cost more:
@@ -1496,7 +1330,7 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
         if (int rc = pa_dev.alloc(sizeof(PredictArgs))) return rc;
         HIP_TRY(hipMemcpyAsync(pa_dev.p, &a, sizeof(PredictArgs), hipMemcpyHostToDevice, stream));
         ctx->fused_pred = (const PredictArgs *)pa_dev.p;
-        const int rc = launch(ctx, &sg.din, &sg.dout, &sg.dst, 0, 0, 0, stream, false, nullptr, a.dur);
+        const int rc = launch(ctx, seg);
         ctx->fused_pred = nullptr;
         if (rc) return rc;
         // the kernel's counters run over the whole loop
@@ -1505,16 +1339,13 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
         HIP_TRY(hipMemcpyAsync(a.acc_n_evals, sg.dst.n_evals, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
     } else
     for (int64_t s = 0; s < n_seg; ++s) {
-        const nyx_hip_states_t *src = s == 0 ? &sg.din : &sg.dout;
-        if (int rc = launch(ctx, src, &sg.dout, &sg.dst, 0, 0, 0, stream, false, nullptr, a.dur)) return rc;
+        if (int rc = launch(ctx, seg)) return rc;
         HIP_TRY(nyx_launch_time_update(&a, stream));
+        seg.in = &sg.dout;
     }
     HIP_TRY(hipEventRecord(ctx->ev1, stream));
     HIP_TRY(hipDeviceSynchronize());
-    {
-        float ms = 0.f;
-        ctx->last_ms = (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ? ms : -1.0;
-    }
+    read_kernel_ms(ctx);
     if (int rc = fetch_batch(ctx, n, true, out, stats)) return rc;
     HIP_TRY(hipMemcpy(est->covar, covar.p, (size_t)n * 81 * 8, hipMemcpyDeviceToHost));
     if (est->state_dev) HIP_TRY(hipMemcpy(est->state_dev, sdev.p, (size_t)n * 9 * 8, hipMemcpyDeviceToHost));
@@ -1542,12 +1373,6 @@ extern "C" int32_t nyx_hip_debug_schedule(nyx_hip_ctx *ctx, int32_t n_waves, int
     CTX_LOCK(ctx);
     const std::unique_ptr<DevCfg> dc(new DevCfg(ctx->host_cfg));
     build_schedule(plan_inputs(ctx), *dc, ctx->shape, n_waves);
-    const DevSched &sd = dc->sched[DEV_SCHED_SOLO];
-    for (int w = 0; w < DEV_MAX_WAVES; ++w) {
-        int l = 0;
-        for (int q = 0; q < sd.n_ranges[w]; ++q)
-            for (int c = sd.range_c0[w][q]; c < sd.range_c0[w][q] + sd.range_cnt[w][q]; ++c) l += ctx->col_len[c];
-        loads[w] = l;
-    }
+    for (int w = 0; w < DEV_MAX_WAVES; ++w) loads[w] = rows_of(ctx, dc->sched[DEV_SCHED_SOLO], w);
     return NYX_HIP_RC_OK;
 }

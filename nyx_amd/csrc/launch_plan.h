@@ -770,3 +770,55 @@ inline LaunchPlan plan_launch(const PlanInputs &in, DevCfg &dc, SchedShape &shap
     p.coop = plan_cooperation(in, dc, n, p.n_waves, shape, p.rebuilt);
     return p;
 }
+
+// One fit of calibrate() (abi.cpp): per wave of workgroup 0 of a calibration launch, prof[8 w + 1] = cycles of role work inside the
+// window (duty), prof[8 w + 2] = cycles in its columns (harm); c[w] = harm / table entries is what an entry costs THAT wave (the four
+// waves of a SIMD are arbitrated oldest first).  The water-filling gets the speed weight cbar / c[w] and the handicap duty[w] / c[w]
+// (in entries), which makes duty + columns equal across the waves; damped with `prev`, the previous fit (the shares interact through
+// the shared SIMDs); rounded to 1/64.  Not usable when fewer than two waves carried columns or fewer than two had a window.
+struct CalibrationFit {
+    bool usable = false;
+    std::array<double, 2 * DEV_MAX_WAVES> w{};  // speed weights [0..16), duties [16..32) (WeightMap)
+    double spread = 0.0;                      // (max - min) / mean of the measured windows
+};
+inline CalibrationFit calibration_fit(const int64_t *prof, const DevSched &sd, const std::vector<int32_t> &col_len, int nw,
+                                      const std::array<double, 2 * DEV_MAX_WAVES> *prev) {
+    CalibrationFit f;
+    double duty[DEV_MAX_WAVES], harm[DEV_MAX_WAVES], ent[DEV_MAX_WAVES], cpe[DEV_MAX_WAVES];
+    double csum = 0.0, lo = 1e300, hi = 0.0, tmean = 0.0;
+    int ccnt = 0, tcnt = 0;
+    for (int q = 0; q < nw; ++q) {
+        duty[q] = (double)prof[q * 8 + 1];
+        harm[q] = (double)prof[q * 8 + 2];
+        ent[q] = 0.0;
+        for (int r = 0; r < sd.n_ranges[q]; ++r)
+            for (int c = sd.range_c0[q][r]; c < sd.range_c0[q][r] + sd.range_cnt[q][r]; ++c) ent[q] += col_len[c];
+        cpe[q] = (ent[q] > 0.0 && harm[q] > 0.0) ? harm[q] / ent[q] : 0.0;   // cycles per table entry, as this wave sees them
+        if (cpe[q] > 0.0) { csum += cpe[q]; ++ccnt; }
+        if (q > 0 || nw < 8) {
+            const double t = duty[q] + (ent[q] > 0.0 ? harm[q] : 0.0);
+            if (t > 0.0) { lo = std::min(lo, t); hi = std::max(hi, t); tmean += t; ++tcnt; }
+        }
+    }
+    if (ccnt < 2 || tcnt < 2) return f;
+    const double cbar = csum / ccnt;
+    f.spread = (hi - lo) / (tmean / tcnt);
+    std::array<double, 2 * DEV_MAX_WAVES> nwgt;
+    for (int q = 0; q < DEV_MAX_WAVES; ++q) {
+        // a wave that carried no columns this time is given the speed of its SIMD age class (waves q, q+4, q+8, q+12 share a SIMD)
+        double c = q < nw ? cpe[q] : 0.0;
+        if (!(c > 0.0)) {
+            double a = 0.0; int an = 0;
+            for (int k = (q / 4) * 4; k < (q / 4) * 4 + 4 && k < nw; ++k) if (cpe[k] > 0.0) { a += cpe[k]; ++an; }
+            c = an ? a / an : cbar;
+        }
+        nwgt[q] = cbar / c;
+        nwgt[DEV_MAX_WAVES + q] = q < nw ? duty[q] / c : 0.0;
+    }
+    for (int q = 0; q < 2 * DEV_MAX_WAVES; ++q) {
+        const double v = prev ? 0.5 * ((*prev)[q] + nwgt[q]) : nwgt[q];
+        f.w[q] = std::round(v * 64.0) / 64.0;
+    }
+    f.usable = true;
+    return f;
+}
