@@ -276,6 +276,20 @@ class PredictHistory(C.Structure):
                 ("covar", c_double_p), ("state_dev", c_double_p), ("n_updates", c_int32_p)]
 
 
+# ---- include/nyx_hip_reports.h (fused device reports) ----
+REPORTS_VERSION = 1
+MAX_REPORT_PARAMS = 8
+# enum nyx_hip_state_param: the orbit-derived members of params.StateParameter, by name
+STATE_PARAM = {"X": 0, "Y": 1, "Z": 2, "VX": 3, "VY": 4, "VZ": 5, "Rmag": 6, "Vmag": 7, "Hmag": 8, "Energy": 9, "SemiMajorAxis": 10,
+               "Eccentricity": 11, "Inclination": 12, "RAAN": 13, "AoP": 14, "TrueAnomaly": 15, "Period": 16, "ApoapsisRadius": 17,
+               "PeriapsisRadius": 18}
+
+
+class ValuesQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("has_window", C.c_int32), ("param", C.c_int32 * MAX_REPORT_PARAMS), ("step_ns", C.c_int64),
+                ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("mu_km3_s2", C.c_double)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -427,6 +441,9 @@ EXPORTS = [
     "nyx_hip_propagate_batch_sharded", "nyx_hip_ensemble_moments", "nyx_hip_ensemble_moments_device",
 ]
 
+# the entries of include/nyx_hip_reports.h: a list of their own (EXPORTS mirrors nyx_hip.h, from which the Rust block is generated)
+REPORT_EXPORTS = ["nyx_hip_traj_values", "nyx_hip_traj_values_device", "nyx_hip_reports_sizeof"]
+
 
 def load_library():
     """dlopen the in-tree HIP extension.  No CPU fallback: a missing build is an error."""
@@ -494,6 +511,13 @@ def load_library():
     lib.nyx_hip_ensemble_moments_device.restype = C.c_int32
     lib.nyx_hip_ctx_set_tuning.argtypes = [C.c_void_p, C.POINTER(Tuning)]
     lib.nyx_hip_ctx_set_tuning.restype = C.c_int32
+    lib.nyx_hip_traj_values.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(ValuesQuery), C.c_int64, c_double_p, c_int32_p]
+    lib.nyx_hip_traj_values.restype = C.c_int32
+    lib.nyx_hip_traj_values_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(ValuesQuery), C.c_int64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+    lib.nyx_hip_traj_values_device.restype = C.c_int32
+    lib.nyx_hip_reports_sizeof.argtypes = [C.c_int32]
+    lib.nyx_hip_reports_sizeof.restype = C.c_int32
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib

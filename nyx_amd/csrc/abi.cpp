@@ -27,12 +27,14 @@
 #include "predict_args.h"
 #include "traj_args.h"
 #include "moments_args.h"
+#include "report_args.h"
 
 extern "C" size_t nyx_kernel_lds_bytes(int n_waves, int rec_doubles, int stm, int reuse_fields);
 extern "C" hipError_t nyx_launch_predict_init(const PredictArgs *a, const int64_t *epoch0, hipStream_t stream);
 extern "C" hipError_t nyx_launch_time_update(const PredictArgs *a, hipStream_t stream);
 extern "C" hipError_t nyx_launch_event_search(const EventSearchArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_eval(const TrajEvalArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_traj_values(const ValuesArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1157,6 +1159,60 @@ extern "C" int32_t nyx_hip_traj_every(nyx_hip_ctx *ctx, const nyx_hip_traj_t *tr
     return traj_eval_host(ctx, traj, n, nullptr, 0, step_ns, out, nullptr, TRAJ_MODE_EVERY);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fused reports (include/nyx_hip_reports.h): report_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_reports_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_values_query_t);
+    case 1: return NYX_HIP_REPORTS_VERSION;
+    case 2: return NYX_HIP_SP_COUNT;
+    case 3: return NYX_HIP_MAX_REPORT_PARAMS;
+    default: return -1;
+    }
+}
+
+// everything but the output arrays (the host flavour stages those itself)
+static int check_values_query(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q, int64_t capacity) {
+    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
+    if (int rc = check_traj(traj, "traj", true)) return rc;
+    if (!q) { nyx_set_error("traj_values: null query"); return NYX_HIP_RC_BAD_ARG; }
+    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
+    if (q->n_params < 1 || q->n_params > NYX_HIP_MAX_REPORT_PARAMS) {
+        nyx_set_error("traj_values: n_params = %d, 1 .. %d parameters per call", q->n_params, NYX_HIP_MAX_REPORT_PARAMS);
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    for (int p = 0; p < q->n_params; ++p)
+        if (report_param_needs(q->param[p]) < 0) {
+            nyx_set_error("traj_values: param[%d] = %d is not a nyx_hip_state_param", p, q->param[p]);
+            return NYX_HIP_RC_BAD_ARG;
+        }
+    if (q->step_ns <= 0) { nyx_set_error("traj_values: step_ns must be > 0 (TimeSeries with a positive step)"); return NYX_HIP_RC_BAD_ARG; }
+    if (capacity < 1 || capacity > INT32_MAX) { nyx_set_error("traj_values: capacity must be 1 .. 2^31 - 1"); return NYX_HIP_RC_BAD_ARG; }
+    return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_traj_values_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
+                                              int64_t capacity, double *values, int32_t *len, void *hip_stream) {
+    if (int rc = check_values_query(ctx, traj, n, q, capacity)) return rc;
+    if (!values || !len) { nyx_set_error("traj_values: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    ValuesArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    if (!(a.q.mu_km3_s2 > 0.0)) a.q.mu_km3_s2 = ctx->host_cfg.mu_central;
+    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
+    HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    HIP_TRY(nyx_launch_traj_values(&a, stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
+    ctx->launched = true;
+    return NYX_HIP_RC_OK;
+}
+
 struct DevBuf {  // RAII device allocation
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -1170,6 +1226,30 @@ struct DevBuf {  // RAII device allocation
     }
     template <typename T> T *as() const { return (T *)p; }
 };
+
+extern "C" int32_t nyx_hip_traj_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
+                                       int64_t capacity, double *values, int32_t *len) {
+    if (int rc = check_values_query(ctx, traj, n, q, capacity)) return rc;
+    if (!values || !len) { nyx_set_error("traj_values: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    if (n == 0) return NYX_HIP_RC_OK;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTraj src;
+    if (int rc = src.alloc(traj->capacity, n)) return rc;
+    if (int rc = src.upload(traj)) return rc;
+    // one block: the values, then the lengths; only these come back
+    const size_t vbytes = (size_t)q->n_params * (size_t)capacity * (size_t)n * sizeof(double);
+    DevBuf out;
+    if (int rc = out.alloc(vbytes + (size_t)n * sizeof(int32_t))) return rc;
+    double *d_values = (double *)out.p;
+    int32_t *d_len = (int32_t *)((char *)out.p + vbytes);
+    if (int rc = nyx_hip_traj_values_device(ctx, &src.t, n, q, capacity, d_values, d_len, nullptr)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("report kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Stop conditions (propagators/event.rs:88-211): propagation with the crossing counter, then the root search

@@ -28,7 +28,7 @@ import numpy as np
 from . import _abi
 from .rng import Pcg64Mcg
 from .params import StateError, StateParameter, state_value
-from .propagator import Almanac, Propagator, Spacecraft, Traj
+from .propagator import Almanac, Propagator, Spacecraft, Traj, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
 STATE_DIM = 9
@@ -206,6 +206,35 @@ class Run:
 
 
 @dataclass
+class ValueSeries:
+    """`Results.values_of`: sample k of run j (position in `Results.runs`) of parameter p is `values[p, k, j]`, taken at
+    `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after them NaN.  A failed run (`ok[j]` False) has
+    len 0 and holds the caller's substitute in every slot."""
+
+    params: list
+    values: np.ndarray      # [P, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+
+    def epochs(self, j: int) -> np.ndarray:
+        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+    def flat(self, param, value_if_run_failed: Optional[float] = None) -> List[float]:
+        """One parameter as the list reports lay it out (results.rs:86-160): run after run; a failed run is skipped, or
+        stands for ONE `value_if_run_failed`."""
+        p = self.params.index(param)
+        out: List[float] = []
+        for j in range(self.values.shape[2]):
+            if self.ok[j]:
+                out.extend(self.values[p, :int(self.len[j]), j].tolist())
+            elif value_if_run_failed is not None:
+                out.append(float(value_if_run_failed))
+        return out
+
+
+@dataclass
 class Results:
     """mc/results.rs:60-245.  Runs are sorted by index.  When the runs of this process carry trajectories they share one
     dense-output batch, and the `every_value_of*` reports resample ALL of them with one launch of the trajectory kernel
@@ -319,14 +348,36 @@ class Results:
         if self._traj_batch is None:
             raise ValueError("these results carry no trajectories (with_traj=False)")
 
+    def _every_batch(self, step_ns: int):
+        """`Traj::every(step)` of all the runs of this process with one launch: a TrajBatch of the resampled states."""
+        self._need_traj()
+        tb = self._traj_batch
+        last = np.array([tb.epoch_ns[max(min(int(tb.len[i]), tb.capacity) - 1, 0), i] for i in range(tb.n)])
+        count = int(np.max(np.abs(last - tb.epoch_ns[0]) // abs(int(step_ns)))) + 1 if tb.n else 1
+        return self._traj_ctx.traj_every(tb, int(step_ns), count) if tb.n else None   # (each rank resamples ITS shard on its device)
+
+    def _states_between(self, run, step_ns: int, start_ns: int, end_ns: int) -> np.ndarray:
+        """`Traj::every_between` of one run (traj.rs:153-162): its states [len, 6], one `traj_at` on a one-row batch."""
+        self._need_traj()
+        tb = self._traj_batch
+        i = self._traj_rows[run.index]
+        ep, _ = tb.trajectory(i)
+        lo, hi = max(int(start_ns), int(ep.min())), min(int(end_ns), int(ep.max()))
+        if hi < lo:
+            return np.zeros((0, 6))
+        q = lo + int(step_ns) * np.arange((hi - lo) // int(step_ns) + 1, dtype=np.int64)
+        one = _abi.TrajBatch(1, max(len(ep), 1))
+        one.len[0] = len(ep)
+        one.epoch_ns[: len(ep), 0] = tb.epoch_ns[: len(ep), i]
+        one.state[:, : len(ep), 0] = tb.state[:, : len(ep), i]
+        states, status = self._traj_ctx.traj_at(one, q)
+        bad = np.nonzero(_abi.interp_failed(status[:, 0]))[0]
+        return states[: (bad[0] if len(bad) else len(q)), 0]
+
     def every_value_of(self, param: StateParameter, step_ns: int, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:127-160: `param` of every run from the start to the end of its trajectory every `step_ns`."""
         def prepare():
-            self._need_traj()
-            tb = self._traj_batch
-            last = np.array([tb.epoch_ns[max(min(int(tb.len[i]), tb.capacity) - 1, 0), i] for i in range(tb.n)])
-            count = int(np.max(np.abs(last - tb.epoch_ns[0]) // abs(int(step_ns)))) + 1 if tb.n else 1
-            res = self._traj_ctx.traj_every(tb, int(step_ns), count) if tb.n else None   # (each rank resamples ITS shard on its device)
+            res = self._every_batch(step_ns)
             return lambda run: res.trajectory(self._traj_rows[run.index])[1]
 
         return self._report(param, None, value_if_run_failed, prepare=prepare)
@@ -336,23 +387,90 @@ class Results:
         """results.rs:89-125: as above between max(start, first epoch) and min(end, last epoch) of each run
         (`Traj::every_between`, traj.rs:153-162; the series stops at the first epoch that cannot be interpolated)."""
         def states_of_run(run):
-            self._need_traj()
-            tb = self._traj_batch
-            i = self._traj_rows[run.index]
-            ep, _ = tb.trajectory(i)
-            lo, hi = max(int(start_ns), int(ep.min())), min(int(end_ns), int(ep.max()))
-            if hi < lo:
-                return np.zeros((0, 6))
-            q = lo + int(step_ns) * np.arange((hi - lo) // int(step_ns) + 1, dtype=np.int64)
-            one = _abi.TrajBatch(1, max(len(ep), 1))
-            one.len[0] = len(ep)
-            one.epoch_ns[: len(ep), 0] = tb.epoch_ns[: len(ep), i]
-            one.state[:, : len(ep), 0] = tb.state[:, : len(ep), i]
-            states, status = self._traj_ctx.traj_at(one, q)
-            bad = np.nonzero(_abi.interp_failed(status[:, 0]))[0]
-            return states[: (bad[0] if len(bad) else len(q)), 0]
+            return self._states_between(run, step_ns, start_ns, end_ns)
 
         return self._report(param, states_of_run, value_if_run_failed)
+
+    def values_of(self, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                  value_if_run_failed: Optional[float] = None) -> "ValueSeries":
+        """The array form of the list reports: `params` (a sequence of StateParameter) of every run every `step_ns`, from the
+        start to the end of its trajectory, or between max(start, first epoch) and min(end, last epoch) when a window is given
+        (`every_value_of` / `every_value_of_between`; sample 0 of a run is its `first_values_of`, a window [end, end] its
+        `last_values_of`).  One ValueSeries for all of them, evaluated from ONE resampling.
+
+        Orbit-derived parameters come fused from the device (`traj_values`: resampled, evaluated, only the values copied back);
+        Cr, Cd and the masses are constants of a run and are filled in here; Isp / Thrust raise StateError.  A failed run is a
+        column of `value_if_run_failed` (NaN when None) with len 0.  Sharded ensemble: a collective call, every rank reports
+        the runs it propagated and the columns are gathered in index order.
+        An evaluator without `traj_values` (the injected CPU evaluators of the tests) is served by `traj_every` / `traj_at` +
+        `state_value`: that composition is the definition of the result, the device path is tested against it."""
+        params = list(params)
+        step = int(step_ns)
+        fill = np.nan if value_if_run_failed is None else float(value_if_run_failed)
+        runs = self._local_runs()
+        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
+        cols = [None] * len(runs)                            # values[P, len] of every successful run
+        err = None
+        try:
+            if (start_ns is None) != (end_ns is None):
+                raise ValueError("values_of: a window needs both start_ns and end_ns")
+            for p in params:
+                if p in (StateParameter.Isp, StateParameter.Thrust) or not isinstance(p, StateParameter):
+                    raise StateError(p)
+            self._need_traj()
+            orbit = [k for k, p in enumerate(params) if p.name in _abi.STATE_PARAM]
+            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
+            rows = [self._traj_rows[runs[k].index] for k in ok]
+            tb = self._traj_batch
+            dev = res = None
+            if ok and hasattr(self._traj_ctx, "traj_values"):
+                ask = [params[k] for k in orbit] or [StateParameter.X]   # (the lengths of the series come from the launch too)
+                vals, length = self._traj_ctx.traj_values(tb, ask, step, start_ns, end_ns, mu_km3_s2=self.mu_km3_s2 if self.mu_km3_s2 > 0 else None)
+                dev = lambda row: vals[:len(orbit), :min(int(length[row]), vals.shape[1]), row]
+            elif ok:
+                res = self._every_batch(step) if start_ns is None else None
+            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
+            for k, row in zip(ok, rows):
+                run = runs[k]
+                if dev is not None:
+                    got = dev(row)
+                    n_k = got.shape[1]
+                    rv = None
+                else:
+                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(run, step, start_ns, end_ns)
+                    n_k = len(rv)
+                col = np.empty((len(params), n_k))
+                for j, p in enumerate(params):
+                    if p.name in _abi.STATE_PARAM and dev is not None:
+                        col[j] = got[orbit.index(j)]
+                    else:   # host: the constants of the run (any rv of the right length does), or the whole composition
+                        col[j] = self._value(p, run, rv if rv is not None else np.zeros((n_k, 6)))
+                cols[k] = col
+                head[k, 0], head[k, 2] = n_k, 1.0
+                head[k, 1:2] = np.array([first[row] if n_k else 0], dtype=np.int64).view(np.float64)
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
+            err = e
+        self._sync_errors(err)
+        sharded = self._dist is not None and self._dist.get_world_size() > 1
+        if sharded:
+            world = self._dist.get_world_size()
+            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
+            head_all = all_gather_rows(self._dist, head, bounds)
+        else:
+            head_all = head
+        k_max = int(head_all[:, 0].max()) if len(head_all) else 0
+        local = np.full((len(runs), len(params) * k_max), np.nan)
+        view = local.reshape(len(runs), len(params), k_max)
+        for k, col in enumerate(cols):
+            if col is None:
+                view[k] = fill
+            else:
+                view[k, :, :col.shape[1]] = col
+        if sharded and local.shape[1]:
+            local = all_gather_rows(self._dist, local, bounds)
+        values = np.ascontiguousarray(local.reshape(len(head_all), len(params), k_max).transpose(1, 2, 0))
+        return ValueSeries(params, values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(),
+                           step, head_all[:, 2] > 0)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

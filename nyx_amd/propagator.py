@@ -29,6 +29,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _abi
+from .params import StateError, StateParameter
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -813,6 +814,36 @@ class GpuContext:
             raise RuntimeError(f"nyx_hip_traj_every failed (rc={rc}): {_abi.last_error()}")
         return out
 
+    def traj_values(self, traj: _abi.TrajBatch, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                    capacity: Optional[int] = None, mu_km3_s2: Optional[float] = None):
+        """``nyx_hip_traj_values`` (include/nyx_hip_reports.h): the orbit-derived `params` (StateParameter members) of every
+        trajectory of the batch every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given -
+        resampled and evaluated on the device in one pass: (values[P, capacity, n], len[n]).  `len[i]` counts the samples
+        produced for trajectory i; slots from `len[i]` on are NaN.  `capacity=None` sizes the series from the batch's epochs;
+        `mu_km3_s2=None` is the context's central body.  More than eight parameters take several launches."""
+        params = list(params)
+        codes = [report_param_code(p) for p in params]
+        if (start_ns is None) != (end_ns is None):
+            raise ValueError("traj_values: a window needs both start_ns and end_ns")
+        cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
+        values = np.empty((len(codes), max(cap, 0), traj.n), dtype=np.float64)
+        length = np.zeros(traj.n, dtype=np.int32)
+        cin = traj.as_c()
+        for lo in range(0, len(codes), _abi.MAX_REPORT_PARAMS):
+            chunk = codes[lo:lo + _abi.MAX_REPORT_PARAMS]
+            q = _abi.ValuesQuery()
+            q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
+            q.param[:len(chunk)] = chunk
+            if start_ns is not None:
+                q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+            q.mu_km3_s2 = 0.0 if mu_km3_s2 is None else float(mu_km3_s2)   # (<= 0: the context's central body)
+            part = values[lo:lo + len(chunk)]   # (a contiguous block of the result: written in place)
+            rc = self._lib.nyx_hip_traj_values(self._h, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p),
+                                               length.ctypes.data_as(_abi.c_int32_p))
+            if rc != 0:
+                raise RuntimeError(f"nyx_hip_traj_values failed (rc={rc}): {_abi.last_error()}")
+        return values, length
+
     def propagate_until_epoch(self, batch: _abi.StateBatch, end_epoch_ns: int, out: Optional[_abi.StateBatch] = None):
         out = out if out is not None else batch.copy()
         stats = _abi.StatsBatch(batch.n)
@@ -821,6 +852,36 @@ class GpuContext:
         if rc != 0:
             raise RuntimeError(f"nyx_hip_propagate_until_epoch failed (rc={rc}): {_abi.last_error()}")
         return out, stats
+
+
+def report_param_code(param) -> int:
+    """enum nyx_hip_state_param of an orbit-derived StateParameter; StateError for the others (Cr, Cd, masses, Isp, Thrust:
+    not functions of the orbit)."""
+    code = _abi.STATE_PARAM.get(getattr(param, "name", None))
+    if code is None:
+        raise StateError(param)
+    return code
+
+
+def series_bounds(traj: _abi.TrajBatch, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+    """(lo[n], hi[n]) of the inclusive series of every trajectory of the batch: its smallest / largest stored epoch, clamped
+    to the window (`Traj::every_between`, traj.rs:153-162).  Empty trajectories get hi < lo."""
+    lo, hi = np.ones(traj.n, dtype=np.int64), np.zeros(traj.n, dtype=np.int64)
+    m = np.minimum(traj.len.astype(np.int64), traj.capacity)
+    cols = np.nonzero(m > 0)[0]
+    if len(cols):
+        a, b = traj.epoch_ns[0, cols], traj.epoch_ns[m[cols] - 1, cols]   # (propagation order: forward or backward in time)
+        lo[cols], hi[cols] = np.minimum(a, b), np.maximum(a, b)
+        if start_ns is not None:
+            lo[cols], hi[cols] = np.maximum(lo[cols], int(start_ns)), np.minimum(hi[cols], int(end_ns))
+    return lo, hi
+
+
+def values_capacity(traj: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> int:
+    """The longest series `traj_values` produces for this batch (at least 1: the ABI takes no empty buffer)."""
+    lo, hi = series_bounds(traj, start_ns, end_ns)
+    live = hi >= lo
+    return int(np.max((hi[live] - lo[live]) // int(step_ns))) + 1 if live.any() else 1
 
 
 class PropInstance:
@@ -1019,6 +1080,15 @@ class Traj:
         bad = np.nonzero(_abi.interp_failed(status[:, 0]))[0]
         n = int(bad[0]) if len(bad) else len(q)
         return q[:n], states[:n, 0]
+
+    def values_every(self, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+        """(epochs[K], values[P, K]) of the orbit-derived `params` every `step_ns` (between `start_ns` and `end_ns` when given):
+        `every` / `every_between` and the parameter evaluation fused on the device (GpuContext.traj_values)."""
+        params = list(params)
+        values, length = self._ctx.traj_values(self._single(), params, int(step_ns), start_ns, end_ns)
+        k = int(length[0])
+        lo, _ = series_bounds(self._single(), start_ns, end_ns)
+        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
 
     def filter_by_epoch(self, start_ns: Optional[int] = None, end_ns: Optional[int] = None, end_inclusive: bool = True) -> "Traj":
         """traj.rs:165-173: the stored states whose epoch lies in the range (a Rust RangeBounds: `a..b`, `a..=b`, `..`)."""
