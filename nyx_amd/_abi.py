@@ -290,6 +290,17 @@ class ValuesQuery(C.Structure):
                 ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("mu_km3_s2", C.c_double)]
 
 
+# ---- include/nyx_hip_ric.h (RIC dispersions of an ensemble against a nominal) ----
+RIC_VERSION = 1
+RIC_MOMENTS = 28       # per sample: count, sum d[6], the row-major upper triangle of sum d d^T
+RIC_MAX_WINDOW = 9
+
+
+class RicQuery(C.Structure):
+    _fields_ = [("step_ns", C.c_int64), ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("has_window", C.c_int32), ("frame_of", C.c_int32),
+                ("transport", C.c_int32), ("smooth_window", C.c_int32)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -444,6 +455,9 @@ EXPORTS = [
 # the entries of include/nyx_hip_reports.h: a list of their own (EXPORTS mirrors nyx_hip.h, from which the Rust block is generated)
 REPORT_EXPORTS = ["nyx_hip_traj_values", "nyx_hip_traj_values_device", "nyx_hip_reports_sizeof"]
 
+# the entries of include/nyx_hip_ric.h, likewise a list of their own
+RIC_EXPORTS = ["nyx_hip_traj_ric_diff", "nyx_hip_traj_ric_diff_device", "nyx_hip_ric_sizeof"]
+
 
 def load_library():
     """dlopen the in-tree HIP extension.  No CPU fallback: a missing build is an error."""
@@ -518,6 +532,14 @@ def load_library():
     lib.nyx_hip_traj_values_device.restype = C.c_int32
     lib.nyx_hip_reports_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_reports_sizeof.restype = C.c_int32
+    lib.nyx_hip_traj_ric_diff.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(Traj), C.c_int64, C.POINTER(RicQuery), C.c_int64,
+                                          c_double_p, c_int32_p, c_int64_p, c_double_p]
+    lib.nyx_hip_traj_ric_diff.restype = C.c_int32
+    lib.nyx_hip_traj_ric_diff_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(Traj), C.c_int64, C.POINTER(RicQuery), C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.nyx_hip_traj_ric_diff_device.restype = C.c_int32
+    lib.nyx_hip_ric_sizeof.argtypes = [C.c_int32]
+    lib.nyx_hip_ric_sizeof.restype = C.c_int32
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib

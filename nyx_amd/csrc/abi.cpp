@@ -28,6 +28,7 @@
 #include "traj_args.h"
 #include "moments_args.h"
 #include "report_args.h"
+#include "ric_args.h"
 
 extern "C" size_t nyx_kernel_lds_bytes(int n_waves, int rec_doubles, int stm, int reuse_fields);
 extern "C" hipError_t nyx_launch_predict_init(const PredictArgs *a, const int64_t *epoch0, hipStream_t stream);
@@ -35,6 +36,7 @@ extern "C" hipError_t nyx_launch_time_update(const PredictArgs *a, hipStream_t s
 extern "C" hipError_t nyx_launch_event_search(const EventSearchArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_eval(const TrajEvalArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_values(const ValuesArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_ric_diff(const RicArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1248,6 +1250,98 @@ extern "C" int32_t nyx_hip_traj_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *t
     read_kernel_ms(ctx);
     HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// RIC dispersions (include/nyx_hip_ric.h): ric_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_ric_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_ric_query_t);
+    case 1: return NYX_HIP_RIC_VERSION;
+    case 2: return NYX_HIP_RIC_MOMENTS;
+    case 3: return NYX_HIP_RIC_MAX_WINDOW;
+    default: return -1;
+    }
+}
+
+// everything the two flavours refuse (epoch0_ns and moments are optional)
+static int check_ric_query(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                           const nyx_hip_ric_query_t *q, int64_t capacity, const double *values, const int32_t *len) {
+    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
+    if (int rc = check_traj(traj, "traj", true)) return rc;
+    if (int rc = check_traj(ref, "ref", true)) return rc;
+    if (!q) { nyx_set_error("traj_ric_diff: null query"); return NYX_HIP_RC_BAD_ARG; }
+    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
+    if (n_ref != 1 && n_ref != n) {
+        nyx_set_error("traj_ric_diff: n_ref = %lld, one reference trajectory or one per run (n = %lld)", (long long)n_ref, (long long)n);
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    if (q->step_ns <= 0) { nyx_set_error("traj_ric_diff: step_ns must be > 0 (TimeSeries with a positive step)"); return NYX_HIP_RC_BAD_ARG; }
+    if (capacity < 1 || capacity > INT32_MAX) { nyx_set_error("traj_ric_diff: capacity must be 1 .. 2^31 - 1"); return NYX_HIP_RC_BAD_ARG; }
+    if (q->frame_of != 0 && q->frame_of != 1) { nyx_set_error("traj_ric_diff: frame_of = %d, 0 (run) or 1 (reference)", q->frame_of); return NYX_HIP_RC_BAD_ARG; }
+    if (q->transport != 0 && q->transport != 1) { nyx_set_error("traj_ric_diff: transport = %d, 0 or 1", q->transport); return NYX_HIP_RC_BAD_ARG; }
+    if (q->smooth_window < 0 || q->smooth_window > NYX_HIP_RIC_MAX_WINDOW || (q->smooth_window != 0 && q->smooth_window % 2 == 0)) {
+        nyx_set_error("traj_ric_diff: smooth_window = %d, 0 or an odd window up to %d", q->smooth_window, NYX_HIP_RIC_MAX_WINDOW);
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    if (!values || !len) { nyx_set_error("traj_ric_diff: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_traj_ric_diff_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref,
+                                                int64_t n_ref, const nyx_hip_ric_query_t *q, int64_t capacity, double *values, int32_t *len,
+                                                int64_t *epoch0_ns, double *moments, void *hip_stream) {
+    if (int rc = check_ric_query(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
+    HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    if (n == 0) {   // no run: every sample has count 0
+        if (moments) HIP_TRY(hipMemsetAsync(moments, 0, (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double), stream));
+    } else {
+        RicArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.src = *traj; a.ref = *ref; a.n = n; a.n_ref = n_ref; a.capacity = capacity;
+        a.values = values; a.len = len; a.epoch0 = epoch0_ns; a.moments = moments; a.q = *q;
+        HIP_TRY(nyx_launch_ric_diff(&a, stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
+    ctx->launched = true;
+    return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_traj_ric_diff(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                                         const nyx_hip_ric_query_t *q, int64_t capacity, double *values, int32_t *len, int64_t *epoch0_ns,
+                                         double *moments) {
+    if (int rc = check_ric_query(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return rc;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTraj src, nominal;
+    if (int rc = src.alloc(traj->capacity, n)) return rc;
+    if (int rc = src.upload(traj)) return rc;
+    if (int rc = nominal.alloc(ref->capacity, n_ref)) return rc;
+    if (int rc = nominal.upload(ref)) return rc;
+    // one block: the values, the moments, the first epochs, then the lengths; only these come back
+    const size_t vbytes = 6 * (size_t)capacity * (size_t)n * sizeof(double);
+    const size_t mbytes = moments ? (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double) : 0;
+    const size_t ebytes = epoch0_ns ? (size_t)n * sizeof(int64_t) : 0;
+    DevBuf out;
+    if (int rc = out.alloc(vbytes + mbytes + ebytes + (size_t)n * sizeof(int32_t))) return rc;
+    double *d_values = (double *)out.p;
+    double *d_moments = moments ? (double *)((char *)out.p + vbytes) : nullptr;
+    int64_t *d_epoch0 = epoch0_ns ? (int64_t *)((char *)out.p + vbytes + mbytes) : nullptr;
+    int32_t *d_len = (int32_t *)((char *)out.p + vbytes + mbytes + ebytes);
+    if (int rc = nyx_hip_traj_ric_diff_device(ctx, &src.t, n, &nominal.t, n_ref, q, capacity, d_values, d_len, d_epoch0, d_moments, nullptr)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("RIC kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    if (vbytes) HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
+    if (mbytes) HIP_TRY(hipMemcpy(moments, d_moments, mbytes, hipMemcpyDeviceToHost));
+    if (ebytes) HIP_TRY(hipMemcpy(epoch0_ns, d_epoch0, ebytes, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return NYX_HIP_RC_OK;
 }
 

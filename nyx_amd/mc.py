@@ -21,14 +21,15 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence
 
+import copy
 import os
 
 import numpy as np
 
 from . import _abi
 from .rng import Pcg64Mcg
-from .params import StateError, StateParameter, state_value
-from .propagator import Almanac, Propagator, Spacecraft, Traj, series_bounds
+from .params import FRAME_OF, StateError, StateParameter, ric_difference, smooth_ric, state_value
+from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
 STATE_DIM = 9
@@ -232,6 +233,60 @@ class ValueSeries:
             elif value_if_run_failed is not None:
                 out.append(float(value_if_run_failed))
         return out
+
+
+@dataclass
+class RicSeries:
+    """`Results.ric_dispersions`: component c (dR, dI, dC in km, dvR, dvI, dvC in km/s) of sample k of run j (position in
+    `Results.runs`) is `values[c, k, j]`, taken at `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after
+    them NaN.  A failed run (`ok[j]` False) is a column of NaN with len 0.  `count[k]` runs have sample k; `mean[k]` and the
+    unbiased `cov[k]` are taken over them (NaN where count < 1 / < 2).  They are indexed by SAMPLE: a time series of the
+    ensemble when all `epoch0_ns` agree - every run and the nominal starting at one epoch, the Monte Carlo case."""
+
+    values: np.ndarray      # [6, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+    count: np.ndarray       # [K]
+    mean: np.ndarray        # [K, 6]
+    cov: np.ndarray         # [K, 6, 6]
+    moments: np.ndarray     # [K, 28] what they are made of: count, sum d[6], the row-major upper triangle of sum d d^T
+
+    def epochs(self, j: int) -> np.ndarray:
+        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+
+RIC_TRIU = np.triu_indices(6)
+
+
+def ric_moments(cols, k_max: int) -> np.ndarray:
+    """[k_max, 28]: per sample the count, sum d[6] and the row-major upper triangle of sum d d^T over the columns
+    (d[6, len] each, None skipped) that have that sample - the layout of nyx_hip_traj_ric_diff's `moments`."""
+    mom = np.zeros((k_max, _abi.RIC_MOMENTS))
+    for col in cols:
+        if col is None:
+            continue
+        d = col.T[:k_max]
+        m = len(d)
+        mom[:m, 0] += 1.0
+        mom[:m, 1:7] += d
+        mom[:m, 7:] += (d[:, :, None] * d[:, None, :])[:, RIC_TRIU[0], RIC_TRIU[1]]
+    return mom
+
+
+def ric_mean_cov(mom: np.ndarray):
+    """(count[K], mean[K, 6], cov[K, 6, 6]) of moments[K, 28]: mean = s / n, cov = (S - n m m^T) / (n - 1)."""
+    k_n = len(mom)
+    count = mom[:, 0].copy()
+    sxx = np.zeros((k_n, 6, 6))
+    sxx[:, RIC_TRIU[0], RIC_TRIU[1]] = mom[:, 7:]
+    sxx[:, RIC_TRIU[1], RIC_TRIU[0]] = mom[:, 7:]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(count[:, None] >= 1, mom[:, 1:7] / count[:, None], np.nan)
+        cov = (sxx - count[:, None, None] * mean[:, :, None] * mean[:, None, :]) / (count[:, None, None] - 1.0)
+    cov[count < 2] = np.nan
+    return count, mean, cov
 
 
 @dataclass
@@ -471,6 +526,107 @@ class Results:
         values = np.ascontiguousarray(local.reshape(len(head_all), len(params), k_max).transpose(1, 2, 0))
         return ValueSeries(params, values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(),
                            step, head_all[:, 2] > 0)
+
+    def _ric_of_run(self, row: int, ref, lo: int, hi: int, step: int, frame_of, transport: bool, window: int) -> np.ndarray:
+        """d[6, len] of one run against the nominal by composition: two `traj_at` on the common grid, cut at the first epoch
+        either cannot be interpolated at, `ric_difference`, `smooth_ric`."""
+        if hi < lo:
+            return np.zeros((6, 0))
+        tb = self._traj_batch
+        q = lo + step * np.arange((hi - lo) // step + 1, dtype=np.int64)
+        m = min(int(tb.len[row]), tb.capacity)
+        one = _abi.TrajBatch(1, max(m, 1))
+        one.len[0] = m
+        one.epoch_ns[:m, 0] = tb.epoch_ns[:m, row]
+        one.state[:, :m, 0] = tb.state[:, :m, row]
+        a, sa = self._traj_ctx.traj_at(one, q)
+        b, sb = self._traj_ctx.traj_at(ref, q)
+        bad = np.nonzero(_abi.interp_failed(sa[:, 0]) | _abi.interp_failed(sb[:, 0]))[0]
+        k = int(bad[0]) if len(bad) else len(q)
+        d = ric_difference(a[:k, 0], b[:k, 0], frame_of=frame_of, transport=transport)
+        return (smooth_ric(d, window) if window >= 3 else d).T
+
+    def ric_dispersions(self, nominal, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="reference",
+                        transport: bool = True, smooth_window: int = 5) -> "RicSeries":
+        """The dispersions of the ensemble around `nominal` (a Traj, or a TrajBatch of one trajectory) over time: the difference
+        of every run to it in the radial / in-track / cross-track frame every `step_ns` over the overlap of the two spans
+        (clamped to the window when given), with the count, mean and unbiased covariance of every sample - what
+        `Traj::ric_diff_to_parquet` (traj.rs:407-600) computes for one pair, for all runs at once -> RicSeries.
+        `frame_of="reference"`: the frame of the nominal ("run": of each run, the reference's `self.ric_difference(&other)`);
+        `transport`: the rotation of that frame removed from the velocity differences; `smooth_window`: the reference's in-place
+        median filter (it uses 5; 0 or 1: none).
+
+        With a device evaluator one fused launch (`traj_ric_diff`: both trajectories resampled, differenced, filtered and
+        summed on the device; 6 K doubles per run and 28 K sums copied back).  A failed run is a column of NaN with len 0, left out of
+        the statistics.  Sharded ensemble: a collective call - every rank reports the runs it propagated, the columns are
+        gathered in index order and the 28 K sums added with one all-reduce; every rank passes the same nominal.
+        An evaluator without `traj_ric_diff` (the injected CPU evaluators of the tests) is served by `traj_at` +
+        `ric_difference` + `smooth_ric` + numpy sums: that composition is the definition, the device path is tested against it."""
+        step = int(step_ns)
+        window = int(smooth_window)
+        runs = self._local_runs()
+        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
+        cols = [None] * len(runs)                            # d[6, len] of every successful run
+        mom = None
+        err = None
+        try:
+            if (start_ns is None) != (end_ns is None):
+                raise ValueError("ric_dispersions: a window needs both start_ns and end_ns")
+            if frame_of not in FRAME_OF:
+                raise ValueError(f"ric_dispersions: frame_of must be 'run' / 0 or 'reference' / 1, not {frame_of!r}")
+            if window < 0 or window > _abi.RIC_MAX_WINDOW or (window and window % 2 == 0) or step <= 0:
+                raise ValueError(f"ric_dispersions: a positive step and smooth_window 0 or odd up to {_abi.RIC_MAX_WINDOW}")
+            self._need_traj()
+            ref = nominal._single() if hasattr(nominal, "_single") else nominal
+            if ref.n != 1:
+                raise ValueError("ric_dispersions: one nominal trajectory")
+            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
+            rows = [self._traj_rows[runs[k].index] for k in ok]
+            tb = self._traj_batch
+            if ok and hasattr(self._traj_ctx, "traj_ric_diff"):
+                live = copy.copy(tb)                         # the same arrays; the rows of the failed runs emptied: no series, no share in the sums
+                live.len = np.zeros_like(tb.len)
+                live.len[rows] = tb.len[rows]
+                vals, length, epoch0, mom = self._traj_ctx.traj_ric_diff(live, ref, step, start_ns, end_ns, frame_of=frame_of, transport=transport,
+                                                                         smooth_window=window, moments=True)
+                for k, row in zip(ok, rows):
+                    cols[k] = vals[:, :min(int(length[row]), vals.shape[1]), row]
+                first = epoch0
+            elif ok:
+                first, last = ric_bounds(tb, ref, start_ns, end_ns)
+                for k, row in zip(ok, rows):
+                    cols[k] = self._ric_of_run(row, ref, int(first[row]), int(last[row]), step, frame_of, bool(transport), window)
+            for k, row in zip(ok, rows):
+                n_k = cols[k].shape[1]
+                head[k, 0], head[k, 2] = n_k, 1.0
+                head[k, 1:2] = np.array([first[row] if n_k else 0], dtype=np.int64).view(np.float64)
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
+            err = e
+        self._sync_errors(err)
+        sharded = self._dist is not None and self._dist.get_world_size() > 1
+        if sharded:
+            world = self._dist.get_world_size()
+            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
+            head_all = all_gather_rows(self._dist, head, bounds)
+        else:
+            head_all = head
+        k_max = int(head_all[:, 0].max()) if len(head_all) else 0
+        local = np.full((len(runs), 6 * k_max), np.nan)
+        view = local.reshape(len(runs), 6, k_max)
+        for k, col in enumerate(cols):
+            if col is not None:
+                view[k, :, :col.shape[1]] = col
+        if mom is None:
+            mom = ric_moments(cols, k_max)
+        else:   # (the device sized its sums by the longest LOCAL series)
+            mom = np.concatenate([mom[:k_max], np.zeros((max(k_max - len(mom), 0), _abi.RIC_MOMENTS))])
+        if sharded and k_max:
+            local = all_gather_rows(self._dist, local, bounds)
+            mom = all_reduce_sum(self._dist, mom.ravel()).reshape(k_max, _abi.RIC_MOMENTS)
+        values = np.ascontiguousarray(local.reshape(len(head_all), 6, k_max).transpose(1, 2, 0))
+        count, mean, cov = ric_mean_cov(mom)
+        return RicSeries(values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(), step,
+                         head_all[:, 2] > 0, count, mean, cov, mom)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

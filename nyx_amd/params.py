@@ -127,3 +127,74 @@ def state_value(param: StateParameter, rv: np.ndarray, mu_km3_s2: float, cr=None
         sint = np.sum(np.cross(evec, r) * h, axis=-1) / hmag
         return _wrap360(np.degrees(np.arctan2(sint, cost)))
     raise StateError(param)
+
+
+# ---- RIC differences (Traj::ric_diff_to_parquet, md/trajectory/traj.rs:407-600) ----
+FRAME_OF = {"run": 0, "reference": 1, 0: 0, 1: 1}
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross3(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def ric_difference(rv, rv_ref, frame_of="reference", transport=True) -> np.ndarray:
+    """`rv - rv_ref` ([..., 6], km and km/s; the two broadcast) in the radial / in-track / cross-track frame of `rv`
+    (`frame_of` "run" or 0: the reference's `self.ric_difference(&other)`) or of `rv_ref` ("reference" or 1: dispersions
+    around a nominal): [dR, dI, dC, dvR, dvI, dvC].
+
+    With d = rv - rv_ref (differenced first, component by component) and f the frame state: r^ = f_r / |f_r|, h = f_r x f_v,
+    c^ = h / |h|, i^ = c^ x r^; the position and velocity differences are projected on (r^, i^, c^), and with `transport`
+    the rotation rate of the frame, w = |h| / (|f_r| |f_r|) around c^, is removed from the velocity:
+    dv = (dv_R + w dr_I, dv_I - w dr_R, dv_C) - a run that only lags the nominal on its circular orbit stands still.
+    That term is the exact limit, under two-body motion, of the finite-differenced DCM rate ANISE applies
+    (`Orbit::ric_difference`, `dcm_from_ric_to_inertial`); ANISE is not part of this reference tree, so like the other
+    restatements here it follows the documented definition and is **parity unpinned**.
+
+    Sums of three are taken as ((a0 + a1) + a2), as in `state_value`: this function is the definition the device kernel
+    (csrc/ric_kernel.hip) restates operation for operation and is tested against bit for bit."""
+    rv, rv_ref = np.broadcast_arrays(np.asarray(rv, dtype=np.float64), np.asarray(rv_ref, dtype=np.float64))
+    if frame_of not in FRAME_OF:
+        raise ValueError(f"ric_difference: frame_of must be 'run' / 0 or 'reference' / 1, not {frame_of!r}")
+    d = rv - rv_ref
+    f = rv_ref if FRAME_OF[frame_of] else rv
+    fr, fv = f[..., :3], f[..., 3:]
+    rmag = np.sqrt(_dot3(fr, fr))
+    rhat = fr / rmag[..., None]
+    h = _cross3(fr, fv)
+    hmag = np.sqrt(_dot3(h, h))
+    chat = h / hmag[..., None]
+    ihat = _cross3(chat, rhat)
+    dr, dv = d[..., :3], d[..., 3:]
+    out = np.stack([_dot3(rhat, dr), _dot3(ihat, dr), _dot3(chat, dr), _dot3(rhat, dv), _dot3(ihat, dv), _dot3(chat, dv)], axis=-1)
+    if transport:
+        w = hmag / (rmag * rmag)
+        vr = out[..., 3] + w * out[..., 1]
+        vi = out[..., 4] - w * out[..., 0]
+        out[..., 3], out[..., 4] = vr, vi
+    return out
+
+
+def smooth_ric(d, window: int = 5) -> np.ndarray:
+    """`smooth_state_diff_in_place` (md/trajectory/mod.rs:75-125) on a copy of d[K, 6]: the median filter of the RIC
+    differences.  k ascending and IN PLACE - the window [max(0, k - window / 2), min(K, k + window / 2 + 1)) of sample k holds
+    the already smoothed samples before k -, the new value is element (end - start) / 2 of the sorted window, the six
+    components independently.  Applied only when K > window (the reference smooths with 5 when it has more than 5
+    samples, else with 1: the identity); an even window raises, as the reference asserts."""
+    window = int(window)
+    if window % 2 != 1 or window < 1:
+        raise ValueError("smooth_ric: the window must be odd (median of the window)")
+    out = np.array(d, dtype=np.float64)
+    if out.ndim != 2 or out.shape[1] != 6:
+        raise ValueError("smooth_ric: d must be [K, 6]")
+    k_n, half = len(out), window // 2
+    if k_n <= window:
+        return out
+    for k in range(k_n):
+        start, end = max(0, k - half), min(k_n, k + half + 1)
+        out[k] = np.sort(out[start:end], axis=0)[(end - start) // 2]
+    return out

@@ -29,7 +29,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .params import StateError, StateParameter
+from .params import FRAME_OF, StateError, StateParameter
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -844,6 +844,35 @@ class GpuContext:
                 raise RuntimeError(f"nyx_hip_traj_values failed (rc={rc}): {_abi.last_error()}")
         return values, length
 
+    def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                      capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
+        """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
+        trajectory for all, or one per run) every `step_ns` over the overlap of the two spans (clamped to `start_ns` / `end_ns`
+        when given) - both resampled, differenced (params.ric_difference), median-filtered (params.smooth_ric; `smooth_window`
+        0 or 1: not) on the device in one pass: (values[6, capacity, n], len[n], epoch0_ns[n], moments[capacity, 28] or None).
+        `len[i]` counts the samples produced for run i, slots from there on are NaN; moments[k] = count, sum d, upper triangle of
+        sum d d^T over the runs that have sample k.  `capacity=None` sizes the series from the epochs of the two batches."""
+        if (start_ns is None) != (end_ns is None):
+            raise ValueError("traj_ric_diff: a window needs both start_ns and end_ns")
+        if frame_of not in FRAME_OF:
+            raise ValueError(f"traj_ric_diff: frame_of must be 'run' / 0 or 'reference' / 1, not {frame_of!r}")
+        cap = int(capacity) if capacity is not None else ric_capacity(traj, ref, int(step_ns), start_ns, end_ns)
+        values = np.empty((6, max(cap, 0), traj.n), dtype=np.float64)
+        length = np.zeros(traj.n, dtype=np.int32)
+        epoch0 = np.zeros(traj.n, dtype=np.int64)
+        mom = np.zeros((max(cap, 0), _abi.RIC_MOMENTS)) if moments else None
+        q = _abi.RicQuery()
+        q.step_ns, q.has_window, q.frame_of, q.transport, q.smooth_window = int(step_ns), int(start_ns is not None), FRAME_OF[frame_of], int(bool(transport)), int(smooth_window)
+        if start_ns is not None:
+            q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+        cin, cref = traj.as_c(), ref.as_c()
+        rc = self._lib.nyx_hip_traj_ric_diff(self._h, C.byref(cin), traj.n, C.byref(cref), ref.n, C.byref(q), cap, values.ctypes.data_as(_abi.c_double_p),
+                                             length.ctypes.data_as(_abi.c_int32_p), epoch0.ctypes.data_as(_abi.c_int64_p),
+                                             None if mom is None else mom.ctypes.data_as(_abi.c_double_p))
+        if rc != 0:
+            raise RuntimeError(f"nyx_hip_traj_ric_diff failed (rc={rc}): {_abi.last_error()}")
+        return values, length, epoch0, mom
+
     def propagate_until_epoch(self, batch: _abi.StateBatch, end_epoch_ns: int, out: Optional[_abi.StateBatch] = None):
         out = out if out is not None else batch.copy()
         stats = _abi.StatsBatch(batch.n)
@@ -880,6 +909,23 @@ def series_bounds(traj: _abi.TrajBatch, start_ns: Optional[int] = None, end_ns: 
 def values_capacity(traj: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> int:
     """The longest series `traj_values` produces for this batch (at least 1: the ABI takes no empty buffer)."""
     lo, hi = series_bounds(traj, start_ns, end_ns)
+    live = hi >= lo
+    return int(np.max((hi[live] - lo[live]) // int(step_ns))) + 1 if live.any() else 1
+
+
+def ric_bounds(traj: _abi.TrajBatch, ref: _abi.TrajBatch, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+    """(lo[n], hi[n]) of the RIC series of every trajectory of `traj` against `ref` (one trajectory, or one per run): the
+    overlap of the two spans (traj.rs:484-495), clamped to the window.  hi < lo where either trajectory is empty."""
+    if ref.n not in (1, traj.n):
+        raise ValueError(f"the reference batch holds {ref.n} trajectories: one, or one per run ({traj.n})")
+    lo, hi = series_bounds(traj, start_ns, end_ns)
+    rlo, rhi = series_bounds(ref, start_ns, end_ns)
+    return np.maximum(lo, rlo), np.minimum(hi, rhi)
+
+
+def ric_capacity(traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> int:
+    """The longest series `traj_ric_diff` produces for these batches (at least 1: the ABI takes no empty buffer)."""
+    lo, hi = ric_bounds(traj, ref, start_ns, end_ns)
     live = hi >= lo
     return int(np.max((hi[live] - lo[live]) // int(step_ns))) + 1 if live.any() else 1
 
@@ -1089,6 +1135,17 @@ class Traj:
         k = int(length[0])
         lo, _ = series_bounds(self._single(), start_ns, end_ns)
         return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
+
+    def ric_diff(self, other: "Traj", step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="run",
+                 transport: bool = True, smooth_window: int = 5):
+        """(epochs[K], d[6, K]): this trajectory minus `other` in the RIC frame every `step_ns` over the overlap of the two
+        (`ric_diff_to_parquet`, traj.rs:407-600, without the file: aligned spans, both resampled, `ric_difference`, the median
+        filter), fused on the device (GpuContext.traj_ric_diff).  `frame_of="run"`, the default here, is the reference's
+        `self.ric_difference(&other)`: the frame of THIS trajectory; "reference" is the frame of `other`."""
+        values, length, epoch0, _ = self._ctx.traj_ric_diff(self._single(), other._single(), int(step_ns), start_ns, end_ns, frame_of=frame_of,
+                                                            transport=transport, smooth_window=smooth_window)
+        k = int(length[0])
+        return int(epoch0[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
 
     def filter_by_epoch(self, start_ns: Optional[int] = None, end_ns: Optional[int] = None, end_inclusive: bool = True) -> "Traj":
         """traj.rs:165-173: the stored states whose epoch lies in the range (a Rust RangeBounds: `a..b`, `a..=b`, `..`)."""
