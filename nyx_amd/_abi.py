@@ -301,6 +301,20 @@ class RicQuery(C.Structure):
                 ("transport", C.c_int32), ("smooth_window", C.c_int32)]
 
 
+# ---- include/nyx_hip_groundtrack.h (ground tracks: body-fixed geodetic latitude / longitude / height of an ensemble) ----
+GROUNDTRACK_VERSION = 1
+MAX_GT_PARAMS = 8
+# enum nyx_hip_gt_param: the members of groundtrack.GroundTrackParameter, by name
+GT_PARAM = {"Latitude": 0, "Longitude": 1, "Height": 2, "Rmag": 3, "Declination": 4, "X": 5, "Y": 6, "Z": 7, "VX": 8, "VY": 9, "VZ": 10,
+            "Vmag": 11}
+
+
+class GtQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("param", C.c_int32 * MAX_GT_PARAMS), ("has_window", C.c_int32), ("step_ns", C.c_int64),
+                ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("has_frame", C.c_int32), ("_pad", C.c_int32),
+                ("frame_eq_radius_km", C.c_double), ("frame_flattening", C.c_double), ("frame", Rotation)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -458,6 +472,9 @@ REPORT_EXPORTS = ["nyx_hip_traj_values", "nyx_hip_traj_values_device", "nyx_hip_
 # the entries of include/nyx_hip_ric.h, likewise a list of their own
 RIC_EXPORTS = ["nyx_hip_traj_ric_diff", "nyx_hip_traj_ric_diff_device", "nyx_hip_ric_sizeof"]
 
+# the entries of include/nyx_hip_groundtrack.h, likewise
+GROUNDTRACK_EXPORTS = ["nyx_hip_traj_ground_track", "nyx_hip_traj_ground_track_device", "nyx_hip_groundtrack_sizeof"]
+
 
 def load_library():
     """dlopen the in-tree HIP extension.  No CPU fallback: a missing build is an error."""
@@ -540,10 +557,27 @@ def load_library():
     lib.nyx_hip_traj_ric_diff_device.restype = C.c_int32
     lib.nyx_hip_ric_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_ric_sizeof.restype = C.c_int32
+    if getattr(lib, "nyx_hip_traj_ground_track", None) is not None:   # (absent from a library built before the ground tracks)
+        lib.nyx_hip_traj_ground_track.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(GtQuery), C.c_int64, c_double_p, c_int32_p]
+        lib.nyx_hip_traj_ground_track.restype = C.c_int32
+        lib.nyx_hip_traj_ground_track_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(GtQuery), C.c_int64, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]
+        lib.nyx_hip_traj_ground_track_device.restype = C.c_int32
+        lib.nyx_hip_groundtrack_sizeof.argtypes = [C.c_int32]
+        lib.nyx_hip_groundtrack_sizeof.restype = C.c_int32
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
     return lib
+
+
+def ground_track_entry(lib, name: str = "nyx_hip_traj_ground_track"):
+    """An entry of include/nyx_hip_groundtrack.h, or a clear error when the loaded library predates it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the ground tracks were added - rebuild the HIP extension "
+                           "(python -c 'import __graft_entry__ as g; g.build()')")
+    return fn
 
 
 def last_error() -> str:

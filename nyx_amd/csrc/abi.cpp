@@ -29,6 +29,7 @@
 #include "moments_args.h"
 #include "report_args.h"
 #include "ric_args.h"
+#include "groundtrack_args.h"
 
 extern "C" size_t nyx_kernel_lds_bytes(int n_waves, int rec_doubles, int stm, int reuse_fields);
 extern "C" hipError_t nyx_launch_predict_init(const PredictArgs *a, const int64_t *epoch0, hipStream_t stream);
@@ -37,6 +38,7 @@ extern "C" hipError_t nyx_launch_event_search(const EventSearchArgs *args, hipSt
 extern "C" hipError_t nyx_launch_traj_eval(const TrajEvalArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_values(const ValuesArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_ric_diff(const RicArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1247,6 +1249,103 @@ extern "C" int32_t nyx_hip_traj_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *t
     int32_t *d_len = (int32_t *)((char *)out.p + vbytes);
     if (int rc = nyx_hip_traj_values_device(ctx, &src.t, n, q, capacity, d_values, d_len, nullptr)) return rc;
     if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("report kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ground tracks (include/nyx_hip_groundtrack.h): groundtrack_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_groundtrack_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_gt_query_t);
+    case 1: return NYX_HIP_GROUNDTRACK_VERSION;
+    case 2: return NYX_HIP_GT_COUNT;
+    case 3: return NYX_HIP_MAX_GT_PARAMS;
+    default: return -1;
+    }
+}
+
+// everything but the output arrays (the host flavour stages those itself)
+static int check_gt_query(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q, int64_t capacity) {
+    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
+    if (int rc = check_traj(traj, "traj", true)) return rc;
+    if (!q) { nyx_set_error("traj_ground_track: null query"); return NYX_HIP_RC_BAD_ARG; }
+    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
+    if (q->n_params < 1 || q->n_params > NYX_HIP_MAX_GT_PARAMS) {
+        nyx_set_error("traj_ground_track: n_params = %d, 1 .. %d parameters per call", q->n_params, NYX_HIP_MAX_GT_PARAMS);
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    int32_t need = 0;
+    for (int p = 0; p < q->n_params; ++p) {
+        const int32_t k = gt_param_needs(q->param[p]);
+        if (k < 0) {
+            nyx_set_error("traj_ground_track: param[%d] = %d is not a nyx_hip_gt_param", p, q->param[p]);
+            return NYX_HIP_RC_BAD_ARG;
+        }
+        need |= k;
+    }
+    if (q->step_ns <= 0) { nyx_set_error("traj_ground_track: step_ns must be > 0 (TimeSeries with a positive step)"); return NYX_HIP_RC_BAD_ARG; }
+    if (capacity < 1 || capacity > INT32_MAX) { nyx_set_error("traj_ground_track: capacity must be 1 .. 2^31 - 1"); return NYX_HIP_RC_BAD_ARG; }
+    if (q->frame.kind != NYX_HIP_ROT_IAU) {
+        nyx_set_error("traj_ground_track: frame.kind = %d, the frame must be an IAU-oriented frame (NYX_HIP_ROT_IAU)", q->frame.kind);
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    if (q->frame.n_nut_prec < 0 || q->frame.n_nut_prec > NYX_HIP_MAX_NUT_PREC) {
+        nyx_set_error("traj_ground_track: frame.n_nut_prec = %d, 0 .. %d terms", q->frame.n_nut_prec, NYX_HIP_MAX_NUT_PREC);
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    if ((need & GT_NEED_GEODETIC) && !(q->frame_eq_radius_km > 0.0)) {
+        nyx_set_error("traj_ground_track: Latitude / Height need frame_eq_radius_km > 0");
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    if (!(q->frame_flattening >= 0.0 && q->frame_flattening < 1.0)) {
+        nyx_set_error("traj_ground_track: frame_flattening must be in [0, 1)");
+        return NYX_HIP_RC_BAD_ARG;
+    }
+    return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_traj_ground_track_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q,
+                                                    int64_t capacity, double *values, int32_t *len, void *hip_stream) {
+    if (int rc = check_gt_query(ctx, traj, n, q, capacity)) return rc;
+    if (!values || !len) { nyx_set_error("traj_ground_track: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    GroundTrackArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
+    HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    HIP_TRY(nyx_launch_ground_track(&a, stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
+    ctx->launched = true;
+    return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_traj_ground_track(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q,
+                                             int64_t capacity, double *values, int32_t *len) {
+    if (int rc = check_gt_query(ctx, traj, n, q, capacity)) return rc;
+    if (!values || !len) { nyx_set_error("traj_ground_track: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    if (n == 0) return NYX_HIP_RC_OK;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTraj src;
+    if (int rc = src.alloc(traj->capacity, n)) return rc;
+    if (int rc = src.upload(traj)) return rc;
+    // one block: the values, then the lengths; only these come back
+    const size_t vbytes = (size_t)q->n_params * (size_t)capacity * (size_t)n * sizeof(double);
+    DevBuf out;
+    if (int rc = out.alloc(vbytes + (size_t)n * sizeof(int32_t))) return rc;
+    double *d_values = (double *)out.p;
+    int32_t *d_len = (int32_t *)((char *)out.p + vbytes);
+    if (int rc = nyx_hip_traj_ground_track_device(ctx, &src.t, n, q, capacity, d_values, d_len, nullptr)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("ground-track kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
     read_kernel_ms(ctx);
     HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));

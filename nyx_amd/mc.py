@@ -29,6 +29,7 @@ import numpy as np
 from . import _abi
 from .rng import Pcg64Mcg
 from .params import FRAME_OF, StateError, StateParameter, ric_difference, smooth_ric, state_value
+from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, body_fixed_value, check_frame, to_body_fixed
 from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
@@ -255,6 +256,28 @@ class RicSeries:
 
     def epochs(self, j: int) -> np.ndarray:
         return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+
+@dataclass
+class GroundTrackSeries:
+    """`Results.ground_tracks`: sample k of run j (position in `Results.runs`) of parameter p is `values[p, k, j]`, taken at
+    `epoch0_ns[j] + k * step_ns` in the body-fixed `frame`; `len[j]` samples are valid, the slots after them NaN.  A failed
+    run (`ok[j]` False) is a column of NaN with len 0: an empty series."""
+
+    params: list
+    values: np.ndarray      # [P, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+    frame: object = None
+
+    def epochs(self, j: int) -> np.ndarray:
+        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+    def of(self, param) -> np.ndarray:
+        """values[K, runs] of one parameter."""
+        return self.values[self.params.index(param)]
 
 
 RIC_TRIU = np.triu_indices(6)
@@ -627,6 +650,77 @@ class Results:
         count, mean, cov = ric_mean_cov(mom)
         return RicSeries(values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(), step,
                          head_all[:, 2] > 0, count, mean, cov, mom)
+
+    def ground_tracks(self, frame, step_ns: int, params=GROUND_TRACK_DEFAULT, start_ns: Optional[int] = None,
+                      end_ns: Optional[int] = None) -> "GroundTrackSeries":
+        """The ground tracks of the ensemble: `params` (GroundTrackParameter members; by default the four fields of
+        `Traj::to_groundtrack_parquet`, sc_traj.rs:131-155: geodetic latitude, longitude, height, |r|) of every run every
+        `step_ns` in the body-fixed `frame` (an IAU-oriented frame of the runs' centre), from the start to the end of its
+        trajectory or between max(start, first epoch) and min(end, last epoch) when a window is given -> GroundTrackSeries.
+
+        With a device evaluator one fused launch per eight parameters (`traj_ground_track`: resampled, rotated at each sample's
+        epoch, evaluated; only the values copied back).  A failed run is a column of NaN with len 0.  Sharded ensemble: a
+        collective call, every rank reports the runs it propagated and the columns are gathered in index order.
+        An evaluator without `traj_ground_track` (the injected CPU evaluators of the tests) is served by `traj_every` /
+        `traj_at` + `groundtrack.ground_track_value`: that composition is the definition, the device path is tested against it."""
+        params = list(params)
+        step = int(step_ns)
+        runs = self._local_runs()
+        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
+        cols = [None] * len(runs)                            # values[P, len] of every successful run
+        err = None
+        try:
+            if (start_ns is None) != (end_ns is None):
+                raise ValueError("ground_tracks: a window needs both start_ns and end_ns")
+            if step <= 0:
+                raise ValueError("ground_tracks: a positive step")
+            for p in params:
+                if not isinstance(p, GroundTrackParameter):
+                    raise TypeError(f"{p!r} is not a GroundTrackParameter")
+            if not params:
+                raise ValueError("ground_tracks: at least one parameter")
+            central = getattr(getattr(self._traj_ctx, "compiled", None), "central", None)
+            check_frame(frame, central.naif_id if central is not None else None, params)
+            self._need_traj()
+            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
+            rows = [self._traj_rows[runs[k].index] for k in ok]
+            tb = self._traj_batch
+            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
+            if ok and hasattr(self._traj_ctx, "traj_ground_track"):
+                vals, length = self._traj_ctx.traj_ground_track(tb, frame, params, step, start_ns, end_ns)
+                for k, row in zip(ok, rows):
+                    cols[k] = vals[:, :min(int(length[row]), vals.shape[1]), row]
+            elif ok:
+                res = self._every_batch(step) if start_ns is None else None
+                for k, row in zip(ok, rows):
+                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(runs[k], step, start_ns, end_ns)
+                    yf = to_body_fixed(rv, int(first[row]) + step * np.arange(len(rv), dtype=np.int64), frame)
+                    cols[k] = np.stack([body_fixed_value(p, yf, frame.mean_equatorial_radius_km, frame.flattening) for p in params]).reshape(len(params), len(rv))
+            for k, row in zip(ok, rows):
+                n_k = cols[k].shape[1]
+                head[k, 0], head[k, 2] = n_k, 1.0
+                head[k, 1:2] = np.array([first[row] if n_k else 0], dtype=np.int64).view(np.float64)
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
+            err = e
+        self._sync_errors(err)
+        sharded = self._dist is not None and self._dist.get_world_size() > 1
+        if sharded:
+            world = self._dist.get_world_size()
+            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
+            head_all = all_gather_rows(self._dist, head, bounds)
+        else:
+            head_all = head
+        k_max = int(head_all[:, 0].max()) if len(head_all) else 0
+        local = np.full((len(runs), len(params) * k_max), np.nan)
+        view = local.reshape(len(runs), len(params), k_max)
+        for k, col in enumerate(cols):
+            if col is not None:
+                view[k, :, :col.shape[1]] = col
+        if sharded and local.shape[1]:
+            local = all_gather_rows(self._dist, local, bounds)
+        values = np.ascontiguousarray(local.reshape(len(head_all), len(params), k_max).transpose(1, 2, 0))
+        return GroundTrackSeries(params, values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(),
+                                 step, head_all[:, 2] > 0, frame)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

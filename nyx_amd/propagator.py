@@ -30,6 +30,7 @@ import numpy as np
 
 from . import _abi
 from .params import FRAME_OF, StateError, StateParameter
+from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, check_frame
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -844,6 +845,38 @@ class GpuContext:
                 raise RuntimeError(f"nyx_hip_traj_values failed (rc={rc}): {_abi.last_error()}")
         return values, length
 
+    def traj_ground_track(self, traj: _abi.TrajBatch, frame: "Frame", params, step_ns: int, start_ns: Optional[int] = None,
+                          end_ns: Optional[int] = None, capacity: Optional[int] = None):
+        """``nyx_hip_traj_ground_track`` (include/nyx_hip_groundtrack.h): the `params` (GroundTrackParameter members) of every
+        trajectory of the batch every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given -
+        resampled, expressed in the body-fixed `frame` at each sample's epoch and evaluated on the device in one pass:
+        (values[P, capacity, n], len[n]).  `len[i]` counts the samples produced for trajectory i; slots from `len[i]` on are
+        NaN.  `frame` is an IAU-oriented frame of the context's centre (`frame.rotation is None`: the inertial state itself);
+        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches."""
+        fn = _abi.ground_track_entry(self._lib)
+        params = list(params)
+        codes = [gt_param_code(p) for p in params]
+        check_frame(frame, self.compiled.central.naif_id, params)
+        if (start_ns is None) != (end_ns is None):
+            raise ValueError("traj_ground_track: a window needs both start_ns and end_ns")
+        cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
+        values = np.empty((len(codes), max(cap, 0), traj.n), dtype=np.float64)
+        length = np.zeros(traj.n, dtype=np.int32)
+        cin = traj.as_c()
+        for lo in range(0, len(codes), _abi.MAX_GT_PARAMS):
+            chunk = codes[lo:lo + _abi.MAX_GT_PARAMS]
+            q = _abi.GtQuery()
+            q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
+            q.param[:len(chunk)] = chunk
+            if start_ns is not None:
+                q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+            fill_gt_frame(q, frame)
+            part = values[lo:lo + len(chunk)]   # (a contiguous block of the result: written in place)
+            rc = fn(self._h, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
+            if rc != 0:
+                raise RuntimeError(f"nyx_hip_traj_ground_track failed (rc={rc}): {_abi.last_error()}")
+        return values, length
+
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                       capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
         """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
@@ -890,6 +923,33 @@ def report_param_code(param) -> int:
     if code is None:
         raise StateError(param)
     return code
+
+
+def gt_param_code(param) -> int:
+    """enum nyx_hip_gt_param of a GroundTrackParameter."""
+    if not isinstance(param, GroundTrackParameter):
+        raise TypeError(f"{param!r} is not a GroundTrackParameter")
+    return _abi.GT_PARAM[param.name]
+
+
+def fill_gt_frame(q: "_abi.GtQuery", frame: "Frame") -> None:
+    """The frame fields of a ground-track query from a `Frame`, as `Event.as_c` fills those of an event."""
+    rot = frame.rotation or Rotation()
+    if rot.euler is not None:
+        raise NotImplementedError("ground-track frames are IAU-oriented frames on the device path")
+    q.has_frame = 1 if frame.rotation is not None else 0
+    q.frame_eq_radius_km, q.frame_flattening = float(frame.mean_equatorial_radius_km), float(frame.flattening)
+    for k in range(3):
+        q.frame.ra_deg[k], q.frame.dec_deg[k], q.frame.w_deg[k] = float(rot.ra_deg[k]), float(rot.dec_deg[k]), float(rot.w_deg[k])
+    q.frame.kind = _abi.ROT_IAU
+    q.frame.n_nut_prec = len(rot.nut_prec_angles_deg)
+    if q.frame.n_nut_prec > _abi.MAX_NUT_PREC:
+        raise ValueError(f"at most {_abi.MAX_NUT_PREC} nutation-precession angles")
+    for k in range(q.frame.n_nut_prec):
+        q.frame.nut_prec_angle_deg[k][0], q.frame.nut_prec_angle_deg[k][1] = float(rot.nut_prec_angles_deg[k][0]), float(rot.nut_prec_angles_deg[k][1])
+        q.frame.nut_prec_ra[k] = float(rot.nut_prec_ra[k]) if k < len(rot.nut_prec_ra) else 0.0
+        q.frame.nut_prec_dec[k] = float(rot.nut_prec_dec[k]) if k < len(rot.nut_prec_dec) else 0.0
+        q.frame.nut_prec_w[k] = float(rot.nut_prec_w[k]) if k < len(rot.nut_prec_w) else 0.0
 
 
 def series_bounds(traj: _abi.TrajBatch, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
@@ -1132,6 +1192,16 @@ class Traj:
         `every` / `every_between` and the parameter evaluation fused on the device (GpuContext.traj_values)."""
         params = list(params)
         values, length = self._ctx.traj_values(self._single(), params, int(step_ns), start_ns, end_ns)
+        k = int(length[0])
+        lo, _ = series_bounds(self._single(), start_ns, end_ns)
+        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
+
+    def ground_track(self, frame: "Frame", step_ns: int, params=GROUND_TRACK_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+        """(epochs[K], values[P, K]) of the ground track in the body-fixed `frame` every `step_ns` (between `start_ns` and `end_ns`
+        when given): `to_groundtrack_parquet` (sc_traj.rs:131-155) without the file - by default its four fields, geodetic
+        latitude, longitude, height and |r| -, resampled, rotated at each sample's epoch and evaluated on the device
+        (GpuContext.traj_ground_track)."""
+        values, length = self._ctx.traj_ground_track(self._single(), frame, list(params), int(step_ns), start_ns, end_ns)
         k = int(length[0])
         lo, _ = series_bounds(self._single(), start_ns, end_ns)
         return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
