@@ -30,6 +30,7 @@
 #include "report_args.h"
 #include "ric_args.h"
 #include "groundtrack_args.h"
+#include "series_host.h"
 
 extern "C" size_t nyx_kernel_lds_bytes(int n_waves, int rec_doubles, int stm, int reuse_fields);
 extern "C" hipError_t nyx_launch_predict_init(const PredictArgs *a, const int64_t *epoch0, hipStream_t stream);
@@ -62,6 +63,12 @@ void nyx_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *nyx_hip_last_error(void) { return g_err; }
+
+// A refusal of one of the pure headers (series_host.h): its message becomes the last error, its code the return value.
+static int refused(const Refusal &r) {
+    nyx_set_error("%s", r.msg);
+    return r.rc;
+}
 
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
@@ -1000,41 +1007,28 @@ extern "C" int32_t nyx_hip_propagate_batch_sharded(nyx_hip_ctx *const *ctxs, int
 // ---------------------------------------------------------------------------------------------
 // Traj evaluation (md/trajectory/traj.rs:82-162): traj_kernel.hip
 // ---------------------------------------------------------------------------------------------
-static int check_traj(const nyx_hip_traj_t *t, const char *what, bool need_epochs) {
-    if (!t || t->capacity < 0 || !t->len || !t->x_km || !t->y_km || !t->z_km || !t->vx_km_s || !t->vy_km_s || !t->vz_km_s ||
-        (need_epochs && !t->epoch_ns)) {
-        nyx_set_error("%s: null array or negative capacity", what);
-        return NYX_HIP_RC_BAD_ARG;
-    }
+// One timed launch of a context on `stream`, the caller holding its lock: behind the context's previous launch (ev_done), between
+// ev0 and ev1 (nyx_hip_last_kernel_ms).  `launch` enqueues the work and returns a hipError_t.
+template <typename Launch> static int timed_launch(nyx_hip_ctx *ctx, hipStream_t stream, Launch launch) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
+    HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    HIP_TRY(launch());
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
+    ctx->launched = true;
     return NYX_HIP_RC_OK;
 }
 
 static int traj_eval_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query, int64_t m,
                             int64_t step_ns, nyx_hip_traj_t *out, int32_t *status, int mode, hipStream_t stream) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_traj(traj, "traj", true)) return rc;
-    if (int rc = check_traj(out, "out", true)) return rc;
-    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
-    if (mode == TRAJ_MODE_AT) {
-        if (m < 0 || (m > 0 && (!query || !status))) { nyx_set_error("traj_at: query/status arrays required"); return NYX_HIP_RC_BAD_ARG; }
-        if (out->capacity < m) { nyx_set_error("traj_at: out->capacity < m"); return NYX_HIP_RC_BAD_ARG; }
-    } else if (step_ns <= 0) {
-        nyx_set_error("traj_every: step_ns must be > 0 (TimeSeries with a positive step)");
-        return NYX_HIP_RC_BAD_ARG;
-    }
+    if (Refusal r = check_traj_eval(ctx, traj, n, query, m, step_ns, out, status, mode)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
     CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
     TrajEvalArgs a;
     std::memset(&a, 0, sizeof a);
     a.src = *traj; a.dst = *out; a.n = n; a.query = query; a.m = m; a.step_ns = step_ns; a.status = status; a.mode = mode;
-    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(nyx_launch_traj_eval(&a, stream));
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
-    ctx->launched = true;
-    return NYX_HIP_RC_OK;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_traj_eval(&a, stream); });
 }
 
 extern "C" int32_t nyx_hip_traj_at_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query_epoch_ns,
@@ -1118,8 +1112,8 @@ extern "C" int32_t nyx_hip_ensemble_moments(nyx_hip_ctx *ctx, const nyx_hip_stat
 static int traj_eval_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query, int64_t m,
                           int64_t step_ns, nyx_hip_traj_t *out, int32_t *status, int mode) {
     if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_traj(traj, "traj", true)) return rc;
-    if (int rc = check_traj(out, "out", true)) return rc;
+    if (Refusal r = check_traj(traj, "traj", true)) return refused(r);
+    if (Refusal r = check_traj(out, "out", true)) return refused(r);
     if (n <= 0) return n == 0 ? NYX_HIP_RC_OK : NYX_HIP_RC_BAD_ARG;
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1176,47 +1170,6 @@ extern "C" int32_t nyx_hip_reports_sizeof(int32_t which) {
     }
 }
 
-// everything but the output arrays (the host flavour stages those itself)
-static int check_values_query(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q, int64_t capacity) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_traj(traj, "traj", true)) return rc;
-    if (!q) { nyx_set_error("traj_values: null query"); return NYX_HIP_RC_BAD_ARG; }
-    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
-    if (q->n_params < 1 || q->n_params > NYX_HIP_MAX_REPORT_PARAMS) {
-        nyx_set_error("traj_values: n_params = %d, 1 .. %d parameters per call", q->n_params, NYX_HIP_MAX_REPORT_PARAMS);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    for (int p = 0; p < q->n_params; ++p)
-        if (report_param_needs(q->param[p]) < 0) {
-            nyx_set_error("traj_values: param[%d] = %d is not a nyx_hip_state_param", p, q->param[p]);
-            return NYX_HIP_RC_BAD_ARG;
-        }
-    if (q->step_ns <= 0) { nyx_set_error("traj_values: step_ns must be > 0 (TimeSeries with a positive step)"); return NYX_HIP_RC_BAD_ARG; }
-    if (capacity < 1 || capacity > INT32_MAX) { nyx_set_error("traj_values: capacity must be 1 .. 2^31 - 1"); return NYX_HIP_RC_BAD_ARG; }
-    return NYX_HIP_RC_OK;
-}
-
-extern "C" int32_t nyx_hip_traj_values_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
-                                              int64_t capacity, double *values, int32_t *len, void *hip_stream) {
-    if (int rc = check_values_query(ctx, traj, n, q, capacity)) return rc;
-    if (!values || !len) { nyx_set_error("traj_values: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
-    if (n == 0) return NYX_HIP_RC_OK;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    ValuesArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
-    if (!(a.q.mu_km3_s2 > 0.0)) a.q.mu_km3_s2 = ctx->host_cfg.mu_central;
-    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(nyx_launch_traj_values(&a, stream));
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
-    ctx->launched = true;
-    return NYX_HIP_RC_OK;
-}
-
 struct DevBuf {  // RAII device allocation
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -1231,28 +1184,59 @@ struct DevBuf {  // RAII device allocation
     template <typename T> T *as() const { return (T *)p; }
 };
 
-extern "C" int32_t nyx_hip_traj_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
-                                       int64_t capacity, double *values, int32_t *len) {
-    if (int rc = check_values_query(ctx, traj, n, q, capacity)) return rc;
-    if (!values || !len) { nyx_set_error("traj_values: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
-    if (n == 0) return NYX_HIP_RC_OK;
+// The host flavour of a report: the trajectories (`ref`: RIC's, or null) staged on the device, the outputs one block laid out by
+// series_block, `entry(src, ref, outputs)` - the device flavour on those - awaited and timed, every non-empty part copied back.
+// `host.epoch0` / `host.moments` may be null: not asked for.  `what` names the kernel in the message of a failed launch.
+struct SeriesOut { double *values; int32_t *len; int64_t *epoch0; double *moments; };
+template <typename Entry>
+static int series_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref, int64_t n_params,
+                       int64_t capacity, const SeriesOut &host, const char *what, Entry entry) {
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    DevTraj src;
+    DevTraj src, nominal;
     if (int rc = src.alloc(traj->capacity, n)) return rc;
     if (int rc = src.upload(traj)) return rc;
-    // one block: the values, then the lengths; only these come back
-    const size_t vbytes = (size_t)q->n_params * (size_t)capacity * (size_t)n * sizeof(double);
+    if (ref) {
+        if (int rc = nominal.alloc(ref->capacity, n_ref)) return rc;
+        if (int rc = nominal.upload(ref)) return rc;
+    }
+    const SeriesBlock b = series_block(n_params, capacity, n, host.moments != nullptr, host.epoch0 != nullptr);
     DevBuf out;
-    if (int rc = out.alloc(vbytes + (size_t)n * sizeof(int32_t))) return rc;
-    double *d_values = (double *)out.p;
-    int32_t *d_len = (int32_t *)((char *)out.p + vbytes);
-    if (int rc = nyx_hip_traj_values_device(ctx, &src.t, n, q, capacity, d_values, d_len, nullptr)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("report kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    if (int rc = out.alloc(b.total)) return rc;
+    char *base = out.as<char>();
+    const SeriesOut dev = {(double *)(base + b.values_at), (int32_t *)(base + b.len_at), host.epoch0 ? (int64_t *)(base + b.epoch0_at) : nullptr,
+                           host.moments ? (double *)(base + b.moments_at) : nullptr};
+    if (int rc = entry(&src.t, ref ? &nominal.t : nullptr, dev)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("%s kernel failed", what); return NYX_HIP_RC_HIP_ERROR; }
     read_kernel_ms(ctx);
-    HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (b.values) HIP_TRY(hipMemcpy(host.values, dev.values, b.values, hipMemcpyDeviceToHost));
+    if (b.moments) HIP_TRY(hipMemcpy(host.moments, dev.moments, b.moments, hipMemcpyDeviceToHost));
+    if (b.epoch0) HIP_TRY(hipMemcpy(host.epoch0, dev.epoch0, b.epoch0, hipMemcpyDeviceToHost));
+    if (b.len) HIP_TRY(hipMemcpy(host.len, dev.len, b.len, hipMemcpyDeviceToHost));
     return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_traj_values_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
+                                              int64_t capacity, double *values, int32_t *len, void *hip_stream) {
+    if (Refusal r = check_values_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    ValuesArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    if (!(a.q.mu_km3_s2 > 0.0)) a.q.mu_km3_s2 = ctx->host_cfg.mu_central;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_traj_values(&a, stream); });
+}
+
+extern "C" int32_t nyx_hip_traj_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
+                                       int64_t capacity, double *values, int32_t *len) {
+    if (Refusal r = check_values_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "report",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
+                           return nyx_hip_traj_values_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
+                       });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1268,88 +1252,26 @@ extern "C" int32_t nyx_hip_groundtrack_sizeof(int32_t which) {
     }
 }
 
-// everything but the output arrays (the host flavour stages those itself)
-static int check_gt_query(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q, int64_t capacity) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_traj(traj, "traj", true)) return rc;
-    if (!q) { nyx_set_error("traj_ground_track: null query"); return NYX_HIP_RC_BAD_ARG; }
-    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
-    if (q->n_params < 1 || q->n_params > NYX_HIP_MAX_GT_PARAMS) {
-        nyx_set_error("traj_ground_track: n_params = %d, 1 .. %d parameters per call", q->n_params, NYX_HIP_MAX_GT_PARAMS);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    int32_t need = 0;
-    for (int p = 0; p < q->n_params; ++p) {
-        const int32_t k = gt_param_needs(q->param[p]);
-        if (k < 0) {
-            nyx_set_error("traj_ground_track: param[%d] = %d is not a nyx_hip_gt_param", p, q->param[p]);
-            return NYX_HIP_RC_BAD_ARG;
-        }
-        need |= k;
-    }
-    if (q->step_ns <= 0) { nyx_set_error("traj_ground_track: step_ns must be > 0 (TimeSeries with a positive step)"); return NYX_HIP_RC_BAD_ARG; }
-    if (capacity < 1 || capacity > INT32_MAX) { nyx_set_error("traj_ground_track: capacity must be 1 .. 2^31 - 1"); return NYX_HIP_RC_BAD_ARG; }
-    if (q->frame.kind != NYX_HIP_ROT_IAU) {
-        nyx_set_error("traj_ground_track: frame.kind = %d, the frame must be an IAU-oriented frame (NYX_HIP_ROT_IAU)", q->frame.kind);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if (q->frame.n_nut_prec < 0 || q->frame.n_nut_prec > NYX_HIP_MAX_NUT_PREC) {
-        nyx_set_error("traj_ground_track: frame.n_nut_prec = %d, 0 .. %d terms", q->frame.n_nut_prec, NYX_HIP_MAX_NUT_PREC);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if ((need & GT_NEED_GEODETIC) && !(q->frame_eq_radius_km > 0.0)) {
-        nyx_set_error("traj_ground_track: Latitude / Height need frame_eq_radius_km > 0");
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if (!(q->frame_flattening >= 0.0 && q->frame_flattening < 1.0)) {
-        nyx_set_error("traj_ground_track: frame_flattening must be in [0, 1)");
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    return NYX_HIP_RC_OK;
-}
-
 extern "C" int32_t nyx_hip_traj_ground_track_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q,
                                                     int64_t capacity, double *values, int32_t *len, void *hip_stream) {
-    if (int rc = check_gt_query(ctx, traj, n, q, capacity)) return rc;
-    if (!values || !len) { nyx_set_error("traj_ground_track: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    if (Refusal r = check_gt_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
     GroundTrackArgs a;
     std::memset(&a, 0, sizeof a);
     a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
-    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(nyx_launch_ground_track(&a, stream));
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
-    ctx->launched = true;
-    return NYX_HIP_RC_OK;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_ground_track(&a, stream); });
 }
 
 extern "C" int32_t nyx_hip_traj_ground_track(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q,
                                              int64_t capacity, double *values, int32_t *len) {
-    if (int rc = check_gt_query(ctx, traj, n, q, capacity)) return rc;
-    if (!values || !len) { nyx_set_error("traj_ground_track: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
+    if (Refusal r = check_gt_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevTraj src;
-    if (int rc = src.alloc(traj->capacity, n)) return rc;
-    if (int rc = src.upload(traj)) return rc;
-    // one block: the values, then the lengths; only these come back
-    const size_t vbytes = (size_t)q->n_params * (size_t)capacity * (size_t)n * sizeof(double);
-    DevBuf out;
-    if (int rc = out.alloc(vbytes + (size_t)n * sizeof(int32_t))) return rc;
-    double *d_values = (double *)out.p;
-    int32_t *d_len = (int32_t *)((char *)out.p + vbytes);
-    if (int rc = nyx_hip_traj_ground_track_device(ctx, &src.t, n, q, capacity, d_values, d_len, nullptr)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("ground-track kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "ground-track",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
+                           return nyx_hip_traj_ground_track_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
+                       });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1365,83 +1287,32 @@ extern "C" int32_t nyx_hip_ric_sizeof(int32_t which) {
     }
 }
 
-// everything the two flavours refuse (epoch0_ns and moments are optional)
-static int check_ric_query(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
-                           const nyx_hip_ric_query_t *q, int64_t capacity, const double *values, const int32_t *len) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_traj(traj, "traj", true)) return rc;
-    if (int rc = check_traj(ref, "ref", true)) return rc;
-    if (!q) { nyx_set_error("traj_ric_diff: null query"); return NYX_HIP_RC_BAD_ARG; }
-    if (n < 0) { nyx_set_error("negative n"); return NYX_HIP_RC_BAD_ARG; }
-    if (n_ref != 1 && n_ref != n) {
-        nyx_set_error("traj_ric_diff: n_ref = %lld, one reference trajectory or one per run (n = %lld)", (long long)n_ref, (long long)n);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if (q->step_ns <= 0) { nyx_set_error("traj_ric_diff: step_ns must be > 0 (TimeSeries with a positive step)"); return NYX_HIP_RC_BAD_ARG; }
-    if (capacity < 1 || capacity > INT32_MAX) { nyx_set_error("traj_ric_diff: capacity must be 1 .. 2^31 - 1"); return NYX_HIP_RC_BAD_ARG; }
-    if (q->frame_of != 0 && q->frame_of != 1) { nyx_set_error("traj_ric_diff: frame_of = %d, 0 (run) or 1 (reference)", q->frame_of); return NYX_HIP_RC_BAD_ARG; }
-    if (q->transport != 0 && q->transport != 1) { nyx_set_error("traj_ric_diff: transport = %d, 0 or 1", q->transport); return NYX_HIP_RC_BAD_ARG; }
-    if (q->smooth_window < 0 || q->smooth_window > NYX_HIP_RIC_MAX_WINDOW || (q->smooth_window != 0 && q->smooth_window % 2 == 0)) {
-        nyx_set_error("traj_ric_diff: smooth_window = %d, 0 or an odd window up to %d", q->smooth_window, NYX_HIP_RIC_MAX_WINDOW);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if (!values || !len) { nyx_set_error("traj_ric_diff: values and len arrays required"); return NYX_HIP_RC_BAD_ARG; }
-    return NYX_HIP_RC_OK;
-}
-
+// (n == 0 is launched, unlike the two reports above: the moments of no run are zeros)
 extern "C" int32_t nyx_hip_traj_ric_diff_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref,
                                                 int64_t n_ref, const nyx_hip_ric_query_t *q, int64_t capacity, double *values, int32_t *len,
                                                 int64_t *epoch0_ns, double *moments, void *hip_stream) {
-    if (int rc = check_ric_query(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return rc;
+    if (Refusal r = check_ric_series(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return refused(r);
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    if (n == 0) {   // no run: every sample has count 0
-        if (moments) HIP_TRY(hipMemsetAsync(moments, 0, (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double), stream));
-    } else {
-        RicArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.src = *traj; a.ref = *ref; a.n = n; a.n_ref = n_ref; a.capacity = capacity;
-        a.values = values; a.len = len; a.epoch0 = epoch0_ns; a.moments = moments; a.q = *q;
-        HIP_TRY(nyx_launch_ric_diff(&a, stream));
-    }
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
-    ctx->launched = true;
-    return NYX_HIP_RC_OK;
+    RicArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.ref = *ref; a.n = n; a.n_ref = n_ref; a.capacity = capacity;
+    a.values = values; a.len = len; a.epoch0 = epoch0_ns; a.moments = moments; a.q = *q;
+    return timed_launch(ctx, stream, [&] {
+        if (n > 0) return nyx_launch_ric_diff(&a, stream);
+        // no run: every sample has count 0
+        return moments ? hipMemsetAsync(moments, 0, (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double), stream) : hipSuccess;
+    });
 }
 
 extern "C" int32_t nyx_hip_traj_ric_diff(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
                                          const nyx_hip_ric_query_t *q, int64_t capacity, double *values, int32_t *len, int64_t *epoch0_ns,
                                          double *moments) {
-    if (int rc = check_ric_query(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return rc;
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevTraj src, nominal;
-    if (int rc = src.alloc(traj->capacity, n)) return rc;
-    if (int rc = src.upload(traj)) return rc;
-    if (int rc = nominal.alloc(ref->capacity, n_ref)) return rc;
-    if (int rc = nominal.upload(ref)) return rc;
-    // one block: the values, the moments, the first epochs, then the lengths; only these come back
-    const size_t vbytes = 6 * (size_t)capacity * (size_t)n * sizeof(double);
-    const size_t mbytes = moments ? (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double) : 0;
-    const size_t ebytes = epoch0_ns ? (size_t)n * sizeof(int64_t) : 0;
-    DevBuf out;
-    if (int rc = out.alloc(vbytes + mbytes + ebytes + (size_t)n * sizeof(int32_t))) return rc;
-    double *d_values = (double *)out.p;
-    double *d_moments = moments ? (double *)((char *)out.p + vbytes) : nullptr;
-    int64_t *d_epoch0 = epoch0_ns ? (int64_t *)((char *)out.p + vbytes + mbytes) : nullptr;
-    int32_t *d_len = (int32_t *)((char *)out.p + vbytes + mbytes + ebytes);
-    if (int rc = nyx_hip_traj_ric_diff_device(ctx, &src.t, n, &nominal.t, n_ref, q, capacity, d_values, d_len, d_epoch0, d_moments, nullptr)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("RIC kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    if (vbytes) HIP_TRY(hipMemcpy(values, d_values, vbytes, hipMemcpyDeviceToHost));
-    if (mbytes) HIP_TRY(hipMemcpy(moments, d_moments, mbytes, hipMemcpyDeviceToHost));
-    if (ebytes) HIP_TRY(hipMemcpy(epoch0_ns, d_epoch0, ebytes, hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(hipMemcpy(len, d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    if (Refusal r = check_ric_series(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return refused(r);
+    return series_host(ctx, traj, n, ref, n_ref, 6, capacity, {values, len, epoch0_ns, moments}, "RIC",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *nominal, const SeriesOut &d) {
+                           return nyx_hip_traj_ric_diff_device(ctx, src, n, nominal, n_ref, q, capacity, d.values, d.len, d.epoch0, d.moments, nullptr);
+                       });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1465,7 +1336,7 @@ extern "C" int32_t nyx_hip_propagate_until_event(nyx_hip_ctx *ctx, const nyx_hip
         nyx_set_error("until_event: bad event (scalar, trigger >= 1, precisions >= 0)");
         return NYX_HIP_RC_BAD_ARG;
     }
-    if (int rc = check_traj(traj, "traj", true)) return rc;
+    if (Refusal r = check_traj(traj, "traj", true)) return refused(r);
     if (traj->capacity < 2) { nyx_set_error("until_event: traj->capacity >= 2 required (the search needs the bracket)"); return NYX_HIP_RC_BAD_ARG; }
     if (int rc = check_states(in, "in")) return rc;
     if (int rc = check_states(out, "out")) return rc;

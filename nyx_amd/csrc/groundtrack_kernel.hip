@@ -24,6 +24,7 @@
 #include "../../include/nyx_hip_groundtrack.h"
 #include "event_dev.h"
 #include "groundtrack_args.h"
+#include "series_host.h"   // series_chunks
 #include "traj_dev.h"
 
 namespace {
@@ -145,11 +146,9 @@ extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipSt
     for (int p = 0; p < a.q.n_params; ++p) a.need |= gt_param_needs(a.q.param[p]);
     const dim3 per_traj((unsigned)((a.n + 255) / 256));
     hipLaunchKernelGGL(nyxgt_init_kernel, per_traj, dim3(256), 0, stream, a);
-    // grid.y <= 32768 chunks of consecutive samples
-    int64_t spb = 16;
-    if ((a.capacity + spb - 1) / spb > 32768) spb = (a.capacity + 32767) / 32768;
-    a.samples_per_block = spb;
-    const dim3 grid((unsigned)((a.n + LANES - 1) / LANES), (unsigned)((a.capacity + spb - 1) / spb));
+    const SeriesChunks chunks = series_chunks(a.capacity);
+    a.samples_per_block = chunks.samples_per_block;
+    const dim3 grid((unsigned)((a.n + LANES - 1) / LANES), chunks.grid_y);
     hipLaunchKernelGGL(nyxgt_values_kernel, grid, dim3(LANES), 0, stream, a);
     hipLaunchKernelGGL(nyxgt_seal_kernel, per_traj, dim3(256), 0, stream, a);
     return hipGetLastError();

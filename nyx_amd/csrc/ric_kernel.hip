@@ -33,6 +33,7 @@
 
 #include "../../include/nyx_hip_ric.h"
 #include "ric_args.h"
+#include "series_host.h"   // series_chunks
 #include "traj_dev.h"
 
 namespace {
@@ -273,11 +274,9 @@ extern "C" hipError_t nyx_launch_ric_diff(const RicArgs *args, hipStream_t strea
     const dim3 per_run((unsigned)((a.n + 255) / 256));
     const dim3 per_wave((unsigned)((a.n + LANES - 1) / LANES));
     hipLaunchKernelGGL(nyxric_init_kernel, per_run, dim3(256), 0, stream, a);
-    // grid.y <= 32768 chunks of consecutive samples
-    int64_t spb = 16;
-    if ((a.capacity + spb - 1) / spb > 32768) spb = (a.capacity + 32767) / 32768;
-    a.samples_per_block = spb;
-    const dim3 grid(per_wave.x, (unsigned)((a.capacity + spb - 1) / spb));
+    const SeriesChunks chunks = series_chunks(a.capacity);
+    a.samples_per_block = chunks.samples_per_block;
+    const dim3 grid(per_wave.x, chunks.grid_y);
     hipLaunchKernelGGL(nyxric_diff_kernel, grid, dim3(LANES), 0, stream, a);
     hipLaunchKernelGGL(nyxric_seal_kernel, per_run, dim3(256), 0, stream, a);
     if (a.q.smooth_window >= 3) hipLaunchKernelGGL(nyxric_smooth_kernel, per_wave, dim3(LANES), 0, stream, a);

@@ -1,0 +1,154 @@
+// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the four series kernels,
+// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the three fused reports (values, ground track, RIC) refuse, the
+// one output block of a report's host flavour, and the chunks of consecutive samples a launch cuts a span into.
+#pragma once
+#include <climits>
+#include <cstdarg>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+#include "groundtrack_args.h"
+#include "report_args.h"
+#include "ric_args.h"
+#include "traj_args.h"
+
+// A refusal as data: the return code and the message the caller hands to nyx_set_error.  rc == NYX_HIP_RC_OK: accepted.
+struct Refusal {
+    int rc = NYX_HIP_RC_OK;
+    char msg[256] = "";
+    explicit operator bool() const { return rc != NYX_HIP_RC_OK; }
+};
+__attribute__((format(printf, 1, 2))) inline Refusal bad_arg(const char *fmt, ...) {
+    Refusal r;
+    r.rc = NYX_HIP_RC_BAD_ARG;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(r.msg, sizeof r.msg, fmt, ap);
+    va_end(ap);
+    return r;
+}
+
+inline Refusal check_traj(const nyx_hip_traj_t *t, const char *what, bool need_epochs) {
+    if (!t || t->capacity < 0 || !t->len || !t->x_km || !t->y_km || !t->z_km || !t->vx_km_s || !t->vy_km_s || !t->vz_km_s ||
+        (need_epochs && !t->epoch_ns))
+        return bad_arg("%s: null array or negative capacity", what);
+    return {};
+}
+
+// traj_at / traj_every on device arrays (mode = TRAJ_MODE_*)
+inline Refusal check_traj_eval(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query, int64_t m,
+                               int64_t step_ns, const nyx_hip_traj_t *out, const int32_t *status, int mode) {
+    if (!ctx) return bad_arg("null ctx");
+    if (Refusal r = check_traj(traj, "traj", true)) return r;
+    if (Refusal r = check_traj(out, "out", true)) return r;
+    if (n < 0) return bad_arg("negative n");
+    if (mode == TRAJ_MODE_AT) {
+        if (m < 0 || (m > 0 && (!query || !status))) return bad_arg("traj_at: query/status arrays required");
+        if (out->capacity < m) return bad_arg("traj_at: out->capacity < m");
+    } else if (step_ns <= 0) {
+        return bad_arg("traj_every: step_ns must be > 0 (TimeSeries with a positive step)");
+    }
+    return {};
+}
+
+// ---- what every series query (`name`: the entry, as the messages call it) is checked for, in the order the checks fire: the
+// opening (RIC: with its reference), the entry's own first checks, the step and the capacity, its own later checks, the outputs
+inline Refusal series_open(const char *name, const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, bool with_ref, const nyx_hip_traj_t *ref,
+                           const void *q, int64_t n) {
+    if (!ctx) return bad_arg("null ctx");
+    if (Refusal r = check_traj(traj, "traj", true)) return r;
+    if (with_ref)
+        if (Refusal r = check_traj(ref, "ref", true)) return r;
+    if (!q) return bad_arg("%s: null query", name);
+    if (n < 0) return bad_arg("negative n");
+    return {};
+}
+inline Refusal series_span(const char *name, int64_t step_ns, int64_t capacity) {
+    if (step_ns <= 0) return bad_arg("%s: step_ns must be > 0 (TimeSeries with a positive step)", name);
+    if (capacity < 1 || capacity > INT32_MAX) return bad_arg("%s: capacity must be 1 .. 2^31 - 1", name);
+    return {};
+}
+inline Refusal series_outputs(const char *name, const double *values, const int32_t *len) {
+    if (!values || !len) return bad_arg("%s: values and len arrays required", name);
+    return {};
+}
+// 1 .. `most` parameters of the enum `type_name`; `needs` is report_param_needs / gt_param_needs, *need the union of what they ask for
+template <typename Query, typename Needs>
+inline Refusal series_params(const char *name, const Query &q, int most, Needs needs, const char *type_name, int32_t *need) {
+    if (q.n_params < 1 || q.n_params > most) return bad_arg("%s: n_params = %d, 1 .. %d parameters per call", name, q.n_params, most);
+    for (int p = 0; p < q.n_params; ++p) {
+        const int32_t k = needs(q.param[p]);
+        if (k < 0) return bad_arg("%s: param[%d] = %d is not a %s", name, p, q.param[p], type_name);
+        *need |= k;
+    }
+    return {};
+}
+
+inline Refusal check_values_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
+                                   int64_t capacity, const double *values, const int32_t *len) {
+    const char *name = "traj_values";
+    int32_t need = 0;
+    if (Refusal r = series_open(name, ctx, traj, false, nullptr, q, n)) return r;
+    if (Refusal r = series_params(name, *q, NYX_HIP_MAX_REPORT_PARAMS, report_param_needs, "nyx_hip_state_param", &need)) return r;
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    return series_outputs(name, values, len);
+}
+
+inline Refusal check_gt_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_gt_query_t *q,
+                               int64_t capacity, const double *values, const int32_t *len) {
+    const char *name = "traj_ground_track";
+    int32_t need = 0;
+    if (Refusal r = series_open(name, ctx, traj, false, nullptr, q, n)) return r;
+    if (Refusal r = series_params(name, *q, NYX_HIP_MAX_GT_PARAMS, gt_param_needs, "nyx_hip_gt_param", &need)) return r;
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    if (q->frame.kind != NYX_HIP_ROT_IAU)
+        return bad_arg("%s: frame.kind = %d, the frame must be an IAU-oriented frame (NYX_HIP_ROT_IAU)", name, q->frame.kind);
+    if (q->frame.n_nut_prec < 0 || q->frame.n_nut_prec > NYX_HIP_MAX_NUT_PREC)
+        return bad_arg("%s: frame.n_nut_prec = %d, 0 .. %d terms", name, q->frame.n_nut_prec, NYX_HIP_MAX_NUT_PREC);
+    if ((need & GT_NEED_GEODETIC) && !(q->frame_eq_radius_km > 0.0)) return bad_arg("%s: Latitude / Height need frame_eq_radius_km > 0", name);
+    if (!(q->frame_flattening >= 0.0 && q->frame_flattening < 1.0)) return bad_arg("%s: frame_flattening must be in [0, 1)", name);
+    return series_outputs(name, values, len);
+}
+
+// (epoch0_ns and moments are optional)
+inline Refusal check_ric_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                                const nyx_hip_ric_query_t *q, int64_t capacity, const double *values, const int32_t *len) {
+    const char *name = "traj_ric_diff";
+    if (Refusal r = series_open(name, ctx, traj, true, ref, q, n)) return r;
+    if (n_ref != 1 && n_ref != n)
+        return bad_arg("%s: n_ref = %lld, one reference trajectory or one per run (n = %lld)", name, (long long)n_ref, (long long)n);
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    if (q->frame_of != 0 && q->frame_of != 1) return bad_arg("%s: frame_of = %d, 0 (run) or 1 (reference)", name, q->frame_of);
+    if (q->transport != 0 && q->transport != 1) return bad_arg("%s: transport = %d, 0 or 1", name, q->transport);
+    if (q->smooth_window < 0 || q->smooth_window > NYX_HIP_RIC_MAX_WINDOW || (q->smooth_window != 0 && q->smooth_window % 2 == 0))
+        return bad_arg("%s: smooth_window = %d, 0 or an odd window up to %d", name, q->smooth_window, NYX_HIP_RIC_MAX_WINDOW);
+    return series_outputs(name, values, len);
+}
+
+// ---- the one output block of a report's host flavour: values[n_params][capacity][n], then the optional moments
+// [capacity][NYX_HIP_RIC_MOMENTS] and first epochs [n], then len[n].  Offsets and sizes in bytes; an absent part has size 0.
+struct SeriesBlock { size_t values_at, values, moments_at, moments, epoch0_at, epoch0, len_at, len, total; };
+inline SeriesBlock series_block(int64_t n_params, int64_t capacity, int64_t n, bool moments, bool epoch0) {
+    SeriesBlock b;
+    b.values_at = 0;
+    b.values = (size_t)n_params * (size_t)capacity * (size_t)n * sizeof(double);
+    b.moments_at = b.values_at + b.values;
+    b.moments = moments ? (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double) : 0;
+    b.epoch0_at = b.moments_at + b.moments;
+    b.epoch0 = epoch0 ? (size_t)n * sizeof(int64_t) : 0;
+    b.len_at = b.epoch0_at + b.epoch0;
+    b.len = (size_t)n * sizeof(int32_t);
+    b.total = b.len_at + b.len;
+    return b;
+}
+
+// ---- a span of samples in chunks of consecutive samples, one per grid.y: sixteen a chunk, more where that would take more than
+// kMaxChunks chunks
+constexpr int64_t kChunkSamples = 16, kMaxChunks = 32768;
+struct SeriesChunks { int64_t samples_per_block; unsigned grid_y; };
+inline SeriesChunks series_chunks(int64_t span) {
+    int64_t spb = kChunkSamples;
+    if ((span + spb - 1) / spb > kMaxChunks) spb = (span + kMaxChunks - 1) / kMaxChunks;
+    return {spb, (unsigned)((span + spb - 1) / spb)};
+}

@@ -21,6 +21,7 @@
 #include "../../include/nyx_hip.h"
 #include "hifitime_dev.h"
 #include "traj_args.h"
+#include "series_host.h"   // series_chunks
 #include "event_dev.h"
 #include "traj_dev.h"   // View, hrmint_*, traj_at: shared with report_kernel.hip
 
@@ -198,11 +199,9 @@ extern "C" hipError_t nyx_launch_traj_eval(const TrajEvalArgs *args, hipStream_t
     const int64_t span = a.mode == TRAJ_MODE_EVERY ? a.dst.capacity : a.m;
     hipLaunchKernelGGL(nyx_traj_init_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, a);
     if (span <= 0) return hipGetLastError();
-    // grid.y <= 32768 chunks of consecutive samples
-    int64_t spb = 16;
-    if ((span + spb - 1) / spb > 32768) spb = (span + 32767) / 32768;
-    a.samples_per_block = spb;
-    const dim3 grid((unsigned)((a.n + LANES - 1) / LANES), (unsigned)((span + spb - 1) / spb));
+    const SeriesChunks chunks = series_chunks(span);
+    a.samples_per_block = chunks.samples_per_block;
+    const dim3 grid((unsigned)((a.n + LANES - 1) / LANES), chunks.grid_y);
     hipLaunchKernelGGL(nyx_traj_eval_kernel, grid, dim3(LANES), 0, stream, a);
     return hipGetLastError();
 }

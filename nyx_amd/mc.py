@@ -280,6 +280,13 @@ class GroundTrackSeries:
         return self.values[self.params.index(param)]
 
 
+def _fill_head(head: np.ndarray, k: int, n_k: int, first_epoch_ns) -> None:
+    """Row k of the head of an array report - what every rank must know of a successful run before the columns are gathered:
+    its len, the bit pattern of its first epoch (0 for an empty series), and that it succeeded."""
+    head[k, 0], head[k, 2] = n_k, 1.0
+    head[k, 1:2] = np.array([first_epoch_ns if n_k else 0], dtype=np.int64).view(np.float64)
+
+
 RIC_TRIU = np.triu_indices(6)
 
 
@@ -393,6 +400,31 @@ class Results:
                 raise RuntimeError("another rank failed while preparing this collective report; aborted on every rank")
         if err is not None:
             raise err
+
+    def _gather_series(self, err: Optional[BaseException], head: np.ndarray, cols, n_rows: int, fill: float):
+        """The common end of the array reports: `head[k]` (see `_fill_head`) and `cols[k]` (values[n_rows, len], or None for a
+        failed run: a column of `fill`) of the local runs -> (values[n_rows, k_max, runs], len[runs], epoch0_ns[runs], ok[runs],
+        k_max, bounds) over ALL the runs; slots past a run's len are NaN.  `err`: what the caller's preparation raised, re-raised
+        on every rank (`_sync_errors`) before the first collective.  Sharded ensemble: the heads, then the rows are gathered in
+        index order; `bounds` are the shards' positions (None when not sharded)."""
+        self._sync_errors(err)
+        bounds = None
+        if self._dist is not None and self._dist.get_world_size() > 1:
+            world = self._dist.get_world_size()
+            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
+            head = all_gather_rows(self._dist, head, bounds)
+        k_max = int(head[:, 0].max()) if len(head) else 0
+        local = np.full((len(cols), n_rows * k_max), np.nan)
+        view = local.reshape(len(cols), n_rows, k_max)
+        for k, col in enumerate(cols):
+            if col is None:
+                view[k] = fill
+            else:
+                view[k, :, :col.shape[1]] = col
+        if bounds is not None and local.shape[1]:
+            local = all_gather_rows(self._dist, local, bounds)
+        values = np.ascontiguousarray(local.reshape(len(head), n_rows, k_max).transpose(1, 2, 0))
+        return values, head[:, 0].astype(np.int32), np.ascontiguousarray(head[:, 1]).view(np.int64).copy(), head[:, 2] > 0, k_max, bounds
 
     def _report(self, param: StateParameter, states_of_run, value_if_run_failed: Optional[float], prepare=None) -> List[float]:
         """One flat list, run after run.  Sharded ensemble: every rank reports the runs it propagated (it holds their
@@ -524,31 +556,11 @@ class Results:
                     else:   # host: the constants of the run (any rv of the right length does), or the whole composition
                         col[j] = self._value(p, run, rv if rv is not None else np.zeros((n_k, 6)))
                 cols[k] = col
-                head[k, 0], head[k, 2] = n_k, 1.0
-                head[k, 1:2] = np.array([first[row] if n_k else 0], dtype=np.int64).view(np.float64)
+                _fill_head(head, k, n_k, first[row])
         except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
             err = e
-        self._sync_errors(err)
-        sharded = self._dist is not None and self._dist.get_world_size() > 1
-        if sharded:
-            world = self._dist.get_world_size()
-            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
-            head_all = all_gather_rows(self._dist, head, bounds)
-        else:
-            head_all = head
-        k_max = int(head_all[:, 0].max()) if len(head_all) else 0
-        local = np.full((len(runs), len(params) * k_max), np.nan)
-        view = local.reshape(len(runs), len(params), k_max)
-        for k, col in enumerate(cols):
-            if col is None:
-                view[k] = fill
-            else:
-                view[k, :, :col.shape[1]] = col
-        if sharded and local.shape[1]:
-            local = all_gather_rows(self._dist, local, bounds)
-        values = np.ascontiguousarray(local.reshape(len(head_all), len(params), k_max).transpose(1, 2, 0))
-        return ValueSeries(params, values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(),
-                           step, head_all[:, 2] > 0)
+        values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), fill)
+        return ValueSeries(params, values, length, epoch0, step, ok)
 
     def _ric_of_run(self, row: int, ref, lo: int, hi: int, step: int, frame_of, transport: bool, window: int) -> np.ndarray:
         """d[6, len] of one run against the nominal by composition: two `traj_at` on the common grid, cut at the first epoch
@@ -620,36 +632,18 @@ class Results:
                 for k, row in zip(ok, rows):
                     cols[k] = self._ric_of_run(row, ref, int(first[row]), int(last[row]), step, frame_of, bool(transport), window)
             for k, row in zip(ok, rows):
-                n_k = cols[k].shape[1]
-                head[k, 0], head[k, 2] = n_k, 1.0
-                head[k, 1:2] = np.array([first[row] if n_k else 0], dtype=np.int64).view(np.float64)
+                _fill_head(head, k, cols[k].shape[1], first[row])
         except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
             err = e
-        self._sync_errors(err)
-        sharded = self._dist is not None and self._dist.get_world_size() > 1
-        if sharded:
-            world = self._dist.get_world_size()
-            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
-            head_all = all_gather_rows(self._dist, head, bounds)
-        else:
-            head_all = head
-        k_max = int(head_all[:, 0].max()) if len(head_all) else 0
-        local = np.full((len(runs), 6 * k_max), np.nan)
-        view = local.reshape(len(runs), 6, k_max)
-        for k, col in enumerate(cols):
-            if col is not None:
-                view[k, :, :col.shape[1]] = col
+        values, length, epoch0, ok, k_max, bounds = self._gather_series(err, head, cols, 6, np.nan)
         if mom is None:
             mom = ric_moments(cols, k_max)
         else:   # (the device sized its sums by the longest LOCAL series)
             mom = np.concatenate([mom[:k_max], np.zeros((max(k_max - len(mom), 0), _abi.RIC_MOMENTS))])
-        if sharded and k_max:
-            local = all_gather_rows(self._dist, local, bounds)
+        if bounds is not None and k_max:
             mom = all_reduce_sum(self._dist, mom.ravel()).reshape(k_max, _abi.RIC_MOMENTS)
-        values = np.ascontiguousarray(local.reshape(len(head_all), 6, k_max).transpose(1, 2, 0))
         count, mean, cov = ric_mean_cov(mom)
-        return RicSeries(values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(), step,
-                         head_all[:, 2] > 0, count, mean, cov, mom)
+        return RicSeries(values, length, epoch0, step, ok, count, mean, cov, mom)
 
     def ground_tracks(self, frame, step_ns: int, params=GROUND_TRACK_DEFAULT, start_ns: Optional[int] = None,
                       end_ns: Optional[int] = None) -> "GroundTrackSeries":
@@ -697,30 +691,11 @@ class Results:
                     yf = to_body_fixed(rv, int(first[row]) + step * np.arange(len(rv), dtype=np.int64), frame)
                     cols[k] = np.stack([body_fixed_value(p, yf, frame.mean_equatorial_radius_km, frame.flattening) for p in params]).reshape(len(params), len(rv))
             for k, row in zip(ok, rows):
-                n_k = cols[k].shape[1]
-                head[k, 0], head[k, 2] = n_k, 1.0
-                head[k, 1:2] = np.array([first[row] if n_k else 0], dtype=np.int64).view(np.float64)
+                _fill_head(head, k, cols[k].shape[1], first[row])
         except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
             err = e
-        self._sync_errors(err)
-        sharded = self._dist is not None and self._dist.get_world_size() > 1
-        if sharded:
-            world = self._dist.get_world_size()
-            bounds = [shard_bounds(len(self.runs), r, world) for r in range(world)]
-            head_all = all_gather_rows(self._dist, head, bounds)
-        else:
-            head_all = head
-        k_max = int(head_all[:, 0].max()) if len(head_all) else 0
-        local = np.full((len(runs), len(params) * k_max), np.nan)
-        view = local.reshape(len(runs), len(params), k_max)
-        for k, col in enumerate(cols):
-            if col is not None:
-                view[k, :, :col.shape[1]] = col
-        if sharded and local.shape[1]:
-            local = all_gather_rows(self._dist, local, bounds)
-        values = np.ascontiguousarray(local.reshape(len(head_all), len(params), k_max).transpose(1, 2, 0))
-        return GroundTrackSeries(params, values, head_all[:, 0].astype(np.int32), np.ascontiguousarray(head_all[:, 1]).view(np.int64).copy(),
-                                 step, head_all[:, 2] > 0, frame)
+        values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), np.nan)
+        return GroundTrackSeries(params, values, length, epoch0, step, ok, frame)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

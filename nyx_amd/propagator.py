@@ -822,28 +822,13 @@ class GpuContext:
         resampled and evaluated on the device in one pass: (values[P, capacity, n], len[n]).  `len[i]` counts the samples
         produced for trajectory i; slots from `len[i]` on are NaN.  `capacity=None` sizes the series from the batch's epochs;
         `mu_km3_s2=None` is the context's central body.  More than eight parameters take several launches."""
-        params = list(params)
         codes = [report_param_code(p) for p in params]
-        if (start_ns is None) != (end_ns is None):
-            raise ValueError("traj_values: a window needs both start_ns and end_ns")
-        cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
-        values = np.empty((len(codes), max(cap, 0), traj.n), dtype=np.float64)
-        length = np.zeros(traj.n, dtype=np.int32)
-        cin = traj.as_c()
-        for lo in range(0, len(codes), _abi.MAX_REPORT_PARAMS):
-            chunk = codes[lo:lo + _abi.MAX_REPORT_PARAMS]
-            q = _abi.ValuesQuery()
-            q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
-            q.param[:len(chunk)] = chunk
-            if start_ns is not None:
-                q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+
+        def fill(q):
             q.mu_km3_s2 = 0.0 if mu_km3_s2 is None else float(mu_km3_s2)   # (<= 0: the context's central body)
-            part = values[lo:lo + len(chunk)]   # (a contiguous block of the result: written in place)
-            rc = self._lib.nyx_hip_traj_values(self._h, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p),
-                                               length.ctypes.data_as(_abi.c_int32_p))
-            if rc != 0:
-                raise RuntimeError(f"nyx_hip_traj_values failed (rc={rc}): {_abi.last_error()}")
-        return values, length
+
+        return _param_series("traj_values", self._lib.nyx_hip_traj_values, self._h, _abi.ValuesQuery, _abi.MAX_REPORT_PARAMS, fill, traj, codes,
+                                  step_ns, start_ns, end_ns, capacity)
 
     def traj_ground_track(self, traj: _abi.TrajBatch, frame: "Frame", params, step_ns: int, start_ns: Optional[int] = None,
                           end_ns: Optional[int] = None, capacity: Optional[int] = None):
@@ -857,25 +842,8 @@ class GpuContext:
         params = list(params)
         codes = [gt_param_code(p) for p in params]
         check_frame(frame, self.compiled.central.naif_id, params)
-        if (start_ns is None) != (end_ns is None):
-            raise ValueError("traj_ground_track: a window needs both start_ns and end_ns")
-        cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
-        values = np.empty((len(codes), max(cap, 0), traj.n), dtype=np.float64)
-        length = np.zeros(traj.n, dtype=np.int32)
-        cin = traj.as_c()
-        for lo in range(0, len(codes), _abi.MAX_GT_PARAMS):
-            chunk = codes[lo:lo + _abi.MAX_GT_PARAMS]
-            q = _abi.GtQuery()
-            q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
-            q.param[:len(chunk)] = chunk
-            if start_ns is not None:
-                q.start_ns, q.end_ns = int(start_ns), int(end_ns)
-            fill_gt_frame(q, frame)
-            part = values[lo:lo + len(chunk)]   # (a contiguous block of the result: written in place)
-            rc = fn(self._h, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
-            if rc != 0:
-                raise RuntimeError(f"nyx_hip_traj_ground_track failed (rc={rc}): {_abi.last_error()}")
-        return values, length
+        return _param_series("traj_ground_track", fn, self._h, _abi.GtQuery, _abi.MAX_GT_PARAMS, lambda q: fill_gt_frame(q, frame), traj, codes,
+                                  step_ns, start_ns, end_ns, capacity)
 
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                       capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
@@ -914,6 +882,31 @@ class GpuContext:
         if rc != 0:
             raise RuntimeError(f"nyx_hip_propagate_until_epoch failed (rc={rc}): {_abi.last_error()}")
         return out, stats
+
+
+def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity):
+    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`) of the context `handle` over the parameter
+    codes, `per_call` of them per launch: (values[len(codes), capacity, n], len[n]).  `query_cls` is the entry's query, `fill(q)` sets the
+    fields that only this entry has."""
+    if (start_ns is None) != (end_ns is None):
+        raise ValueError(f"{name}: a window needs both start_ns and end_ns")
+    cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
+    values = np.empty((len(codes), max(cap, 0), traj.n), dtype=np.float64)
+    length = np.zeros(traj.n, dtype=np.int32)
+    cin = traj.as_c()
+    for lo in range(0, len(codes), per_call):
+        chunk = codes[lo:lo + per_call]
+        q = query_cls()
+        q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
+        q.param[:len(chunk)] = chunk
+        if start_ns is not None:
+            q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+        fill(q)
+        part = values[lo:lo + len(chunk)]   # (a contiguous block of the result: written in place)
+        rc = fn(handle, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
+        if rc != 0:
+            raise RuntimeError(f"nyx_hip_{name} failed (rc={rc}): {_abi.last_error()}")
+    return values, length
 
 
 def report_param_code(param) -> int:
@@ -966,11 +959,15 @@ def series_bounds(traj: _abi.TrajBatch, start_ns: Optional[int] = None, end_ns: 
     return lo, hi
 
 
-def values_capacity(traj: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> int:
-    """The longest series `traj_values` produces for this batch (at least 1: the ABI takes no empty buffer)."""
-    lo, hi = series_bounds(traj, start_ns, end_ns)
+def _longest_series(lo, hi, step_ns: int) -> int:
+    """Samples of the longest of the inclusive series lo[i] .. hi[i] every `step_ns`; 1 when all are empty (hi < lo)."""
     live = hi >= lo
     return int(np.max((hi[live] - lo[live]) // int(step_ns))) + 1 if live.any() else 1
+
+
+def values_capacity(traj: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> int:
+    """The longest series `traj_values` produces for this batch (at least 1: the ABI takes no empty buffer)."""
+    return _longest_series(*series_bounds(traj, start_ns, end_ns), step_ns)
 
 
 def ric_bounds(traj: _abi.TrajBatch, ref: _abi.TrajBatch, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
@@ -985,9 +982,7 @@ def ric_bounds(traj: _abi.TrajBatch, ref: _abi.TrajBatch, start_ns: Optional[int
 
 def ric_capacity(traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> int:
     """The longest series `traj_ric_diff` produces for these batches (at least 1: the ABI takes no empty buffer)."""
-    lo, hi = ric_bounds(traj, ref, start_ns, end_ns)
-    live = hi >= lo
-    return int(np.max((hi[live] - lo[live]) // int(step_ns))) + 1 if live.any() else 1
+    return _longest_series(*ric_bounds(traj, ref, start_ns, end_ns), step_ns)
 
 
 class PropInstance:

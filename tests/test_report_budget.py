@@ -1,7 +1,7 @@
 """CPU-side fence around the report kernels (report_kernel.hip), the twin of tests/test_code_budget.py for the kernels with
 the `nyxrep_` prefix: VGPRs, scratch bytes per lane, static spill counts and .text bytes of every one of them
 (tools/kernel_meta.py) are held to tests/golden/report_budget.json - a figure above its budget fails with the number, a
-figure more than 25 % BELOW its budget fails too (stale budget: `python tools/report_budget.py --update`), and the tests skip
+figure more than 25 % BELOW its budget fails too (stale budget: `python tools/series_budget.py report --update`), and the tests skip
 under another hipcc than the one the budgets were written under.  On top of that the evaluation kernel, which runs the
 interpolation of nyx_traj_eval_kernel plus the parameter block, may not use more scratch or spill more VGPRs than that
 sibling's own budget (tests/golden/code_budget.json): the parameter block must not push HRMINT's tables out of registers.
@@ -27,13 +27,13 @@ _CACHE = {}
 
 def measured():
     import code_budget
-    import report_budget
+    import series_budget
     want = json.load(open(BUDGET)).get("hipcc")
     have = code_budget.toolchain()
     if want and have and want != have:
-        pytest.skip(f"budgets were written under hipcc {want}, this is {have}: python tools/report_budget.py --update")
+        pytest.skip(f"budgets were written under hipcc {want}, this is {have}: python tools/series_budget.py report --update")
     if "m" not in _CACHE:
-        _CACHE["m"] = report_budget.measure(LIB)
+        _CACHE["m"] = series_budget.measure(LIB, "report")
     return _CACHE["m"]
 
 
@@ -43,7 +43,7 @@ def test_every_report_kernel_is_inside_its_budget():
     assert set(budget) == {"init_kernel", "values_kernel", "seal_kernel"}
     problems = []
     for kernel, b in budget.items():
-        assert kernel in got, f"{kernel}: not in the library any more (python tools/report_budget.py --update)"
+        assert kernel in got, f"{kernel}: not in the library any more (python tools/series_budget.py report --update)"
         for key, limit in b.items():
             v = got[kernel][key]
             if v > limit:

@@ -1,7 +1,7 @@
 """CPU-side fence around the RIC kernels (ric_kernel.hip), the twin of tests/test_report_budget.py for the kernels with the
 `nyxric_` prefix: VGPRs, scratch bytes per lane, static spill counts and .text bytes of every one of them
 (tools/kernel_meta.py) are held to tests/golden/ric_budget.json - a figure above its budget fails with the number, a figure
-more than 25 % BELOW its budget fails too (stale budget: `python tools/ric_budget.py --update`), and the tests skip under
+more than 25 % BELOW its budget fails too (stale budget: `python tools/series_budget.py ric --update`), and the tests skip under
 another hipcc than the one the budgets were written under.  On top of that the evaluation kernel, which runs the
 interpolation of nyx_traj_eval_kernel TWICE per sample (run, then reference), may not use more scratch or spill more VGPRs
 than that sibling's own budget (tests/golden/code_budget.json): the two interpolations are sequential so that their tables
@@ -28,13 +28,13 @@ _CACHE = {}
 
 def measured():
     import code_budget
-    import ric_budget
+    import series_budget
     want = json.load(open(BUDGET)).get("hipcc")
     have = code_budget.toolchain()
     if want and have and want != have:
-        pytest.skip(f"budgets were written under hipcc {want}, this is {have}: python tools/ric_budget.py --update")
+        pytest.skip(f"budgets were written under hipcc {want}, this is {have}: python tools/series_budget.py ric --update")
     if "m" not in _CACHE:
-        _CACHE["m"] = ric_budget.measure(LIB)
+        _CACHE["m"] = series_budget.measure(LIB, "ric")
     return _CACHE["m"]
 
 
@@ -44,7 +44,7 @@ def test_every_ric_kernel_is_inside_its_budget():
     assert set(budget) == KERNELS
     problems = []
     for kernel, b in budget.items():
-        assert kernel in got, f"{kernel}: not in the library any more (python tools/ric_budget.py --update)"
+        assert kernel in got, f"{kernel}: not in the library any more (python tools/series_budget.py ric --update)"
         for key, limit in b.items():
             v = got[kernel][key]
             if v > limit:
@@ -68,7 +68,7 @@ def test_two_interpolations_per_sample_do_not_push_the_tables_into_scratch():
 
 
 def test_ric_kernels_stay_out_of_the_other_fences():
-    """tools/code_budget.py takes every kernel whose name contains `nyx_`, tools/report_budget.py every `nyxrep_` one: the
+    """tools/code_budget.py takes every kernel whose name contains `nyx_`, the report fence (tools/series_budget.py) every `nyxrep_` one: the
     RIC kernels carry another prefix."""
     import kernel_meta
     names = [k.get("name", "") for k in kernel_meta.kernels(LIB)]
