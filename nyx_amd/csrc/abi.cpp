@@ -1438,6 +1438,13 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
         if (hist->stm) { if (int rc = h_stm.alloc(slots * 81 * 8)) return rc; a.hist.stm = h_stm.as<double>(); }
         if (hist->covar) { if (int rc = h_covar.alloc(slots * 81 * 8)) return rc; a.hist.covar = h_covar.as<double>(); }
         if (hist->state_dev) { if (int rc = h_sdev.alloc(slots * 9 * 8)) return rc; a.hist.state_dev = h_sdev.as<double>(); }
+        // a run with fewer updates than the capacity (ragged starts, a failure) leaves its last slots unwritten, and the whole block is
+        // copied back: zeros there, as the oracle leaves them, not what the allocation held
+        if (a.hist.epoch_ns) HIP_TRY(hipMemsetAsync(a.hist.epoch_ns, 0, slots * 8, nullptr));
+        if (a.hist.state) HIP_TRY(hipMemsetAsync(a.hist.state, 0, slots * 9 * 8, nullptr));
+        if (a.hist.stm) HIP_TRY(hipMemsetAsync(a.hist.stm, 0, slots * 81 * 8, nullptr));
+        if (a.hist.covar) HIP_TRY(hipMemsetAsync(a.hist.covar, 0, slots * 81 * 8, nullptr));
+        if (a.hist.state_dev) HIP_TRY(hipMemsetAsync(a.hist.state_dev, 0, slots * 9 * 8, nullptr));
     }
     hipStream_t stream = nullptr;
     HIP_TRY(hipEventRecord(ctx->ev0, stream));

@@ -6,33 +6,11 @@ import pytest
 
 import nyx_amd as nx
 import oracle_lib
-from nyx_amd import ephem
-from scenarios import EPOCH0_NS, dispersed_leo_batch, keplerian_to_cartesian, leo_full_setup
+from predict_cases import geo_batch, init_covar, oracle_predict_threaded, rel_err
+from scenarios import EPOCH0_NS, dispersed_leo_batch, leo_full_setup
 
 pytestmark = pytest.mark.gpu
 S = nx.NS_PER_S
-
-
-def geo_batch(n, seed):
-    b = dispersed_leo_batch(n, seed=seed)
-    geo = keplerian_to_cartesian(42164.0, 1e-5, 0.0, 163.0, 75.0, 0.0, ephem.MU_EARTH)   # examples/03_geo_analysis/drift.rs:50
-    rv = b.rv()
-    b.set_rv(geo[None, :] + (rv - rv.mean(axis=0)))
-    return b
-
-
-def init_covar(n, seed=0):
-    rng = np.random.default_rng(seed)
-    out = np.zeros((n, 9, 9))
-    for i in range(n):
-        a = rng.standard_normal((9, 9)) * np.array([1.0, 1.0, 1.0, 1e-3, 1e-3, 1e-3, 1e-2, 0.0, 0.0])[:, None]
-        out[i] = a @ a.T
-    return out
-
-
-def rel_err(got, ref):
-    scale = np.maximum(np.abs(ref), 1e-6 * np.abs(ref).max(axis=(-2, -1), keepdims=True))
-    return (np.abs(got - ref) / scale).max()
 
 
 def test_config4_geo_covariance_map_vs_oracle():
@@ -155,7 +133,7 @@ def test_requires_an_stm_context_and_valid_config():
 
 
 def test_config4_full_size_one_hour():
-    # N = 1 000 GEO states (BASELINE config 4), 60 one-minute updates in one call; properties + head vs the oracle
+    # N = 1 000 GEO states (BASELINE config 4), 60 one-minute updates in one call; properties + every trajectory vs the oracle
     prop, almanac, central = leo_full_setup(degree=21)
     compiled = prop.compile(almanac, central, stm=True)
     ctx = nx.GpuContext(compiled)
@@ -170,11 +148,15 @@ def test_config4_full_size_one_hour():
     assert (d >= 0).all() and (d[-1, :, :3] > 1.0).all()                         # positive, position variance inflates
     asym = np.abs(got.covar - np.transpose(got.covar, (0, 2, 1))).max() / np.abs(got.covar).max()
     assert asym < 1e-12
-    head = nx._abi.StateBatch(8)
-    for f in ["epoch_ns"] + nx._abi.F64_FIELDS:
-        getattr(head, f)[:] = getattr(b, f)[:8]
-    ref = oracle_lib.predict_until(compiled, head, p0[:8], end, 60 * S, history=60, keep_stm=False)
-    assert rel_err(got.covar_history[:, :8], ref.covar_history) < 1e-9
+    # the whole ensemble against the oracle (serial and re-entrant: sliced over a thread pool)
+    ref = oracle_predict_threaded(compiled, b, p0, end, 60 * S, history=60, keep_stm=False)
+    assert (ref.stats.status == 0).all() and (ref.n_updates == 60).all()
+    e_p = rel_err(got.covar_history, ref.covar_history)
+    dr = np.linalg.norm(got.states.rv()[:, :3] - ref.states.rv()[:, :3], axis=1).max()
+    dv = np.linalg.norm(got.states.rv()[:, 3:] - ref.states.rv()[:, 3:], axis=1).max()
+    print(f"config 4 full size vs the oracle, all {n}: Pbar {e_p:.2e} dr {dr*1e3:.2e} m dv {dv*1e6:.2e} mm/s")
+    assert e_p < 1e-9
+    assert dr < 1e-3 and dv < 1e-6
     print(f"config 4 full size: 60 updates x {n} trajectories in {got.kernel_ms:.1f} ms of device time "
           f"({got.kernel_ms / 60:.2f} ms per update)")
     ctx.close()
