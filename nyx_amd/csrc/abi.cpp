@@ -1,5 +1,5 @@
 // abi.cpp — host side of the C-ABI (include/nyx_hip.h): context creation (what it builds: ctx_build.h; the launch policy:
-// launch_plan.h; how a batch's arrays reach a launch: batch_bind.h; here the device, the uploads), batch staging and kernel launch.
+// launch_plan.h; a batch's arrays in a launch: batch_bind.h; refusals and device blocks: run_host.h, series_host.h; here the device, the uploads), batch staging and kernel launch.
 // Compiled with hipcc.
 
 #include <hip/hip_runtime.h>
@@ -31,6 +31,7 @@
 #include "ric_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
+#include "run_host.h"
 
 extern "C" size_t nyx_kernel_lds_bytes(int n_waves, int rec_doubles, int stm, int reuse_fields);
 extern "C" hipError_t nyx_launch_predict_init(const PredictArgs *a, const int64_t *epoch0, hipStream_t stream);
@@ -64,7 +65,7 @@ void nyx_set_error(const char *fmt, ...) {
 
 extern "C" const char *nyx_hip_last_error(void) { return g_err; }
 
-// A refusal of one of the pure headers (series_host.h): its message becomes the last error, its code the return value.
+// A refusal of one of the pure headers (run_host.h, series_host.h): its message becomes the last error, its code the return value.
 static int refused(const Refusal &r) {
     nyx_set_error("%s", r.msg);
     return r.rc;
@@ -78,6 +79,18 @@ static int refused(const Refusal &r) {
             return NYX_HIP_RC_HIP_ERROR;                                                   \
         }                                                                                  \
     } while (0)
+
+struct DevBuf {  // RAII device allocation
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) {
+        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) == hipSuccess) return NYX_HIP_RC_OK;
+        p = nullptr;
+        nyx_set_error("hipMalloc of %zu bytes failed", bytes);
+        return NYX_HIP_RC_HIP_ERROR;
+    }
+    template <typename T> T *as() const { return (T *)p; }
+};
 
 // ---------------------------------------------------------------------------------------------
 // context
@@ -557,8 +570,6 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
 // propagate
 // ---------------------------------------------------------------------------------------------
 
-static bool calibration_on(const nyx_hip_ctx *ctx) { return ctx->tune.schedule == NYX_HIP_SCHED_CALIBRATED; }
-
 static int launch(nyx_hip_ctx *ctx, const LaunchReq &r);
 
 // Device views of a DevArrays block (outputs + stats).
@@ -723,8 +734,7 @@ static int launch_here(nyx_hip_ctx *ctx, const LaunchReq &r) {
         const WKey key = weight_key(ctx->host_cfg, nw, plan.quad, bt.coop_helpers > 0);
         ctx->last_key = key;
         const int64_t span = r.use_end ? INT64_MAX : (r.duration_ns < 0 ? -r.duration_ns : r.duration_ns);
-        if (!r.calibrating && calibration_on(ctx) && ctx->host_cfg.has_grav && nw >= 8 && in->n >= 64 && !r.traj && !r.dur_ns && !r.ev &&
-            span >= 100 * ctx->host_cfg.init_step_ns && !ctx->weights.count(key)) {
+        if (calibrates_first(plan_inputs(ctx), ctx->host_cfg, key, nw, in->n, /*min_n=*/64, !r.calibrating && !r.traj && !r.dur_ns && !r.ev, span, /*min_steps=*/100)) {
             if (int rc = calibrate(ctx, in, stream, !r.use_end && r.duration_ns < 0)) return rc;
             return launch_here(ctx, r);
         }
@@ -793,19 +803,11 @@ static int launch(nyx_hip_ctx *ctx, const LaunchReq &r) {
     return NYX_HIP_RC_OK;
 }
 
-static int check_states(const nyx_hip_states_t *s, const char *what) {
-    if (!s || s->n < 0 || !s->epoch_ns || !s->x_km || !s->y_km || !s->z_km || !s->vx_km_s || !s->vy_km_s || !s->vz_km_s) {
-        nyx_set_error("%s: epoch and the six Cartesian arrays are mandatory", what);
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    return NYX_HIP_RC_OK;
-}
-
 // The device entry points: the caller's device arrays, on the caller's stream.
 static int propagate_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns, nyx_hip_states_t *out,
                             nyx_hip_step_stats_t *stats, const nyx_hip_traj_t *traj, void *hip_stream) {
-    if (int rc = check_states(in, "in")) return rc;
-    if (int rc = check_states(out, "out")) return rc;
+    if (Refusal r = check_states(in, "in")) return refused(r);
+    if (Refusal r = check_states(out, "out")) return refused(r);
     if (in->n == 0) return NYX_HIP_RC_OK;
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -835,8 +837,8 @@ struct Staged {
 };
 
 // H2D of a host batch through the pinned mirror (one copy for the SoA block, one for the STMs).
-// `upload_stm` false leaves ctx->in.stm allocated but unwritten (covariance mapping starts from identity).
-static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_hip_states_t *out, Staged &sg, bool upload_stm = true) {
+// `upload_stm` false leaves ctx->in.stm allocated but unwritten (covariance mapping starts from identity); true: check_run has seen in->stm.
+static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, Staged &sg, bool upload_stm) {
     const int64_t n = in->n;
     if (int rc = ensure_arrays(ctx->in, n, false)) return rc;
     if (int rc = ensure_arrays(ctx->out, n, true)) return rc;
@@ -851,7 +853,6 @@ static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_h
     HIP_TRY(hipMemcpy(di.dblock, di.hblock, (size_t)((char *)(di.f[kStateRows - 1] + di.cap) - di.dblock), hipMemcpyHostToDevice));
     sg.stm = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
     if (sg.stm) {
-        if (upload_stm && (!in->stm || !out->stm)) { nyx_set_error("STM context: in->stm and out->stm are mandatory"); return NYX_HIP_RC_BAD_ARG; }
         for (DevArrays *d : {&di, &dq})
             if (int rc = ensure_stm(*d, n)) return rc;
         if (upload_stm) HIP_TRY(hipMemcpy(di.stm, in->stm, (size_t)n * 81 * sizeof(double), hipMemcpyHostToDevice));
@@ -880,19 +881,14 @@ static int fetch_batch(nyx_hip_ctx *ctx, int64_t n, bool stm, nyx_hip_states_t *
 // A nyx_hip_traj_t whose arrays are one device allocation (RAII), laid out by traj_in_block (batch_bind.h).
 struct DevTraj {
     nyx_hip_traj_t t;
-    void *block = nullptr;
+    DevBuf block;
     size_t slots = 0;
     int64_t n = 0;
-    ~DevTraj() { if (block) (void)hipFree(block); }
     int alloc(int64_t capacity, int64_t n_) {
         n = n_;
         slots = (size_t)capacity * (size_t)n;
-        if (hipMalloc(&block, traj_block_bytes(capacity, n)) != hipSuccess) {
-            block = nullptr;
-            nyx_set_error("hipMalloc of the trajectory staging block failed");
-            return NYX_HIP_RC_HIP_ERROR;
-        }
-        t = traj_in_block(block, capacity, n);
+        if (int rc = block.alloc(traj_block_bytes(capacity, n))) return rc;
+        t = traj_in_block(block.p, capacity, n);
         return NYX_HIP_RC_OK;
     }
     int upload(const nyx_hip_traj_t *h) const { return copy(*h, t, hipMemcpyHostToDevice); }
@@ -906,34 +902,40 @@ struct DevTraj {
     }
 };
 
-static int host_propagate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns, int64_t end_epoch_ns, bool use_end,
-                          nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj = nullptr) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_states(in, "in")) return rc;
-    if (int rc = check_states(out, "out")) return rc;
+// The host bracket of a run: what every such entry checks (check_run, run_host.h; an empty batch is done), the batch staged in the
+// context's blocks, `enqueue(sg)` - the entry's launches on the staged views -, awaited and timed, the states and stats fetched, then
+// `collect()` - the entry's own copies back.  `upload_stm` false: predict_until.  `traced`: host_propagate (debug_flags 0x400: stderr).
+template <typename Enqueue, typename Collect>
+static int host_run(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, bool upload_stm, bool traced, Enqueue enqueue, Collect collect) {
+    if (Refusal r = check_run(ctx, in, out, upload_stm && ctx && (ctx->host_cfg.flags & NYX_HIP_FLAG_STM))) return refused(r);
     const int64_t n = in->n;
     if (n == 0) return NYX_HIP_RC_OK;
-    if (out->n < n) { nyx_set_error("out batch smaller than in batch"); return NYX_HIP_RC_BAD_ARG; }
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool trace = (ctx->tune.debug_flags & 0x400) != 0;  // (tuning.debug_flags 0x400: milestones of the host path on stderr)
+    const bool trace = traced && (ctx->tune.debug_flags & 0x400) != 0;
     if (trace) std::fprintf(stderr, "[nyx_hip] host_propagate n=%lld: staging\n", (long long)n);
     Staged sg;
-    if (int rc = stage_batch(ctx, in, out, sg)) return rc;
+    if (int rc = stage_batch(ctx, in, sg, upload_stm)) return rc;
     if (trace) std::fprintf(stderr, "[nyx_hip] staged, launching\n");
-    const bool dense = traj && traj->capacity > 0;
-    DevTraj dtraj;
-    if (int rc = dense ? dtraj.alloc(traj->capacity, n) : NYX_HIP_RC_OK) return rc;
-    LaunchReq r;
-    r.in = &sg.din; r.out = &sg.dout; r.stats = &sg.dst; r.timed = true;
-    r.duration_ns = duration_ns; r.end_epoch_ns = end_epoch_ns; r.use_end = use_end; r.traj = dense ? &dtraj.t : nullptr;
-    if (int rc = launch(ctx, r)) return rc;
+    if (int rc = enqueue(sg)) return rc;
     if (trace) std::fprintf(stderr, "[nyx_hip] launched (%d helpers, %d waves), synchronising\n", ctx->last_coop_helpers, ctx->host_cfg.n_waves);
     HIP_TRY(hipDeviceSynchronize());
     if (trace) std::fprintf(stderr, "[nyx_hip] kernel done\n");
-    if (int rc = dense ? dtraj.download(traj) : NYX_HIP_RC_OK) return rc;
     read_kernel_ms(ctx);
-    return fetch_batch(ctx, n, sg.stm, out, stats);
+    if (int rc = fetch_batch(ctx, n, sg.stm, out, stats)) return rc;
+    return collect();
+}
+
+static int host_propagate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns, int64_t end_epoch_ns, bool use_end,
+                          nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj = nullptr) {
+    const bool dense = traj && traj->capacity > 0;
+    DevTraj dtraj;
+    return host_run(ctx, in, out, stats, true, true, [&](Staged &sg) -> int {
+        if (int rc = dense ? dtraj.alloc(traj->capacity, in->n) : NYX_HIP_RC_OK) return rc;
+        LaunchReq r;
+        r.in = &sg.din; r.out = &sg.dout; r.stats = &sg.dst; r.timed = true; r.duration_ns = duration_ns; r.end_epoch_ns = end_epoch_ns; r.use_end = use_end; r.traj = dense ? &dtraj.t : nullptr;
+        return launch(ctx, r);
+    }, [&]() -> int { return dense ? dtraj.download(traj) : NYX_HIP_RC_OK; });
 }
 
 extern "C" int32_t nyx_hip_propagate_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
@@ -943,7 +945,7 @@ extern "C" int32_t nyx_hip_propagate_batch(nyx_hip_ctx *ctx, const nyx_hip_state
 
 extern "C" int32_t nyx_hip_propagate_batch_with_traj(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t duration_ns,
                                                      nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj) {
-    if (!traj || traj->capacity < 1) { nyx_set_error("traj with capacity >= 1 required"); return NYX_HIP_RC_BAD_ARG; }
+    if (Refusal r = check_traj_wanted(traj)) return refused(r);
     return host_propagate(ctx, in, duration_ns, 0, false, out, stats, traj);
 }
 
@@ -962,11 +964,7 @@ extern "C" int32_t nyx_hip_propagate_until_epoch(nyx_hip_ctx *ctx, const nyx_hip
 // ---------------------------------------------------------------------------------------------
 extern "C" int32_t nyx_hip_propagate_batch_sharded(nyx_hip_ctx *const *ctxs, int32_t n_ctx, const nyx_hip_states_t *in, int64_t duration_ns,
                                                    nyx_hip_states_t *out, nyx_hip_step_stats_t *stats, nyx_hip_traj_t *traj) {
-    if (!ctxs || n_ctx < 1 || !in || !out) { nyx_set_error("sharded: null argument or no context"); return NYX_HIP_RC_BAD_ARG; }
-    for (int32_t k = 0; k < n_ctx; ++k)
-        if (!ctxs[k]) { nyx_set_error("sharded: null context %d", k); return NYX_HIP_RC_BAD_ARG; }
-    if (out->n != in->n) { nyx_set_error("sharded: out->n != in->n"); return NYX_HIP_RC_BAD_ARG; }
-    if (traj && traj->capacity < 1) { nyx_set_error("traj with capacity >= 1 required"); return NYX_HIP_RC_BAD_ARG; }
+    if (Refusal r = check_sharded(ctxs, n_ctx, in, out, traj)) return refused(r);
     const int64_t n = in->n, cap = traj ? traj->capacity : 0;
     std::vector<int32_t> rcs((size_t)n_ctx, NYX_HIP_RC_OK);
     std::vector<std::string> errs((size_t)n_ctx);
@@ -1045,10 +1043,7 @@ extern "C" int32_t nyx_hip_traj_every_device(nyx_hip_ctx *ctx, const nyx_hip_tra
 // Ensemble moments of the final states (mc/results.rs:60-245 consumers): moments_kernel.hip
 // ---------------------------------------------------------------------------------------------
 static int moments_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *s, const int32_t *status, const double *x0, double *out55, hipStream_t stream) {
-    if (!ctx || !s || !out55 || s->n < 0 || (s->n > 0 && (!s->x_km || !s->y_km || !s->z_km || !s->vx_km_s || !s->vy_km_s || !s->vz_km_s))) {
-        nyx_set_error("ensemble_moments: ctx, states (six Cartesian arrays) and out are mandatory");
-        return NYX_HIP_RC_BAD_ARG;
-    }
+    if (Refusal r = check_moments(ctx, s, out55, false)) return refused(r);
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->d_mom) HIP_TRY(hipMalloc((void **)&ctx->d_mom, (size_t)(MOM_BLOCKS + 1) * MOM_N * sizeof(double)));
     MomArgs a;
@@ -1071,81 +1066,51 @@ extern "C" int32_t nyx_hip_ensemble_moments_device(nyx_hip_ctx *ctx, const nyx_h
     return moments_device(ctx, states, status, x0, out55, (hipStream_t)hip_stream);
 }
 
+// Host arrays: one device block (moments_block), copied row by row; the reduction itself is two small launches into the tail of the context's scratch.
 extern "C" int32_t nyx_hip_ensemble_moments(nyx_hip_ctx *ctx, const nyx_hip_states_t *states, const int32_t *status, const double *x0, double *out55) {
-    if (!ctx || !states || !out55 || states->n < 0) { nyx_set_error("ensemble_moments: null argument"); return NYX_HIP_RC_BAD_ARG; }
+    if (Refusal r = check_moments(ctx, states, out55, true)) return refused(r);
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    const int64_t n = states->n;
-    if (n > 0 && (!states->x_km || !states->y_km || !states->z_km || !states->vx_km_s || !states->vy_km_s || !states->vz_km_s)) {
-        nyx_set_error("ensemble_moments: the six Cartesian arrays are mandatory");
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    // host arrays: one device block of 9 rows (+ the status words), copied row by row; the reduction itself is two small launches
-    char *blk = nullptr;
-    const size_t row = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
-    HIP_TRY(hipMalloc((void **)&blk, kMomentRows * row + (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
-    nyx_hip_states_t d;
-    std::memset(&d, 0, sizeof d);
-    d.n = n;
-    int rc = NYX_HIP_RC_OK;
-    for (int k = 0; k < kMomentRows && rc == NYX_HIP_RC_OK; ++k) {
-        const double *h = states->*kStateRow[k].s;
-        if (!h) continue;
-        double *dk = d.*kStateRow[k].s = (double *)(blk + (size_t)k * row);
-        if (n > 0 && hipMemcpy(dk, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
-    }
-    int32_t *dst = nullptr;
-    if (rc == NYX_HIP_RC_OK && status) {
-        dst = (int32_t *)(blk + kMomentRows * row);
-        if (n > 0 && hipMemcpy(dst, status, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
-    }
-    if (rc == NYX_HIP_RC_OK) {
-        if (!ctx->d_mom && hipMalloc((void **)&ctx->d_mom, (size_t)(MOM_BLOCKS + 1) * MOM_N * sizeof(double)) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
-    }
-    if (rc == NYX_HIP_RC_OK) rc = moments_device(ctx, &d, dst, x0, ctx->d_mom + (size_t)MOM_BLOCKS * MOM_N, nullptr);
-    if (rc == NYX_HIP_RC_OK && hipMemcpy(out55, ctx->d_mom + (size_t)MOM_BLOCKS * MOM_N, MOM_N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = NYX_HIP_RC_HIP_ERROR;
-    if (rc == NYX_HIP_RC_HIP_ERROR) nyx_set_error("ensemble_moments: HIP error: %s", hipGetErrorString(hipGetLastError()));
-    (void)hipFree(blk);
-    return rc;
+    const auto b = moments_block(states->n, status != nullptr);
+    DevBuf blk;
+    if (int rc = blk.alloc(b.total)) return rc;
+    nyx_hip_states_t d{}; d.n = states->n;  // (the staged rows: a device pointer where the caller gave a row)
+    for (int k = 0; k < kMomentRows; ++k)
+        if (const double *h = states->*kStateRow[k].s) {
+            d.*kStateRow[k].s = (double *)(blk.as<char>() + b[k].at);
+            if (b[k].bytes) HIP_TRY(hipMemcpy(d.*kStateRow[k].s, h, b[k].bytes, hipMemcpyHostToDevice));
+        }
+    int32_t *dst = status ? (int32_t *)(blk.as<char>() + b[M_STATUS].at) : nullptr;
+    if (b[M_STATUS].bytes) HIP_TRY(hipMemcpy(dst, status, b[M_STATUS].bytes, hipMemcpyHostToDevice));
+    if (!ctx->d_mom) HIP_TRY(hipMalloc((void **)&ctx->d_mom, (size_t)(MOM_BLOCKS + 1) * MOM_N * sizeof(double)));
+    double *result = ctx->d_mom + (size_t)MOM_BLOCKS * MOM_N;
+    if (int rc = moments_device(ctx, &d, dst, x0, result, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out55, result, MOM_N * sizeof(double), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
 }
 
-static int traj_eval_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query, int64_t m,
-                          int64_t step_ns, nyx_hip_traj_t *out, int32_t *status, int mode) {
-    if (!ctx) { nyx_set_error("null ctx"); return NYX_HIP_RC_BAD_ARG; }
-    if (Refusal r = check_traj(traj, "traj", true)) return refused(r);
-    if (Refusal r = check_traj(out, "out", true)) return refused(r);
-    if (n <= 0) return n == 0 ? NYX_HIP_RC_OK : NYX_HIP_RC_BAD_ARG;
+static int traj_eval_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query, int64_t m, int64_t step_ns, nyx_hip_traj_t *out, int32_t *status, int mode) {
+    if (Refusal r = check_traj_eval_host(ctx, traj, n, query, m, step_ns, out, status, mode)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     DevTraj src, dst;
     if (int rc = src.alloc(traj->capacity, n)) return rc;
     if (int rc = dst.alloc(out->capacity, n)) return rc;
     if (int rc = src.upload(traj)) return rc;
-    int64_t *d_query = nullptr;
-    int32_t *d_status = nullptr;
-    int rc = NYX_HIP_RC_OK;
-    if (mode == TRAJ_MODE_AT && m > 0) {
-        if (!query || !status) { nyx_set_error("traj_at: query/status arrays required"); return NYX_HIP_RC_BAD_ARG; }
-        if (hipMalloc(&d_query, (size_t)m * sizeof(int64_t)) != hipSuccess ||
-            hipMalloc(&d_status, (size_t)m * (size_t)n * sizeof(int32_t)) != hipSuccess ||
-            hipMemcpy(d_query, query, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
-            nyx_set_error("traj_at: staging of the query epochs failed");
-            rc = NYX_HIP_RC_HIP_ERROR;
-        }
+    DevBuf d_query, d_status;  // traj_at with m > 0 only: the query epochs [m], the statuses [m][n]
+    const size_t qbytes = mode == TRAJ_MODE_AT ? (size_t)m * sizeof(int64_t) : 0, sbytes = mode == TRAJ_MODE_AT ? (size_t)m * (size_t)n * sizeof(int32_t) : 0;
+    if (qbytes) {
+        if (int rc = d_query.alloc(qbytes)) return rc;
+        if (int rc = d_status.alloc(sbytes)) return rc;
+        HIP_TRY(hipMemcpy(d_query.p, query, qbytes, hipMemcpyHostToDevice));
     }
-    if (!rc) rc = traj_eval_device(ctx, &src.t, n, d_query, m, step_ns, &dst.t, d_status, mode, nullptr);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) { nyx_set_error("trajectory evaluation kernel failed"); rc = NYX_HIP_RC_HIP_ERROR; }
-    if (!rc) {
-        read_kernel_ms(ctx);
-        rc = dst.download(out);
-    }
-    if (!rc && d_status && hipMemcpy(status, d_status, (size_t)m * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-        nyx_set_error("traj_at: D2H of the statuses failed");
-        rc = NYX_HIP_RC_HIP_ERROR;
-    }
-    (void)hipFree(d_query);
-    (void)hipFree(d_status);
-    return rc;
+    if (int rc = traj_eval_device(ctx, &src.t, n, d_query.as<int64_t>(), m, step_ns, &dst.t, d_status.as<int32_t>(), mode, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    read_kernel_ms(ctx);
+    if (int rc = dst.download(out)) return rc;
+    if (sbytes) HIP_TRY(hipMemcpy(status, d_status.p, sbytes, hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
 }
 
 extern "C" int32_t nyx_hip_traj_at(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const int64_t *query_epoch_ns, int64_t m,
@@ -1169,20 +1134,6 @@ extern "C" int32_t nyx_hip_reports_sizeof(int32_t which) {
     default: return -1;
     }
 }
-
-struct DevBuf {  // RAII device allocation
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-            p = nullptr;
-            nyx_set_error("hipMalloc of %zu bytes failed", bytes);
-            return NYX_HIP_RC_HIP_ERROR;
-        }
-        return NYX_HIP_RC_OK;
-    }
-    template <typename T> T *as() const { return (T *)p; }
-};
 
 // The host flavour of a report: the trajectories (`ref`: RIC's, or null) staged on the device, the outputs one block laid out by
 // series_block, `entry(src, ref, outputs)` - the device flavour on those - awaited and timed, every non-empty part copied back.
@@ -1321,61 +1272,34 @@ extern "C" int32_t nyx_hip_traj_ric_diff(nyx_hip_ctx *ctx, const nyx_hip_traj_t 
 extern "C" int32_t nyx_hip_propagate_until_event(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, int64_t max_duration_ns,
                                                  const nyx_hip_event_t *event, nyx_hip_states_t *out, nyx_hip_step_stats_t *stats,
                                                  nyx_hip_traj_t *traj, int32_t *crossings) {
-    if (!ctx || !event) { nyx_set_error("until_event: ctx and event are mandatory"); return NYX_HIP_RC_BAD_ARG; }
-    if (event->has_frame && (event->frame.kind != NYX_HIP_ROT_IAU || event->frame.n_nut_prec < 0 || event->frame.n_nut_prec > NYX_HIP_MAX_NUT_PREC)) {
-        nyx_set_error("until_event: the event frame must be an IAU-oriented frame (NYX_HIP_ROT_IAU)");
-        return NYX_HIP_RC_UNSUPPORTED;
-    }
-    if ((event->scalar == NYX_HIP_EV_LATITUDE_DEG || event->scalar == NYX_HIP_EV_HEIGHT_KM) &&
-        !(event->frame_eq_radius_km > 0.0 && event->frame_flattening >= 0.0 && event->frame_flattening < 1.0)) {
-        nyx_set_error("until_event: geodetic scalars need the frame's ellipsoid (frame_eq_radius_km > 0, 0 <= flattening < 1)");
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if (event->scalar < NYX_HIP_EV_TRUE_ANOMALY_DEG || event->scalar > NYX_HIP_EV_HEIGHT_KM || event->trigger < 1 ||
-        event->epoch_precision_ns < 0 || !(event->value_precision >= 0.0)) {
-        nyx_set_error("until_event: bad event (scalar, trigger >= 1, precisions >= 0)");
-        return NYX_HIP_RC_BAD_ARG;
-    }
-    if (Refusal r = check_traj(traj, "traj", true)) return refused(r);
-    if (traj->capacity < 2) { nyx_set_error("until_event: traj->capacity >= 2 required (the search needs the bracket)"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_states(in, "in")) return rc;
-    if (int rc = check_states(out, "out")) return rc;
-    const int64_t n = in->n;
-    if (n == 0) return NYX_HIP_RC_OK;
-    if (out->n < n) { nyx_set_error("out batch smaller than in batch"); return NYX_HIP_RC_BAD_ARG; }
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    Staged sg;
-    if (int rc = stage_batch(ctx, in, out, sg)) return rc;
+    if (Refusal r = check_event(ctx, event, traj)) return refused(r);
     DevTraj dtraj;
-    if (int rc = dtraj.alloc(traj->capacity, n)) return rc;
-    DevBuf evbuf, evdesc;  // prev (f64), count, found (i32); the event descriptor itself
-    if (int rc = evbuf.alloc((size_t)n * 16)) return rc;
-    if (int rc = evdesc.alloc(sizeof(nyx_hip_event_t))) return rc;
-    HIP_TRY(hipMemcpy(evdesc.p, event, sizeof(nyx_hip_event_t), hipMemcpyHostToDevice));
-    DevBatch ev;
-    std::memset(&ev, 0, sizeof ev);
-    ev.ev = evdesc.as<nyx_hip_event_t>();
-    ev.ev_mu = ctx->host_cfg.mu_central;
-    ev.ev_prev = evbuf.as<double>();
-    ev.ev_count = (int32_t *)(evbuf.as<double>() + n);
-    ev.ev_found = ev.ev_count + n;
-    HIP_TRY(hipMemset(evbuf.p, 0, (size_t)n * 16));
-    LaunchReq r;
-    r.in = &sg.din; r.out = &sg.dout; r.stats = &sg.dst; r.duration_ns = max_duration_ns; r.traj = &dtraj.t; r.ev = &ev; r.timed = true;
-    if (int rc = launch(ctx, r)) return rc;
-    EventSearchArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.traj = dtraj.t; a.n = n; a.ev = *event; a.mu = ctx->host_cfg.mu_central;
-    a.found = ev.ev_found; a.status = sg.dst.status; a.epoch_ns = sg.dout.epoch_ns;
-    for (int c = 0; c < kCartRows; ++c) a.state[c] = sg.dout.*kStateRow[c].s;
-    HIP_TRY(nyx_launch_event_search(&a, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    read_kernel_ms(ctx);
-    if (int rc = fetch_batch(ctx, n, sg.stm, out, stats)) return rc;
-    if (int rc = dtraj.download(traj)) return rc;
-    if (crossings) HIP_TRY(hipMemcpy(crossings, ev.ev_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    DevBuf evbuf, evdesc;  // prev, count, found (event_block); the event descriptor itself
+    DevBatch ev{};
+    return host_run(ctx, in, out, stats, true, false, [&](Staged &sg) -> int {
+        const int64_t n = in->n;
+        if (int rc = dtraj.alloc(traj->capacity, n)) return rc;
+        const auto b = event_block(n);
+        if (int rc = evbuf.alloc(b.total)) return rc;
+        if (int rc = evdesc.alloc(sizeof(nyx_hip_event_t))) return rc;
+        HIP_TRY(hipMemcpy(evdesc.p, event, sizeof(nyx_hip_event_t), hipMemcpyHostToDevice));
+        ev.ev = evdesc.as<nyx_hip_event_t>(); ev.ev_mu = ctx->host_cfg.mu_central;
+        char *base = evbuf.as<char>();
+        ev.ev_prev = (double *)(base + b[E_PREV].at); ev.ev_count = (int32_t *)(base + b[E_COUNT].at); ev.ev_found = (int32_t *)(base + b[E_FOUND].at);
+        HIP_TRY(hipMemset(evbuf.p, 0, b.total));
+        LaunchReq r;
+        r.in = &sg.din; r.out = &sg.dout; r.stats = &sg.dst; r.duration_ns = max_duration_ns; r.traj = &dtraj.t; r.ev = &ev; r.timed = true;
+        if (int rc = launch(ctx, r)) return rc;
+        EventSearchArgs a{};
+        a.traj = dtraj.t; a.n = n; a.ev = *event; a.mu = ctx->host_cfg.mu_central; a.found = ev.ev_found; a.status = sg.dst.status; a.epoch_ns = sg.dout.epoch_ns;
+        for (int c = 0; c < kCartRows; ++c) a.state[c] = sg.dout.*kStateRow[c].s;
+        HIP_TRY(nyx_launch_event_search(&a, nullptr));
+        return NYX_HIP_RC_OK;
+    }, [&]() -> int {
+        if (int rc = dtraj.download(traj)) return rc;
+        if (crossings) HIP_TRY(hipMemcpy(crossings, ev.ev_count, (size_t)in->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return NYX_HIP_RC_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1385,136 +1309,76 @@ extern "C" int32_t nyx_hip_propagate_until_event(nyx_hip_ctx *ctx, const nyx_hip
 extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_hip_predict_t *cfg,
                                          nyx_hip_estimates_t *est, nyx_hip_states_t *out, nyx_hip_step_stats_t *stats,
                                          nyx_hip_predict_history_t *hist) {
-    if (!ctx || !cfg || !est || !est->covar) { nyx_set_error("predict: ctx, cfg and est->covar are mandatory"); return NYX_HIP_RC_BAD_ARG; }
-    if (!(ctx->host_cfg.flags & NYX_HIP_FLAG_STM)) { nyx_set_error("predict: the context must be created with NYX_HIP_FLAG_STM"); return NYX_HIP_RC_BAD_ARG; }
-    if (cfg->max_step_ns <= 0) { nyx_set_error("predict: max_step_ns must be > 0"); return NYX_HIP_RC_BAD_ARG; }
-    if (cfg->n_process_noise < 0 || cfg->n_process_noise > NYX_HIP_MAX_PROCESS_NOISE) { nyx_set_error("predict: n_process_noise out of range"); return NYX_HIP_RC_BAD_ARG; }
-    for (int q = 0; q < cfg->n_process_noise; ++q)
-        if (cfg->process_noise[q].local_frame < NYX_HIP_FRAME_INERTIAL || cfg->process_noise[q].local_frame > NYX_HIP_FRAME_VNC) {
-            nyx_set_error("predict: process noise %d: local frame not on the device path (inertial, RIC, VNC)", q);
-            return NYX_HIP_RC_UNSUPPORTED;
-        }
-    if (hist && (hist->capacity < 0 || !hist->n_updates)) { nyx_set_error("predict: hist->n_updates is mandatory, capacity >= 0"); return NYX_HIP_RC_BAD_ARG; }
-    if (int rc = check_states(in, "in")) return rc;
-    if (int rc = check_states(out, "out")) return rc;
-    const int64_t n = in->n;
-    if (n == 0) return NYX_HIP_RC_OK;
-    if (out->n < n) { nyx_set_error("out batch smaller than in batch"); return NYX_HIP_RC_BAD_ARG; }
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    Staged sg;
-    if (int rc = stage_batch(ctx, in, out, sg, /*upload_stm=*/false)) return rc;
-    // segments needed: the longest trajectory decides (the others idle with duration 0)
-    int64_t n_seg = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t span = cfg->end_epoch_ns - in->epoch_ns[i];
-        if (span > 0) n_seg = std::max(n_seg, (span + cfg->max_step_ns - 1) / cfg->max_step_ns);
-    }
-    const int64_t cap = hist ? hist->capacity : 0;
-    const size_t slots = (size_t)cap * (size_t)n;
-    DevBuf covar, sdev, work, h_epoch, h_state, h_stm, h_covar, h_sdev;
-    // work: prev_epoch, dur, acc x3, init_epoch (int64) then status, n_updates (int32)
-    if (int rc = covar.alloc((size_t)n * 81 * 8)) return rc;
-    if (int rc = sdev.alloc((size_t)n * 9 * 8)) return rc;
-    if (int rc = work.alloc((size_t)n * (6 * 8 + 2 * 4))) return rc;
-    HIP_TRY(hipMemcpy(covar.p, est->covar, (size_t)n * 81 * 8, hipMemcpyHostToDevice));
-    if (est->state_dev) HIP_TRY(hipMemcpy(sdev.p, est->state_dev, (size_t)n * 9 * 8, hipMemcpyHostToDevice));
-    else HIP_TRY(hipMemset(sdev.p, 0, (size_t)n * 9 * 8));
-    PredictArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n = n; a.cfg = *cfg;
-    a.epoch = sg.dout.epoch_ns;
-    for (int k = 0; k < kMomentRows; ++k) a.s9[k] = sg.dout.*kStateRow[k].s;
-    a.seg_status = sg.dst.status; a.seg_n_acc = sg.dst.n_accepted; a.seg_n_rej = sg.dst.n_rejected; a.seg_n_evals = sg.dst.n_evals;
-    a.covar = covar.as<double>(); a.state_dev = sdev.as<double>();
-    int64_t *w64 = work.as<int64_t>();
-    a.prev_epoch = w64; a.dur = w64 + n; a.acc_n_acc = w64 + 2 * n; a.acc_n_rej = w64 + 3 * n; a.acc_n_evals = w64 + 4 * n;
-    a.init_epoch = w64 + 5 * n;
-    a.status = (int32_t *)(w64 + 6 * n); a.hist.n_updates = a.status + n;
-    a.hist.capacity = cap;
-    if (hist && slots) {
-        if (hist->epoch_ns) { if (int rc = h_epoch.alloc(slots * 8)) return rc; a.hist.epoch_ns = h_epoch.as<int64_t>(); }
-        if (hist->state) { if (int rc = h_state.alloc(slots * 9 * 8)) return rc; a.hist.state = h_state.as<double>(); }
-        if (hist->stm) { if (int rc = h_stm.alloc(slots * 81 * 8)) return rc; a.hist.stm = h_stm.as<double>(); }
-        if (hist->covar) { if (int rc = h_covar.alloc(slots * 81 * 8)) return rc; a.hist.covar = h_covar.as<double>(); }
-        if (hist->state_dev) { if (int rc = h_sdev.alloc(slots * 9 * 8)) return rc; a.hist.state_dev = h_sdev.as<double>(); }
-        // a run with fewer updates than the capacity (ragged starts, a failure) leaves its last slots unwritten, and the whole block is
-        // copied back: zeros there, as the oracle leaves them, not what the allocation held
-        if (a.hist.epoch_ns) HIP_TRY(hipMemsetAsync(a.hist.epoch_ns, 0, slots * 8, nullptr));
-        if (a.hist.state) HIP_TRY(hipMemsetAsync(a.hist.state, 0, slots * 9 * 8, nullptr));
-        if (a.hist.stm) HIP_TRY(hipMemsetAsync(a.hist.stm, 0, slots * 81 * 8, nullptr));
-        if (a.hist.covar) HIP_TRY(hipMemsetAsync(a.hist.covar, 0, slots * 81 * 8, nullptr));
-        if (a.hist.state_dev) HIP_TRY(hipMemsetAsync(a.hist.state_dev, 0, slots * 9 * 8, nullptr));
-    }
-    hipStream_t stream = nullptr;
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    // segment 0 reads the caller's states (ctx->in) with an identity STM and writes ctx->out; later segments run in place
-    a.stm = sg.din.stm;
-    HIP_TRY(nyx_launch_predict_init(&a, sg.din.epoch_ns, stream));
-    {
-        // the segment launches carry a per-trajectory duration array and are too short to calibrate on themselves: measure
-        // the column weights of their workgroup shape once per context, on the staged states (identity STM set above)
-        // (the shape of their launches, planned on a copy of the descriptor: each launch plans for itself)
+    if (Refusal r = check_predict(ctx, ctx ? ctx->host_cfg.flags : 0, cfg, est, hist)) return refused(r);
+    const nyx_hip_predict_history_t h = hist ? *hist : nyx_hip_predict_history_t{};  // (no history: every array null)
+    const nyx_hip_step_stats_t st = stats ? *stats : nyx_hip_step_stats_t{};
+    DevBuf block, pa_dev;  // the filter's working memory, one allocation (predict_block); the device copy of a fused loop's arguments
+    const auto b = predict_block(in ? in->n : 0, h);  // (used behind check_run only)
+    return host_run(ctx, in, out, stats, false, false, [&](Staged &sg) -> int {
+        const int64_t n = in->n;
+        if (int rc = block.alloc(b.total)) return rc;
+        char *base = block.as<char>();
+        HIP_TRY(hipMemcpy(base + b[P_COVAR].at, est->covar, b[P_COVAR].bytes, hipMemcpyHostToDevice));
+        if (est->state_dev) HIP_TRY(hipMemcpy(base + b[P_SDEV].at, est->state_dev, b[P_SDEV].bytes, hipMemcpyHostToDevice));
+        // zeros in the history (a run's unwritten last slots are copied back: zeros, as the oracle leaves them) and, in front of it, in the deviations of a caller who gives none
+        const size_t zero = b[est->state_dev ? P_H_EPOCH : P_SDEV].at;
+        if (b[P_STATUS].at > zero) HIP_TRY(hipMemsetAsync(base + zero, 0, b[P_STATUS].at - zero, nullptr));
+        PredictArgs a{};
+        a.n = n; a.cfg = *cfg; a.epoch = sg.dout.epoch_ns;
+        for (int k = 0; k < kMomentRows; ++k) a.s9[k] = sg.dout.*kStateRow[k].s;
+        a.seg_status = sg.dst.status; a.seg_n_acc = sg.dst.n_accepted; a.seg_n_rej = sg.dst.n_rejected; a.seg_n_evals = sg.dst.n_evals;
+        bind_predict(a, base, b);
+        a.hist.capacity = h.capacity;
+        hipStream_t stream = nullptr;
+        HIP_TRY(hipEventRecord(ctx->ev0, stream));
+        // segment 0 reads the caller's states (ctx->in) with an identity STM and writes ctx->out; later segments run in place
+        a.stm = sg.din.stm;
+        HIP_TRY(nyx_launch_predict_init(&a, sg.din.epoch_ns, stream));
+        // the segment launches are measured once per context, on the staged states (identity STM set above): see calibrates_first,
+        // launch_plan.h (the shape of their launches, planned on a copy of the descriptor: each launch plans for itself)
         const std::unique_ptr<DevCfg> dc(new DevCfg(ctx->host_cfg));
         SchedShape shape = ctx->shape;
         const LaunchPlan p = plan_launch(plan_inputs(ctx), *dc, shape, n, true);
-        const WKey key = weight_key(*dc, p.n_waves, p.quad, p.coop.run);
-        if (calibration_on(ctx) && ctx->host_cfg.has_grav && p.n_waves >= 8 && n >= 16 && !ctx->weights.count(key)) {
+        if (calibrates_first(plan_inputs(ctx), ctx->host_cfg, weight_key(*dc, p.n_waves, p.quad, p.coop.run), p.n_waves, n, /*min_n=*/16, /*plain=*/true, 0, /*min_steps=*/0)) {
             if (int rc = calibrate(ctx, &sg.din, stream)) return rc;
             HIP_TRY(hipEventRecord(ctx->ev0, stream));  // (the timed region is the segment loop, not the one-off calibration)
         }
-    }
-    a.stm = sg.dout.stm;
-    // Round 6: the whole loop in ONE launch - the workgroups stay resident, the integrator wave performs the time updates of its
-    // trajectories at every segment boundary (propagate_kernel.hip, segment_update; DevBatch.pred = a device copy of `a`).  A segment
-    // launch cost ~30 us beyond its force evaluations (tools/seg_cost.py), a fifth of BASELINE config 4's loop.  The launch-per-segment
-    // loop of rounds 2-5 stays for the integration-frame swap (translated in and out per segment, od/process/mod.rs:453-468) and as
-    // the A/B reference (debug_flags 0x20000000): same states, STMs and covariances.
-    LaunchReq seg;  // (per-trajectory durations; segment 0 reads the staged states, the later ones run in place)
-    seg.in = &sg.din; seg.out = &sg.dout; seg.stats = &sg.dst; seg.dur_ns = a.dur; seg.stream = stream;
-    DevBuf pa_dev;
-    // (quad layout only: sixteen waves share sixteen trajectories' updates; the 64-lane layout - four waves, sixty-four trajectories per
-    //  workgroup - is the large-ensemble shape, where the per-launch cost is a small share and sixteen serial updates per wave cost more:
-    //  measured 26.2 ms fused against 24.3 ms per segment at n = 1 000)
-    const bool fused = ctx->swap_n_chain == 0 && !(ctx->tune.debug_flags & 0x20000000) && pick_quad(plan_inputs(ctx), ctx->host_cfg, n);
-    if (fused) {
-        if (int rc = pa_dev.alloc(sizeof(PredictArgs))) return rc;
-        HIP_TRY(hipMemcpyAsync(pa_dev.p, &a, sizeof(PredictArgs), hipMemcpyHostToDevice, stream));
-        ctx->fused_pred = (const PredictArgs *)pa_dev.p;
-        const int rc = launch(ctx, seg);
-        ctx->fused_pred = nullptr;
-        if (rc) return rc;
-        // the kernel's counters run over the whole loop
-        HIP_TRY(hipMemcpyAsync(a.acc_n_acc, sg.dst.n_accepted, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(a.acc_n_rej, sg.dst.n_rejected, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(a.acc_n_evals, sg.dst.n_evals, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
-    } else
-    for (int64_t s = 0; s < n_seg; ++s) {
-        if (int rc = launch(ctx, seg)) return rc;
-        HIP_TRY(nyx_launch_time_update(&a, stream));
-        seg.in = &sg.dout;
-    }
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(hipDeviceSynchronize());
-    read_kernel_ms(ctx);
-    if (int rc = fetch_batch(ctx, n, true, out, stats)) return rc;
-    HIP_TRY(hipMemcpy(est->covar, covar.p, (size_t)n * 81 * 8, hipMemcpyDeviceToHost));
-    if (est->state_dev) HIP_TRY(hipMemcpy(est->state_dev, sdev.p, (size_t)n * 9 * 8, hipMemcpyDeviceToHost));
-    if (stats) {  // first failing status, counters summed over the segments
-        if (stats->status) HIP_TRY(hipMemcpy(stats->status, a.status, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (stats->n_accepted) HIP_TRY(hipMemcpy(stats->n_accepted, a.acc_n_acc, (size_t)n * 8, hipMemcpyDeviceToHost));
-        if (stats->n_rejected) HIP_TRY(hipMemcpy(stats->n_rejected, a.acc_n_rej, (size_t)n * 8, hipMemcpyDeviceToHost));
-        if (stats->n_evals) HIP_TRY(hipMemcpy(stats->n_evals, a.acc_n_evals, (size_t)n * 8, hipMemcpyDeviceToHost));
-    }
-    if (hist) {
-        HIP_TRY(hipMemcpy(hist->n_updates, a.hist.n_updates, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (a.hist.epoch_ns) HIP_TRY(hipMemcpy(hist->epoch_ns, a.hist.epoch_ns, slots * 8, hipMemcpyDeviceToHost));
-        if (a.hist.state) HIP_TRY(hipMemcpy(hist->state, a.hist.state, slots * 9 * 8, hipMemcpyDeviceToHost));
-        if (a.hist.stm) HIP_TRY(hipMemcpy(hist->stm, a.hist.stm, slots * 81 * 8, hipMemcpyDeviceToHost));
-        if (a.hist.covar) HIP_TRY(hipMemcpy(hist->covar, a.hist.covar, slots * 81 * 8, hipMemcpyDeviceToHost));
-        if (a.hist.state_dev) HIP_TRY(hipMemcpy(hist->state_dev, a.hist.state_dev, slots * 9 * 8, hipMemcpyDeviceToHost));
-    }
-    return NYX_HIP_RC_OK;
+        a.stm = sg.dout.stm;
+        // Round 6: the whole loop in ONE launch - the workgroups stay resident, the integrator wave performs the time updates of its
+        // trajectories at every segment boundary (propagate_kernel.hip, segment_update; DevBatch.pred = a device copy of `a`).  A segment
+        // launch cost ~30 us beyond its force evaluations (tools/seg_cost.py), a fifth of BASELINE config 4's loop.  The launch-per-segment
+        // loop of rounds 2-5 stays for the integration-frame swap (translated in and out per segment, od/process/mod.rs:453-468) and as
+        // the A/B reference (debug_flags 0x20000000): same states, STMs and covariances.  Which of the two: predict_fused (launch_plan.h).
+        LaunchReq seg;  // (per-trajectory durations; segment 0 reads the staged states, the later ones run in place)
+        seg.in = &sg.din; seg.out = &sg.dout; seg.stats = &sg.dst; seg.dur_ns = a.dur; seg.stream = stream;
+        if (predict_fused(plan_inputs(ctx), ctx->host_cfg, n, ctx->swap_n_chain)) {
+            if (int rc = pa_dev.alloc(sizeof(PredictArgs))) return rc;
+            HIP_TRY(hipMemcpyAsync(pa_dev.p, &a, sizeof(PredictArgs), hipMemcpyHostToDevice, stream));
+            ctx->fused_pred = (const PredictArgs *)pa_dev.p;
+            const int rc = launch(ctx, seg);
+            ctx->fused_pred = nullptr;
+            if (rc) return rc;
+            // the kernel's counters run over the whole loop
+            HIP_TRY(hipMemcpyAsync(a.acc_n_acc, sg.dst.n_accepted, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(a.acc_n_rej, sg.dst.n_rejected, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(a.acc_n_evals, sg.dst.n_evals, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
+        } else
+        for (int64_t s = predict_segments(in->epoch_ns, n, cfg->end_epoch_ns, cfg->max_step_ns); s > 0; --s) {
+            if (int rc = launch(ctx, seg)) return rc;
+            HIP_TRY(nyx_launch_time_update(&a, stream));
+            seg.in = &sg.dout;
+        }
+        HIP_TRY(hipEventRecord(ctx->ev1, stream));
+        return NYX_HIP_RC_OK;
+    }, [&]() -> int {
+        // after the fetch of the last segment's stats: the first failing status, the summed counters; every part the caller asked for
+        const struct { void *host; int part; } back[] = {
+            {est->covar, P_COVAR}, {est->state_dev, P_SDEV}, {st.status, P_STATUS}, {st.n_accepted, P_ACC_N_ACC}, {st.n_rejected, P_ACC_N_REJ}, {st.n_evals, P_ACC_N_EVALS},
+            {h.n_updates, P_N_UPDATES}, {h.epoch_ns, P_H_EPOCH}, {h.state, P_H_STATE}, {h.stm, P_H_STM}, {h.covar, P_H_COVAR}, {h.state_dev, P_H_SDEV}};
+        for (const auto &c : back)
+            if (c.host && b[c.part].bytes) HIP_TRY(hipMemcpy(c.host, block.as<char>() + b[c.part].at, b[c.part].bytes, hipMemcpyDeviceToHost));
+        return NYX_HIP_RC_OK;
+    });
 }
 
 // Introspection for tests / DESIGN.md: rows per wave of the SOLO column schedule an n_waves workgroup of this context would walk.

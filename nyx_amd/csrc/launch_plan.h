@@ -646,6 +646,22 @@ inline bool pick_quad(const PlanInputs &in, const DevCfg &dc, int64_t n) {
     return (n + 15) / 16 <= 2 * cus;
 }
 
+// Whether the covariance-mapping loop of n trajectories (nyx_hip_predict_until) runs in ONE launch.  Quad layout only: sixteen waves
+// share sixteen trajectories' updates; in the 64-lane layout, the large-ensemble shape, the per-launch cost is a small share and sixteen
+// serial updates per wave cost more (26.2 ms fused against 24.3 ms per segment at n = 1 000).  Not with an integration-frame swap
+// (translated in and out per segment); debug_flags 0x20000000 keeps the launch per segment as the A/B reference.
+inline bool predict_fused(const PlanInputs &in, const DevCfg &dc, int64_t n, int swap_n_chain) {
+    return swap_n_chain == 0 && !(in.tune.debug_flags & 0x20000000) && pick_quad(in, dc, n);
+}
+// Whether the column weights of a workgroup shape (`key`, `n_waves` waves) are measured on the device before n trajectories are
+// launched with it.  The two callers differ on purpose.  A launch measures on its own first steps: a plain request only (`plain`: no
+// calibration launch itself, no dense output, per-trajectory durations or stop condition), min_n 64, min_steps 100 initial steps.  The
+// segment launches of a covariance-mapping loop carry a per-trajectory duration array and are too short to calibrate on themselves:
+// their shape is measured once before the loop, whatever the span (min_steps 0), from one quad workgroup on (min_n 16).
+inline bool calibrates_first(const PlanInputs &in, const DevCfg &dc, const WKey &key, int n_waves, int64_t n, int64_t min_n, bool plain, int64_t span_ns, int64_t min_steps) {
+    return plain && in.tune.schedule == NYX_HIP_SCHED_CALIBRATED && dc.has_grav && n_waves >= 8 && n >= min_n && span_ns >= min_steps * dc.init_step_ns && !in.weights.count(key);
+}
+
 inline int pick_waves(const PlanInputs &in, const DevCfg &dc, int64_t n) {
     const bool stm = (dc.flags & NYX_HIP_FLAG_STM) != 0;
     if (stm && pick_quad(in, dc, n)) {  // quad layout: 128 VGPRs per wave like the plain kernel
