@@ -315,6 +315,25 @@ class GtQuery(C.Structure):
                 ("frame_eq_radius_km", C.c_double), ("frame_flattening", C.c_double), ("frame", Rotation)]
 
 
+# ---- include/nyx_hip_aer.h (station views: azimuth / elevation / range / range rate of an ensemble from ground stations) ----
+AER_VERSION = 1
+MAX_AER_PARAMS = 8
+MAX_STATIONS = 16
+# enum nyx_hip_aer_param: the members of stations.AerParameter, by name
+AER_PARAM = {"Azimuth": 0, "Elevation": 1, "Range": 2, "RangeRate": 3, "ElevationAboveMask": 4, "Visible": 5, "RhoS": 6, "RhoE": 7, "RhoZ": 8}
+
+
+class Station(C.Structure):
+    _fields_ = [("latitude_deg", C.c_double), ("longitude_deg", C.c_double), ("height_km", C.c_double), ("elevation_mask_deg", C.c_double)]
+
+
+class AerQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("param", C.c_int32 * MAX_AER_PARAMS), ("has_window", C.c_int32), ("step_ns", C.c_int64),
+                ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("has_frame", C.c_int32), ("_pad", C.c_int32),
+                ("frame_eq_radius_km", C.c_double), ("frame_flattening", C.c_double), ("frame", Rotation), ("n_stations", C.c_int32),
+                ("_pad2", C.c_int32), ("stations", Station * MAX_STATIONS)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -475,6 +494,9 @@ RIC_EXPORTS = ["nyx_hip_traj_ric_diff", "nyx_hip_traj_ric_diff_device", "nyx_hip
 # the entries of include/nyx_hip_groundtrack.h, likewise
 GROUNDTRACK_EXPORTS = ["nyx_hip_traj_ground_track", "nyx_hip_traj_ground_track_device", "nyx_hip_groundtrack_sizeof"]
 
+# the entries of include/nyx_hip_aer.h, likewise
+AER_EXPORTS = ["nyx_hip_traj_aer", "nyx_hip_traj_aer_device", "nyx_hip_aer_sizeof"]
+
 
 def load_library():
     """dlopen the in-tree HIP extension.  No CPU fallback: a missing build is an error."""
@@ -565,6 +587,14 @@ def load_library():
         lib.nyx_hip_traj_ground_track_device.restype = C.c_int32
         lib.nyx_hip_groundtrack_sizeof.argtypes = [C.c_int32]
         lib.nyx_hip_groundtrack_sizeof.restype = C.c_int32
+    if getattr(lib, "nyx_hip_traj_aer", None) is not None:   # (absent from a library built before the station views)
+        lib.nyx_hip_traj_aer.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(AerQuery), C.c_int64, c_double_p, c_int32_p]
+        lib.nyx_hip_traj_aer.restype = C.c_int32
+        lib.nyx_hip_traj_aer_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(AerQuery), C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
+        lib.nyx_hip_traj_aer_device.restype = C.c_int32
+        lib.nyx_hip_aer_sizeof.argtypes = [C.c_int32]
+        lib.nyx_hip_aer_sizeof.restype = C.c_int32
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -576,6 +606,15 @@ def ground_track_entry(lib, name: str = "nyx_hip_traj_ground_track"):
     fn = getattr(lib, name, None)
     if fn is None:
         raise RuntimeError(f"{lib_path()} has no {name}: it was built before the ground tracks were added - rebuild the HIP extension "
+                           "(python -c 'import __graft_entry__ as g; g.build()')")
+    return fn
+
+
+def aer_entry(lib, name: str = "nyx_hip_traj_aer"):
+    """An entry of include/nyx_hip_aer.h, or a clear error when the loaded library predates it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the station views were added - rebuild the HIP extension "
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     return fn
 

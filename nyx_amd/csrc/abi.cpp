@@ -29,6 +29,7 @@
 #include "moments_args.h"
 #include "report_args.h"
 #include "ric_args.h"
+#include "aer_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
 #include "run_host.h"
@@ -41,6 +42,7 @@ extern "C" hipError_t nyx_launch_traj_eval(const TrajEvalArgs *args, hipStream_t
 extern "C" hipError_t nyx_launch_traj_values(const ValuesArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_ric_diff(const RicArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_traj_aer(const AerArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1222,6 +1224,42 @@ extern "C" int32_t nyx_hip_traj_ground_track(nyx_hip_ctx *ctx, const nyx_hip_tra
     return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "ground-track",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_ground_track_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
+                       });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Station views (include/nyx_hip_aer.h): aer_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_aer_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_aer_query_t);
+    case 1: return NYX_HIP_AER_VERSION;
+    case 2: return NYX_HIP_AER_COUNT;
+    case 3: return NYX_HIP_MAX_AER_PARAMS;
+    case 4: return NYX_HIP_MAX_STATIONS;
+    default: return -1;
+    }
+}
+
+extern "C" int32_t nyx_hip_traj_aer_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_aer_query_t *q, int64_t capacity,
+                                           double *values, int32_t *len, void *hip_stream) {
+    if (Refusal r = check_aer_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    AerArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_traj_aer(&a, stream); });
+}
+
+extern "C" int32_t nyx_hip_traj_aer(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_aer_query_t *q, int64_t capacity,
+                                    double *values, int32_t *len) {
+    if (Refusal r = check_aer_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    return series_host(ctx, traj, n, nullptr, 0, (int64_t)q->n_stations * q->n_params, capacity, {values, len, nullptr, nullptr}, "station-view",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
+                           return nyx_hip_traj_aer_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
 }
 

@@ -1,13 +1,15 @@
-// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the four series kernels,
-// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the three fused reports (values, ground track, RIC) refuse, the
+// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the five series kernels,
+// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the four fused reports (values, ground track, station views, RIC) refuse, the
 // one output block of a report's host flavour, and the chunks of consecutive samples a launch cuts a span into.
 #pragma once
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
+#include "aer_args.h"
 #include "groundtrack_args.h"
 #include "report_args.h"
 #include "ric_args.h"
@@ -111,6 +113,32 @@ inline Refusal check_gt_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *tra
     return series_outputs(name, values, len);
 }
 
+inline Refusal check_aer_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_aer_query_t *q,
+                                int64_t capacity, const double *values, const int32_t *len) {
+    const char *name = "traj_aer";
+    int32_t need = 0;
+    if (Refusal r = series_open(name, ctx, traj, false, nullptr, q, n)) return r;
+    if (Refusal r = series_params(name, *q, NYX_HIP_MAX_AER_PARAMS, aer_param_needs, "nyx_hip_aer_param", &need)) return r;
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    if (q->n_stations < 1 || q->n_stations > NYX_HIP_MAX_STATIONS)
+        return bad_arg("%s: n_stations = %d, 1 .. %d stations per call", name, q->n_stations, NYX_HIP_MAX_STATIONS);
+    for (int s = 0; s < q->n_stations; ++s) {
+        const nyx_hip_station_t &st = q->stations[s];
+        if (!(st.latitude_deg >= -90.0 && st.latitude_deg <= 90.0)) return bad_arg("%s: stations[%d].latitude_deg must be in [-90, 90]", name, s);
+        if (!std::isfinite(st.longitude_deg)) return bad_arg("%s: stations[%d].longitude_deg must be finite", name, s);
+        if (!std::isfinite(st.height_km)) return bad_arg("%s: stations[%d].height_km must be finite", name, s);
+        if (!(st.elevation_mask_deg >= -90.0 && st.elevation_mask_deg <= 90.0))
+            return bad_arg("%s: stations[%d].elevation_mask_deg must be in [-90, 90]", name, s);
+    }
+    if (q->frame.kind != NYX_HIP_ROT_IAU)
+        return bad_arg("%s: frame.kind = %d, the frame must be an IAU-oriented frame (NYX_HIP_ROT_IAU)", name, q->frame.kind);
+    if (q->frame.n_nut_prec < 0 || q->frame.n_nut_prec > NYX_HIP_MAX_NUT_PREC)
+        return bad_arg("%s: frame.n_nut_prec = %d, 0 .. %d terms", name, q->frame.n_nut_prec, NYX_HIP_MAX_NUT_PREC);
+    if (!(q->frame_eq_radius_km > 0.0)) return bad_arg("%s: the stations stand on the ellipsoid, frame_eq_radius_km must be > 0", name);
+    if (!(q->frame_flattening >= 0.0 && q->frame_flattening < 1.0)) return bad_arg("%s: frame_flattening must be in [0, 1)", name);
+    return series_outputs(name, values, len);
+}
+
 // (epoch0_ns and moments are optional)
 inline Refusal check_ric_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
                                 const nyx_hip_ric_query_t *q, int64_t capacity, const double *values, const int32_t *len) {
@@ -126,7 +154,8 @@ inline Refusal check_ric_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *tr
     return series_outputs(name, values, len);
 }
 
-// ---- the one output block of a report's host flavour: values[n_params][capacity][n], then the optional moments
+// ---- the one output block of a report's host flavour: values[n_params][capacity][n] (station views: one row per station and
+// parameter), then the optional moments
 // [capacity][NYX_HIP_RIC_MOMENTS] and first epochs [n], then len[n].  Offsets and sizes in bytes; an absent part has size 0.
 struct SeriesBlock { size_t values_at, values, moments_at, moments, epoch0_at, epoch0, len_at, len, total; };
 inline SeriesBlock series_block(int64_t n_params, int64_t capacity, int64_t n, bool moments, bool epoch0) {

@@ -30,6 +30,7 @@ from . import _abi
 from .rng import Pcg64Mcg
 from .params import FRAME_OF, StateError, StateParameter, ric_difference, smooth_ric, state_value
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, body_fixed_value, check_frame, to_body_fixed
+from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations, sez_value, station_consts
 from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
@@ -278,6 +279,49 @@ class GroundTrackSeries:
     def of(self, param) -> np.ndarray:
         """values[K, runs] of one parameter."""
         return self.values[self.params.index(param)]
+
+
+@dataclass
+class AerSeries:
+    """`Results.station_views`: sample k of run j (position in `Results.runs`) of parameter p seen from station s is
+    `values[s, p, k, j]`, taken at `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid (the same for every station), the
+    slots after them NaN.  A failed run (`ok[j]` False) is a column of NaN with len 0: an empty series."""
+
+    stations: list
+    params: list
+    values: np.ndarray      # [S, P, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+
+    def epochs(self, j: int) -> np.ndarray:
+        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+    def of(self, station, param) -> np.ndarray:
+        """values[K, runs] of one parameter seen from one station (a GroundStation of `stations`, or its position)."""
+        return self.values[self._station(station), self.params.index(param)]
+
+    def _station(self, station) -> int:
+        return int(station) if isinstance(station, (int, np.integer)) else [st is station for st in self.stations].index(True)
+
+    def visible_fraction(self, station) -> np.ndarray:
+        """[K]: per sample, the share of the runs HOLDING that sample (k < len[j]) whose elevation is at or above the mask of
+        `station` (a GroundStation of `stations`, or its position); NaN where no run holds the sample.  Formed on the host from
+        `Visible`, or from `ElevationAboveMask` / `Elevation` when that is what the series holds."""
+        s = self._station(station)
+        if AerParameter.Visible in self.params:
+            seen = self.values[s, self.params.index(AerParameter.Visible)] > 0.0
+        elif AerParameter.ElevationAboveMask in self.params:
+            seen = self.values[s, self.params.index(AerParameter.ElevationAboveMask)] >= 0.0
+        elif AerParameter.Elevation in self.params:
+            seen = self.values[s, self.params.index(AerParameter.Elevation)] - float(self.stations[s].elevation_mask_deg) >= 0.0
+        else:
+            raise ValueError("visible_fraction: the series holds none of Visible, ElevationAboveMask and Elevation")
+        held = np.arange(self.values.shape[2])[:, None] < self.len[None, :].astype(np.int64)
+        count = held.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (seen & held).sum(axis=1) / np.where(count > 0, count, np.nan)
 
 
 def _fill_head(head: np.ndarray, k: int, n_k: int, first_epoch_ns) -> None:
@@ -696,6 +740,62 @@ class Results:
             err = e
         values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), np.nan)
         return GroundTrackSeries(params, values, length, epoch0, step, ok, frame)
+
+    def station_views(self, stations, step_ns: int, params=AER_DEFAULT, start_ns: Optional[int] = None,
+                      end_ns: Optional[int] = None) -> "AerSeries":
+        """What every one of `stations` (GroundStation, all of one IAU-oriented frame of the runs' centre) sees of the ensemble:
+        `params` (AerParameter members; by default azimuth, elevation, range and range rate, what
+        `MeasurementType::compute_one_way` reads, od/msr/types.rs:102-117) of every run every `step_ns`, from the start to the
+        end of its trajectory or between max(start, first epoch) and min(end, last epoch) when a window is given -> AerSeries.
+        The geometry of `GroundStation::azimuth_elevation_of` only: no noise, no light time, no measurement update.
+
+        With a device evaluator one fused launch per eight parameters and sixteen stations (`traj_aer`: resampled, rotated at
+        each sample's epoch - once for all stations -, evaluated; only the values copied back).  A failed run is a column of NaN
+        with len 0.  Sharded ensemble: a collective call, every rank reports the runs it propagated and the columns are gathered
+        in index order.  An evaluator without `traj_aer` (the injected CPU evaluators of the tests) is served by `traj_every` /
+        `traj_at` + `stations.aer_value`: that composition is the definition, the device path is tested against it."""
+        stations, params = list(stations), list(params)
+        step = int(step_ns)
+        rows_out = len(stations) * len(params)
+        runs = self._local_runs()
+        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
+        cols = [None] * len(runs)                            # values[S * P, len] of every successful run
+        err = None
+        try:
+            if (start_ns is None) != (end_ns is None):
+                raise ValueError("station_views: a window needs both start_ns and end_ns")
+            if step <= 0:
+                raise ValueError("station_views: a positive step")
+            for p in params:
+                if not isinstance(p, AerParameter):
+                    raise TypeError(f"{p!r} is not an AerParameter")
+            if not params:
+                raise ValueError("station_views: at least one parameter")
+            central = getattr(getattr(self._traj_ctx, "compiled", None), "central", None)
+            frame = check_stations(stations, central.naif_id if central is not None else None)
+            self._need_traj()
+            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
+            rows = [self._traj_rows[runs[k].index] for k in ok]
+            tb = self._traj_batch
+            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
+            if ok and hasattr(self._traj_ctx, "traj_aer"):
+                vals, length = self._traj_ctx.traj_aer(tb, stations, params, step, start_ns, end_ns)
+                for k, row in zip(ok, rows):
+                    m = min(int(length[row]), vals.shape[2])
+                    cols[k] = vals[:, :, :m, row].reshape(rows_out, m)
+            elif ok:
+                consts = [station_consts(st) for st in stations]
+                res = self._every_batch(step) if start_ns is None else None
+                for k, row in zip(ok, rows):
+                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(runs[k], step, start_ns, end_ns)
+                    yf = to_body_fixed(rv, int(first[row]) + step * np.arange(len(rv), dtype=np.int64), frame)
+                    cols[k] = np.stack([sez_value(p, yf, c) for c in consts for p in params]).reshape(rows_out, len(rv))
+            for k, row in zip(ok, rows):
+                _fill_head(head, k, cols[k].shape[1], first[row])
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
+            err = e
+        values, length, epoch0, ok, k_max, _ = self._gather_series(err, head, cols, rows_out, np.nan)
+        return AerSeries(stations, params, values.reshape(len(stations), len(params), k_max, values.shape[2]), length, epoch0, step, ok)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

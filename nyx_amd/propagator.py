@@ -31,6 +31,7 @@ import numpy as np
 from . import _abi
 from .params import FRAME_OF, StateError, StateParameter
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, check_frame
+from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -845,6 +846,50 @@ class GpuContext:
         return _param_series("traj_ground_track", fn, self._h, _abi.GtQuery, _abi.MAX_GT_PARAMS, lambda q: fill_gt_frame(q, frame), traj, codes,
                                   step_ns, start_ns, end_ns, capacity)
 
+    def traj_aer(self, traj: _abi.TrajBatch, stations, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                 capacity: Optional[int] = None):
+        """``nyx_hip_traj_aer`` (include/nyx_hip_aer.h): the `params` (AerParameter members) of every trajectory of the batch seen
+        from every one of `stations` (GroundStation, all of one IAU-oriented frame of the context's centre) every `step_ns` -
+        `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given - resampled, expressed in the stations' frame
+        at each sample's epoch and evaluated on the device in one pass, one interpolation and one rotation per sample serving all
+        stations: (values[S, P, capacity, n], len[n]).  `len[i]` counts the samples produced for trajectory i (the same for every
+        station); slots from `len[i]` on are NaN.  `capacity=None` sizes the series from the batch's epochs.  More than eight
+        parameters or sixteen stations take several launches."""
+        fn = _abi.aer_entry(self._lib)
+        stations, params = list(stations), list(params)
+        codes = [aer_param_code(p) for p in params]
+        if not codes:
+            raise ValueError("traj_aer: at least one parameter")
+        frame = check_stations(stations, self.compiled.central.naif_id)
+        if (start_ns is None) != (end_ns is None):
+            raise ValueError("traj_aer: a window needs both start_ns and end_ns")
+        cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
+        values = np.empty((len(stations), len(codes), max(cap, 0), traj.n), dtype=np.float64)
+        length = np.zeros(traj.n, dtype=np.int32)
+        cin = traj.as_c()
+        for s0 in range(0, len(stations), _abi.MAX_STATIONS):
+            group = stations[s0:s0 + _abi.MAX_STATIONS]
+            for p0 in range(0, len(codes), _abi.MAX_AER_PARAMS):
+                chunk = codes[p0:p0 + _abi.MAX_AER_PARAMS]
+                q = _abi.AerQuery()
+                q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
+                q.param[:len(chunk)] = chunk
+                if start_ns is not None:
+                    q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+                fill_gt_frame(q, frame)
+                q.n_stations = len(group)
+                for k, st in enumerate(group):
+                    q.stations[k].latitude_deg, q.stations[k].longitude_deg = float(st.latitude_deg), float(st.longitude_deg)
+                    q.stations[k].height_km, q.stations[k].elevation_mask_deg = float(st.height_km), float(st.elevation_mask_deg)
+                whole = len(chunk) == len(codes)
+                part = values[s0:s0 + len(group)] if whole else np.empty((len(group), len(chunk), max(cap, 0), traj.n))   # (contiguous: in place)
+                rc = fn(self._h, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
+                if rc != 0:
+                    raise RuntimeError(f"nyx_hip_traj_aer failed (rc={rc}): {_abi.last_error()}")
+                if not whole:
+                    values[s0:s0 + len(group), p0:p0 + len(chunk)] = part
+        return values, length
+
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                       capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
         """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
@@ -925,8 +970,16 @@ def gt_param_code(param) -> int:
     return _abi.GT_PARAM[param.name]
 
 
-def fill_gt_frame(q: "_abi.GtQuery", frame: "Frame") -> None:
-    """The frame fields of a ground-track query from a `Frame`, as `Event.as_c` fills those of an event."""
+def aer_param_code(param) -> int:
+    """enum nyx_hip_aer_param of an AerParameter."""
+    if not isinstance(param, AerParameter):
+        raise TypeError(f"{param!r} is not an AerParameter")
+    return _abi.AER_PARAM[param.name]
+
+
+def fill_gt_frame(q, frame: "Frame") -> None:
+    """The frame fields of a ground-track or station-view query (`_abi.GtQuery`, `_abi.AerQuery`) from a `Frame`, as `Event.as_c` fills
+    those of an event."""
     rot = frame.rotation or Rotation()
     if rot.euler is not None:
         raise NotImplementedError("ground-track frames are IAU-oriented frames on the device path")
@@ -1200,6 +1253,16 @@ class Traj:
         k = int(length[0])
         lo, _ = series_bounds(self._single(), start_ns, end_ns)
         return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
+
+    def station_view(self, stations, step_ns: int, params=AER_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+        """(epochs[K], values[S, P, K]) of this trajectory seen from `stations` (GroundStation, all of one frame) every `step_ns`
+        (between `start_ns` and `end_ns` when given): by default azimuth, elevation, range and range rate - what
+        `TrackingDevice::measure_instantaneous` reads (trk_device.rs:158-208), without noise or light time -, resampled, rotated at
+        each sample's epoch and evaluated on the device (GpuContext.traj_aer)."""
+        values, length = self._ctx.traj_aer(self._single(), list(stations), list(params), int(step_ns), start_ns, end_ns)
+        k = int(length[0])
+        lo, _ = series_bounds(self._single(), start_ns, end_ns)
+        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :, :k, 0].copy()
 
     def ric_diff(self, other: "Traj", step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="run",
                  transport: bool = True, smooth_window: int = 5):

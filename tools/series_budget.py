@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""The code-object fences of the three fused trajectory reports - the report kernels (report_kernel.hip), the RIC kernels
-(ric_kernel.hip) and the ground-track kernels (groundtrack_kernel.hip): what tests/test_report_budget.py, tests/test_ric_budget.py
-and tests/test_groundtrack_budget.py measure on the built library, and the tool that writes the committed budgets:
-`python tools/series_budget.py FAMILY --update [slack]` (FAMILY = report, ric or groundtrack) = measured figures x (1 + slack,
+"""The code-object fences of the four fused trajectory reports - the report kernels (report_kernel.hip), the RIC kernels
+(ric_kernel.hip), the ground-track kernels (groundtrack_kernel.hip) and the station-view kernels (aer_kernel.hip): what
+tests/test_report_budget.py, tests/test_ric_budget.py, tests/test_groundtrack_budget.py and tests/test_aer_budget.py measure on the
+built library, and the tool that writes the committed budgets:
+`python tools/series_budget.py FAMILY --update [slack]` (FAMILY = report, ric, groundtrack or aer) = measured figures x (1 + slack,
 default 0.08), to be run - and its diff read - when a change of those kernels is INTENDED to move them.  Same figures and rules as
 tools/code_budget.py; each family carries a kernel-name prefix and a budget file of its own."""
 import json
@@ -14,7 +15,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import code_budget  # noqa: E402
 import kernel_meta  # noqa: E402
 
-FAMILIES = {"report": ("nyxrep_", "report_budget.json"), "ric": ("nyxric_", "ric_budget.json"), "groundtrack": ("nyxgt_", "groundtrack_budget.json")}
+FAMILIES = {"report": ("nyxrep_", "report_budget.json"), "ric": ("nyxric_", "ric_budget.json"), "groundtrack": ("nyxgt_", "groundtrack_budget.json"),
+            "aer": ("nyxaer_", "aer_budget.json")}
 
 
 def measure(lib, family):
