@@ -334,6 +334,27 @@ class AerQuery(C.Structure):
                 ("_pad2", C.c_int32), ("stations", Station * MAX_STATIONS)]
 
 
+# ---- include/nyx_hip_eclipse.h (eclipses: how much of the light source every run of an ensemble sees) ----
+ECL_VERSION = 1
+MAX_ECL_PARAMS = 8
+MAX_ECL_BODIES = 8
+# enum nyx_hip_ecl_param: the members of eclipse.EclipseParameter, by name
+ECL_PARAM = {"Occultation": 0, "Illumination": 1, "State": 2, "EclipsingBody": 3, "SunRange": 4, "SunApparentRadius": 5, "BodyOccultation": 6,
+             "BodyApparentRadius": 7, "BodySeparation": 8, "BodyPenumbraMargin": 9, "BodyUmbraMargin": 10}
+ECL_FIRST_PER_BODY = 6
+
+
+class EclBody(C.Structure):
+    _fields_ = [("n_chain", C.c_int32), ("chain_segment", C.c_int32 * MAX_CHAIN), ("chain_sign", C.c_int32 * MAX_CHAIN), ("_pad", C.c_int32),
+                ("mean_radius_km", C.c_double)]
+
+
+class EclQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("param", C.c_int32 * MAX_ECL_PARAMS), ("param_body", C.c_int32 * MAX_ECL_PARAMS), ("has_window", C.c_int32),
+                ("step_ns", C.c_int64), ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("light", EclBody), ("n_bodies", C.c_int32),
+                ("_pad", C.c_int32), ("bodies", EclBody * MAX_ECL_BODIES)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -497,6 +518,9 @@ GROUNDTRACK_EXPORTS = ["nyx_hip_traj_ground_track", "nyx_hip_traj_ground_track_d
 # the entries of include/nyx_hip_aer.h, likewise
 AER_EXPORTS = ["nyx_hip_traj_aer", "nyx_hip_traj_aer_device", "nyx_hip_aer_sizeof"]
 
+# the entries of include/nyx_hip_eclipse.h, likewise
+ECLIPSE_EXPORTS = ["nyx_hip_traj_eclipse", "nyx_hip_traj_eclipse_device", "nyx_hip_ecl_sizeof"]
+
 
 def load_library():
     """dlopen the in-tree HIP extension.  No CPU fallback: a missing build is an error."""
@@ -595,6 +619,16 @@ def load_library():
         lib.nyx_hip_traj_aer_device.restype = C.c_int32
         lib.nyx_hip_aer_sizeof.argtypes = [C.c_int32]
         lib.nyx_hip_aer_sizeof.restype = C.c_int32
+    if getattr(lib, "nyx_hip_traj_eclipse", None) is not None:   # (absent from a library built before the eclipses)
+        lib.nyx_hip_traj_eclipse.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(EclQuery), C.c_int64, c_double_p, c_int32_p]
+        lib.nyx_hip_traj_eclipse.restype = C.c_int32
+        lib.nyx_hip_traj_eclipse_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(EclQuery), C.c_int64, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
+        lib.nyx_hip_traj_eclipse_device.restype = C.c_int32
+        lib.nyx_hip_ecl_sizeof.argtypes = [C.c_int32]
+        lib.nyx_hip_ecl_sizeof.restype = C.c_int32
+        if lib.nyx_hip_ecl_sizeof(0) != C.sizeof(EclQuery) or lib.nyx_hip_ecl_sizeof(5) != C.sizeof(EclBody):
+            raise RuntimeError(f"{lib_path()}: nyx_hip_ecl_query_t is {lib.nyx_hip_ecl_sizeof(0)} bytes, the ctypes mirror {C.sizeof(EclQuery)}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -615,6 +649,15 @@ def aer_entry(lib, name: str = "nyx_hip_traj_aer"):
     fn = getattr(lib, name, None)
     if fn is None:
         raise RuntimeError(f"{lib_path()} has no {name}: it was built before the station views were added - rebuild the HIP extension "
+                           "(python -c 'import __graft_entry__ as g; g.build()')")
+    return fn
+
+
+def eclipse_entry(lib, name: str = "nyx_hip_traj_eclipse"):
+    """An entry of include/nyx_hip_eclipse.h, or a clear error when the loaded library predates it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the eclipses were added - rebuild the HIP extension "
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     return fn
 

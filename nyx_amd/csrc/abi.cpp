@@ -30,6 +30,7 @@
 #include "report_args.h"
 #include "ric_args.h"
 #include "aer_args.h"
+#include "eclipse_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
 #include "run_host.h"
@@ -43,6 +44,7 @@ extern "C" hipError_t nyx_launch_traj_values(const ValuesArgs *args, hipStream_t
 extern "C" hipError_t nyx_launch_ric_diff(const RicArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_aer(const AerArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_traj_eclipse(const EclArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1260,6 +1262,52 @@ extern "C" int32_t nyx_hip_traj_aer(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj
     return series_host(ctx, traj, n, nullptr, 0, (int64_t)q->n_stations * q->n_params, capacity, {values, len, nullptr, nullptr}, "station-view",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_aer_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
+                       });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Eclipses (include/nyx_hip_eclipse.h): eclipse_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_ecl_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_ecl_query_t);
+    case 1: return NYX_HIP_ECL_VERSION;
+    case 2: return NYX_HIP_ECL_COUNT;
+    case 3: return NYX_HIP_MAX_ECL_PARAMS;
+    case 4: return NYX_HIP_MAX_ECL_BODIES;
+    case 5: return (int32_t)sizeof(nyx_hip_ecl_body_t);
+    default: return -1;
+    }
+}
+
+// check_ecl_series never reads the context (a refusal of the query alone is given for any context pointer); what the query asks of
+// the context - its segments, no integration-frame swap - is checked behind it
+static Refusal check_ecl(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_ecl_query_t *q, int64_t capacity,
+                         const double *values, const int32_t *len) {
+    if (Refusal r = check_ecl_series(ctx, traj, n, q, capacity, values, len)) return r;
+    return check_ecl_context(*q, ctx->host_cfg.n_seg, ctx->swap_n_chain != 0);
+}
+
+extern "C" int32_t nyx_hip_traj_eclipse_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_ecl_query_t *q, int64_t capacity,
+                                               double *values, int32_t *len, void *hip_stream) {
+    if (Refusal r = check_ecl(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    EclArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    a.records = ctx->d_records;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_traj_eclipse(&a, ctx->host_cfg.seg, stream); });
+}
+
+extern "C" int32_t nyx_hip_traj_eclipse(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_ecl_query_t *q, int64_t capacity,
+                                        double *values, int32_t *len) {
+    if (Refusal r = check_ecl(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "eclipse",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
+                           return nyx_hip_traj_eclipse_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
 }
 

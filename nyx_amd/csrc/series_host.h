@@ -1,5 +1,5 @@
-// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the five series kernels,
-// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the four fused reports (values, ground track, station views, RIC) refuse, the
+// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the six series kernels,
+// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the five fused reports (values, ground track, station views, eclipses, RIC) refuse, the
 // one output block of a report's host flavour, and the chunks of consecutive samples a launch cuts a span into.
 #pragma once
 #include <climits>
@@ -10,6 +10,7 @@
 #include <cstdio>
 
 #include "aer_args.h"
+#include "eclipse_args.h"
 #include "groundtrack_args.h"
 #include "report_args.h"
 #include "ric_args.h"
@@ -137,6 +138,64 @@ inline Refusal check_aer_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *tr
     if (!(q->frame_eq_radius_km > 0.0)) return bad_arg("%s: the stations stand on the ellipsoid, frame_eq_radius_km must be > 0", name);
     if (!(q->frame_flattening >= 0.0 && q->frame_flattening < 1.0)) return bad_arg("%s: frame_flattening must be in [0, 1)", name);
     return series_outputs(name, values, len);
+}
+
+// The eclipses are checked in two steps.  check_ecl_series is what its siblings are - it never dereferences the context - and
+// refuses everything that can be told from the query alone.  check_ecl_context is what the query asks OF the context, checked once the
+// query itself is sound: every chain segment is one of the context's `n_seg` (DevCfg.n_seg), and the context was not built with an
+// integration-frame swap (`frame_swapped`: state_frame_body != 0) - the one refusal that is not a bad argument.
+inline const char *ecl_body_name(char (&who)[32], const char *which, int index) {
+    if (index < 0) std::snprintf(who, sizeof who, "%s", which);
+    else std::snprintf(who, sizeof who, "%s[%d]", which, index);
+    return who;
+}
+inline Refusal check_ecl_body(const char *name, const char *which, int index, const nyx_hip_ecl_body_t &b, int min_chain) {
+    char who[32];
+    ecl_body_name(who, which, index);
+    if (b.n_chain < min_chain || b.n_chain > NYX_HIP_MAX_CHAIN)
+        return bad_arg("%s: %s.n_chain = %d, %d .. %d segments", name, who, b.n_chain, min_chain, NYX_HIP_MAX_CHAIN);
+    for (int k = 0; k < b.n_chain; ++k) {
+        if (b.chain_segment[k] < 0) return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context", name, who, k, b.chain_segment[k]);
+        if (b.chain_sign[k] != 1 && b.chain_sign[k] != -1) return bad_arg("%s: %s.chain_sign[%d] = %d, +1 or -1", name, who, k, b.chain_sign[k]);
+    }
+    if (!(std::isfinite(b.mean_radius_km) && b.mean_radius_km > 0.0)) return bad_arg("%s: %s.mean_radius_km must be finite and > 0", name, who);
+    return {};
+}
+inline Refusal check_ecl_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_ecl_query_t *q, int64_t capacity,
+                                const double *values, const int32_t *len) {
+    const char *name = "traj_eclipse";
+    int32_t need = 0;
+    if (Refusal r = series_open(name, ctx, traj, false, nullptr, q, n)) return r;
+    if (Refusal r = series_params(name, *q, NYX_HIP_MAX_ECL_PARAMS, ecl_param_needs, "nyx_hip_ecl_param", &need)) return r;
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    if (q->n_bodies < 1 || q->n_bodies > NYX_HIP_MAX_ECL_BODIES)
+        return bad_arg("%s: n_bodies = %d, 1 .. %d shadow bodies per call", name, q->n_bodies, NYX_HIP_MAX_ECL_BODIES);
+    if (Refusal r = check_ecl_body(name, "light", -1, q->light, 1)) return r;
+    for (int b = 0; b < q->n_bodies; ++b)
+        if (Refusal r = check_ecl_body(name, "bodies", b, q->bodies[b], 0)) return r;
+    for (int p = 0; p < q->n_params; ++p)
+        if (ecl_param_per_body(q->param[p]) && (q->param_body[p] < 0 || q->param_body[p] >= q->n_bodies))
+            return bad_arg("%s: param_body[%d] = %d, param[%d] is a per-body parameter of bodies[0 .. %d]", name, p, q->param_body[p], p, q->n_bodies - 1);
+    return series_outputs(name, values, len);
+}
+// (of a query check_ecl_series has accepted)
+inline Refusal check_ecl_context(const nyx_hip_ecl_query_t &q, int n_seg, bool frame_swapped) {
+    const char *name = "traj_eclipse";
+    for (int b = -1; b < q.n_bodies; ++b) {
+        const nyx_hip_ecl_body_t &body = b < 0 ? q.light : q.bodies[b];
+        char who[32];
+        ecl_body_name(who, b < 0 ? "light" : "bodies", b);
+        for (int k = 0; k < body.n_chain; ++k)
+            if (body.chain_segment[k] >= n_seg)
+                return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, who, k, body.chain_segment[k], n_seg - 1);
+    }
+    if (frame_swapped) {
+        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
+                            "trajectories is in another frame than the rest, an eclipse series of them is not defined", name);
+        r.rc = NYX_HIP_RC_UNSUPPORTED;
+        return r;
+    }
+    return {};
 }
 
 // (epoch0_ns and moments are optional)

@@ -31,6 +31,7 @@ from .rng import Pcg64Mcg
 from .params import FRAME_OF, StateError, StateParameter, ric_difference, smooth_ric, state_value
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, body_fixed_value, check_frame, to_body_fixed
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations, sez_value, station_consts
+from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, EclipseParameter, check_shadow_model, eclipse_value, state_changes
 from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
@@ -322,6 +323,62 @@ class AerSeries:
         count = held.sum(axis=1)
         with np.errstate(invalid="ignore", divide="ignore"):
             return (seen & held).sum(axis=1) / np.where(count > 0, count, np.nan)
+
+
+@dataclass
+class EclipseSeries:
+    """`Results.eclipses`: sample k of run j (position in `Results.runs`) of parameter p is `values[p, k, j]`, taken at
+    `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after them NaN.  A failed run (`ok[j]` False) is a
+    column of NaN with len 0: an empty series.  A parameter is an EclipseParameter or a pair (per-body parameter, body)."""
+
+    model: object
+    params: list
+    values: np.ndarray      # [P, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+
+    def epochs(self, j: int) -> np.ndarray:
+        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+    def of(self, param) -> np.ndarray:
+        return self.values[self.params.index(param)]
+
+    def _held(self) -> np.ndarray:
+        return np.arange(self.values.shape[1])[:, None] < self.len[None, :].astype(np.int64)
+
+    def _state(self) -> np.ndarray:
+        """0 / 1 / 2 per slot, from `State`, or from `Occultation` when that is what the series holds."""
+        if EclipseParameter.State in self.params:
+            return self.of(EclipseParameter.State)
+        if EclipseParameter.Occultation in self.params:
+            occ = self.of(EclipseParameter.Occultation)
+            return np.where(occ == 0.0, 0.0, np.where(occ == 100.0, 2.0, 1.0))
+        raise ValueError("the series holds neither State nor Occultation")
+
+    def _share(self, hit: np.ndarray) -> np.ndarray:
+        held = self._held()
+        count = held.sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (hit & held).sum(axis=0) / np.where(count > 0, count, np.nan)
+
+    @property
+    def shadow_fraction(self) -> np.ndarray:
+        """[runs]: the share of the produced samples of a run that are not fully lit (State != 0); NaN for an empty series."""
+        return self._share(self._state() != 0.0)
+
+    @property
+    def umbra_fraction(self) -> np.ndarray:
+        """[runs]: the share of the produced samples of a run in the umbra (State == 2); NaN for an empty series."""
+        return self._share(self._state() == 2.0)
+
+    @property
+    def state_changes(self) -> np.ndarray:
+        """[runs]: the number of samples whose Occultation differs from the previous sample's (`eclipse.state_changes`)."""
+        if EclipseParameter.Occultation not in self.params:
+            raise ValueError("state_changes: the series does not hold Occultation")
+        return state_changes(self.of(EclipseParameter.Occultation), self.len)
 
 
 def _fill_head(head: np.ndarray, k: int, n_k: int, first_epoch_ns) -> None:
@@ -796,6 +853,59 @@ class Results:
             err = e
         values, length, epoch0, ok, k_max, _ = self._gather_series(err, head, cols, rows_out, np.nan)
         return AerSeries(stations, params, values.reshape(len(stations), len(params), k_max, values.shape[2]), length, epoch0, step, ok)
+
+    def eclipses(self, model, step_ns: int, params=ECLIPSE_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> "EclipseSeries":
+        """The eclipse history of the ensemble: `params` of the shadow `model` (eclipse.ShadowModel; an EclipseParameter, or a
+        pair (per-body EclipseParameter, frame or index); by default the percentage hidden and the state, `ShadowModel::compute`,
+        cosmic/eclipse.rs:69-83) of every run every `step_ns`, from the start to the end of its trajectory or between
+        max(start, first epoch) and min(end, last epoch) when a window is given -> EclipseSeries.
+
+        With a device evaluator one fused launch per eight parameters (`traj_eclipse`: resampled, the almanac evaluated at each
+        sample's epoch, the disks overlapped; only the values copied back).  A failed run is a column of NaN with len 0.  Sharded
+        ensemble: a collective call.  An evaluator without `traj_eclipse` (the injected CPU evaluators of the tests) is served by
+        `traj_every` / `traj_at` + `eclipse.eclipse_value`: that composition is the definition, the device path is tested against it."""
+        params = list(params)
+        step = int(step_ns)
+        runs = self._local_runs()
+        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
+        cols = [None] * len(runs)                            # values[P, len] of every successful run
+        err = None
+        try:
+            if (start_ns is None) != (end_ns is None):
+                raise ValueError("eclipses: a window needs both start_ns and end_ns")
+            if step <= 0:
+                raise ValueError("eclipses: a positive step")
+            if not params:
+                raise ValueError("eclipses: at least one parameter")
+            compiled = getattr(self._traj_ctx, "compiled", None)
+            almanac, central = getattr(compiled, "almanac", None), getattr(compiled, "central", None)
+            if almanac is None or central is None:
+                raise ValueError("eclipses: the evaluator does not know the almanac and the central frame of the runs")
+            check_shadow_model(model, almanac, central)
+            self._need_traj()
+            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
+            rows = [self._traj_rows[runs[k].index] for k in ok]
+            tb = self._traj_batch
+            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
+            if ok and hasattr(self._traj_ctx, "traj_eclipse"):
+                vals, length = self._traj_ctx.traj_eclipse(tb, model, params, step, start_ns, end_ns)
+                for k, row in zip(ok, rows):
+                    cols[k] = vals[:, :min(int(length[row]), vals.shape[1]), row]
+            elif ok:
+                res = self._every_batch(step) if start_ns is None else None
+                pairs = [p if isinstance(p, tuple) else (p, None) for p in params]
+                for k, row in zip(ok, rows):
+                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(runs[k], step, start_ns, end_ns)
+                    ep = int(first[row]) + step * np.arange(len(rv), dtype=np.int64)
+                    col = np.stack([eclipse_value(p, rv, ep, model, almanac, central, body=b) for p, b in pairs]).reshape(len(params), len(rv))
+                    bad = np.nonzero(np.isnan(col).any(axis=0))[0]   # (a sample outside the ephemerides ends the series)
+                    cols[k] = col[:, :int(bad[0])] if len(bad) else col
+            for k, row in zip(ok, rows):
+                _fill_head(head, k, cols[k].shape[1], first[row])
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
+            err = e
+        values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), np.nan)
+        return EclipseSeries(model, params, values, length, epoch0, step, ok)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

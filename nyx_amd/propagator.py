@@ -32,6 +32,7 @@ from . import _abi
 from .params import FRAME_OF, StateError, StateParameter
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, check_frame
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations
+from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -422,10 +423,11 @@ class PropagationError(RuntimeError):
 class CompiledConfig:
     """C descriptor + the numpy arrays it points into (kept alive here)."""
 
-    def __init__(self, cfg: _abi.Config, keep: list, central: Frame):
+    def __init__(self, cfg: _abi.Config, keep: list, central: Frame, almanac: Optional["Almanac"] = None):
         self.cfg = cfg
         self._keep = keep
         self.central = central
+        self.almanac = almanac   # what the segments were compiled from: cfg.segments[k] is almanac.segments[k] (the eclipse report resolves chains in it)
 
 
 def compile_config(dynamics: SpacecraftDynamics, method: IntegratorMethod, opts: IntegratorOptions, almanac: Almanac,
@@ -616,7 +618,7 @@ def compile_config(dynamics: SpacecraftDynamics, method: IntegratorMethod, opts:
     keep.append(bodies)
     cfg.n_bodies = len(body_list)
     cfg.bodies = C.cast(bodies, C.POINTER(_abi.Body))
-    return CompiledConfig(cfg, keep, central)
+    return CompiledConfig(cfg, keep, central, almanac)
 
 
 def pack_spacecraft(states: Sequence[Spacecraft], with_stm: bool) -> _abi.StateBatch:
@@ -890,6 +892,42 @@ class GpuContext:
                     values[s0:s0 + len(group), p0:p0 + len(chunk)] = part
         return values, length
 
+    def traj_eclipse(self, traj: _abi.TrajBatch, model, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                     capacity: Optional[int] = None):
+        """``nyx_hip_traj_eclipse`` (include/nyx_hip_eclipse.h): the `params` of the shadow `model` (eclipse.ShadowModel) for every
+        trajectory of the batch every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given -
+        resampled, the ephemerides of the almanac this context was compiled from evaluated at each sample's epoch, the occultation
+        and the parameters evaluated on the device in one pass: (values[P, capacity, n], len[n]).  A parameter is an
+        EclipseParameter, a per-body one a pair `(EclipseParameter.BodyOccultation, frame_or_index)`.  `len[i]` counts the samples
+        produced for trajectory i; slots from `len[i]` on are NaN; a sample outside the ephemerides ends the series.
+        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches."""
+        fn = _abi.eclipse_entry(self._lib)
+        almanac, central = self.compiled.almanac, self.compiled.central
+        if almanac is None:
+            raise ValueError("traj_eclipse: the context was not compiled from an almanac (CompiledConfig.almanac)")
+        check_shadow_model(model, almanac, central)
+        codes = [ecl_param_code(p, model) for p in params]
+        if not codes:
+            raise ValueError("traj_eclipse: at least one parameter")
+
+        def fill_body(dst, frame):
+            chain = body_chain(frame.naif_id, almanac, central)
+            dst.n_chain, dst.mean_radius_km = len(chain), float(frame.mean_equatorial_radius_km)
+            for k, (seg, sign) in enumerate(chain):
+                dst.chain_segment[k], dst.chain_sign[k] = seg, sign
+
+        def fill(q):
+            fill_body(q.light, model.light_source)
+            q.n_bodies = len(model.shadow_bodies)
+            for b, frame in enumerate(model.shadow_bodies):
+                fill_body(q.bodies[b], frame)
+            for k in range(q.n_params):   # (_param_series stored the pairs' codes; the bodies ride in a list of their own)
+                q.param_body[k] = bodies.pop(0)
+
+        bodies = [b for _, b in codes]
+        return _param_series("traj_eclipse", fn, self._h, _abi.EclQuery, _abi.MAX_ECL_PARAMS, fill, traj, [c for c, _ in codes], step_ns, start_ns,
+                             end_ns, capacity)
+
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                       capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
         """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
@@ -975,6 +1013,22 @@ def aer_param_code(param) -> int:
     if not isinstance(param, AerParameter):
         raise TypeError(f"{param!r} is not an AerParameter")
     return _abi.AER_PARAM[param.name]
+
+
+def ecl_param_code(param, model=None):
+    """(enum nyx_hip_ecl_param, body index) of an EclipseParameter, or of a pair (per-body EclipseParameter, frame or index)."""
+    body = None
+    if isinstance(param, tuple):
+        param, body = param
+    if not isinstance(param, EclipseParameter):
+        raise TypeError(f"{param!r} is not an EclipseParameter")
+    if param in ECLIPSE_PER_BODY:
+        if body is None or model is None:
+            raise ValueError(f"{param.name} is a per-body parameter: give it as ({param.name}, frame_or_index)")
+        return _abi.ECL_PARAM[param.name], model.index_of(body)
+    if body is not None:
+        raise ValueError(f"{param.name} is a parameter of the whole shadow model: it takes no body")
+    return _abi.ECL_PARAM[param.name], 0
 
 
 def fill_gt_frame(q, frame: "Frame") -> None:
@@ -1263,6 +1317,15 @@ class Traj:
         k = int(length[0])
         lo, _ = series_bounds(self._single(), start_ns, end_ns)
         return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :, :k, 0].copy()
+
+    def eclipse(self, model, step_ns: int, params=ECLIPSE_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+        """(epochs[K], values[P, K]) of the shadow `model` (eclipse.ShadowModel) along this trajectory every `step_ns` (between
+        `start_ns` and `end_ns` when given): by default the percentage of the light source hidden and the eclipse state -
+        `ShadowModel::compute` (cosmic/eclipse.rs:69-83) -, resampled and evaluated on the device (GpuContext.traj_eclipse)."""
+        values, length = self._ctx.traj_eclipse(self._single(), model, list(params), int(step_ns), start_ns, end_ns)
+        k = int(length[0])
+        lo, _ = series_bounds(self._single(), start_ns, end_ns)
+        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
 
     def ric_diff(self, other: "Traj", step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="run",
                  transport: bool = True, smooth_window: int = 5):

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""The code-object fences of the four fused trajectory reports - the report kernels (report_kernel.hip), the RIC kernels
-(ric_kernel.hip), the ground-track kernels (groundtrack_kernel.hip) and the station-view kernels (aer_kernel.hip): what
-tests/test_report_budget.py, tests/test_ric_budget.py, tests/test_groundtrack_budget.py and tests/test_aer_budget.py measure on the
-built library, and the tool that writes the committed budgets:
-`python tools/series_budget.py FAMILY --update [slack]` (FAMILY = report, ric, groundtrack or aer) = measured figures x (1 + slack,
+"""The code-object fences of the five fused trajectory reports - the report kernels (report_kernel.hip), the RIC kernels
+(ric_kernel.hip), the ground-track kernels (groundtrack_kernel.hip), the station-view kernels (aer_kernel.hip) and the eclipse
+kernels (eclipse_kernel.hip): what tests/test_report_budget.py, tests/test_ric_budget.py, tests/test_groundtrack_budget.py,
+tests/test_aer_budget.py and tests/test_eclipse_budget.py measure on the built library, and the tool that writes the committed budgets:
+`python tools/series_budget.py FAMILY --update [slack]` (FAMILY = report, ric, groundtrack, aer or ecl) = measured figures x (1 + slack,
 default 0.08), to be run - and its diff read - when a change of those kernels is INTENDED to move them.  Same figures and rules as
 tools/code_budget.py; each family carries a kernel-name prefix and a budget file of its own."""
 import json
@@ -16,7 +16,7 @@ import code_budget  # noqa: E402
 import kernel_meta  # noqa: E402
 
 FAMILIES = {"report": ("nyxrep_", "report_budget.json"), "ric": ("nyxric_", "ric_budget.json"), "groundtrack": ("nyxgt_", "groundtrack_budget.json"),
-            "aer": ("nyxaer_", "aer_budget.json")}
+            "aer": ("nyxaer_", "aer_budget.json"), "ecl": ("nyxecl_", "eclipse_budget.json")}
 
 
 def measure(lib, family):
@@ -42,7 +42,7 @@ if __name__ == "__main__":
         i = sys.argv.index("--update")
         slack = float(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 0.08
         up = lambda v: int(v * (1.0 + slack)) + (4 if v else 0)
-        b = {"note": f"budgets = the figures of the build they were written from x (1 + slack); see tests/test_{family}_budget.py", "slack": slack,
+        b = {"note": f"budgets = the figures of the build they were written from x (1 + slack); see tests/test_{FAMILIES[family][1][:-5]}.py", "slack": slack,
              "hipcc": code_budget.toolchain(), "kernels": {k: {f: (v if f == "vgprs" else up(v)) for f, v in d.items()} for k, d in m.items()}}
         with open(os.path.join(ROOT, "tests", "golden", FAMILIES[family][1]), "w") as f:
             json.dump(b, f, indent=1, sort_keys=True)
