@@ -521,6 +521,11 @@ AER_EXPORTS = ["nyx_hip_traj_aer", "nyx_hip_traj_aer_device", "nyx_hip_aer_sizeo
 # the entries of include/nyx_hip_eclipse.h, likewise
 ECLIPSE_EXPORTS = ["nyx_hip_traj_eclipse", "nyx_hip_traj_eclipse_device", "nyx_hip_ecl_sizeof"]
 
+# the parameter-series entries nyx_hip_traj_<name>, nyx_hip_traj_<name>_device and nyx_hip_<sizeof>_sizeof share one signature but for the
+# query: name -> (sizeof, query, what a library built before them lacks - None: every library has them)
+SERIES_ENTRIES = {"values": ("reports", ValuesQuery, None), "ground_track": ("groundtrack", GtQuery, "the ground tracks"),
+                  "aer": ("aer", AerQuery, "the station views"), "eclipse": ("ecl", EclQuery, "the eclipses")}
+
 
 def load_library():
     """dlopen the in-tree HIP extension.  No CPU fallback: a missing build is an error."""
@@ -588,13 +593,6 @@ def load_library():
     lib.nyx_hip_ensemble_moments_device.restype = C.c_int32
     lib.nyx_hip_ctx_set_tuning.argtypes = [C.c_void_p, C.POINTER(Tuning)]
     lib.nyx_hip_ctx_set_tuning.restype = C.c_int32
-    lib.nyx_hip_traj_values.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(ValuesQuery), C.c_int64, c_double_p, c_int32_p]
-    lib.nyx_hip_traj_values.restype = C.c_int32
-    lib.nyx_hip_traj_values_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(ValuesQuery), C.c_int64, C.c_void_p, C.c_void_p,
-                                               C.c_void_p]
-    lib.nyx_hip_traj_values_device.restype = C.c_int32
-    lib.nyx_hip_reports_sizeof.argtypes = [C.c_int32]
-    lib.nyx_hip_reports_sizeof.restype = C.c_int32
     lib.nyx_hip_traj_ric_diff.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(Traj), C.c_int64, C.POINTER(RicQuery), C.c_int64,
                                           c_double_p, c_int32_p, c_int64_p, c_double_p]
     lib.nyx_hip_traj_ric_diff.restype = C.c_int32
@@ -603,30 +601,15 @@ def load_library():
     lib.nyx_hip_traj_ric_diff_device.restype = C.c_int32
     lib.nyx_hip_ric_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_ric_sizeof.restype = C.c_int32
-    if getattr(lib, "nyx_hip_traj_ground_track", None) is not None:   # (absent from a library built before the ground tracks)
-        lib.nyx_hip_traj_ground_track.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(GtQuery), C.c_int64, c_double_p, c_int32_p]
-        lib.nyx_hip_traj_ground_track.restype = C.c_int32
-        lib.nyx_hip_traj_ground_track_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(GtQuery), C.c_int64, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p]
-        lib.nyx_hip_traj_ground_track_device.restype = C.c_int32
-        lib.nyx_hip_groundtrack_sizeof.argtypes = [C.c_int32]
-        lib.nyx_hip_groundtrack_sizeof.restype = C.c_int32
-    if getattr(lib, "nyx_hip_traj_aer", None) is not None:   # (absent from a library built before the station views)
-        lib.nyx_hip_traj_aer.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(AerQuery), C.c_int64, c_double_p, c_int32_p]
-        lib.nyx_hip_traj_aer.restype = C.c_int32
-        lib.nyx_hip_traj_aer_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(AerQuery), C.c_int64, C.c_void_p, C.c_void_p,
-                                                C.c_void_p]
-        lib.nyx_hip_traj_aer_device.restype = C.c_int32
-        lib.nyx_hip_aer_sizeof.argtypes = [C.c_int32]
-        lib.nyx_hip_aer_sizeof.restype = C.c_int32
-    if getattr(lib, "nyx_hip_traj_eclipse", None) is not None:   # (absent from a library built before the eclipses)
-        lib.nyx_hip_traj_eclipse.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(EclQuery), C.c_int64, c_double_p, c_int32_p]
-        lib.nyx_hip_traj_eclipse.restype = C.c_int32
-        lib.nyx_hip_traj_eclipse_device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(EclQuery), C.c_int64, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p]
-        lib.nyx_hip_traj_eclipse_device.restype = C.c_int32
-        lib.nyx_hip_ecl_sizeof.argtypes = [C.c_int32]
-        lib.nyx_hip_ecl_sizeof.restype = C.c_int32
+    for name, (sizeof, query, since) in SERIES_ENTRIES.items():
+        if since is not None and getattr(lib, f"nyx_hip_traj_{name}", None) is None:   # (absent from a library built before that report)
+            continue
+        host, device, size = (getattr(lib, n) for n in (f"nyx_hip_traj_{name}", f"nyx_hip_traj_{name}_device", f"nyx_hip_{sizeof}_sizeof"))
+        host.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(query), C.c_int64, c_double_p, c_int32_p]
+        device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(query), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        size.argtypes = [C.c_int32]
+        host.restype = device.restype = size.restype = C.c_int32
+    if getattr(lib, "nyx_hip_ecl_sizeof", None) is not None:
         if lib.nyx_hip_ecl_sizeof(0) != C.sizeof(EclQuery) or lib.nyx_hip_ecl_sizeof(5) != C.sizeof(EclBody):
             raise RuntimeError(f"{lib_path()}: nyx_hip_ecl_query_t is {lib.nyx_hip_ecl_sizeof(0)} bytes, the ctypes mirror {C.sizeof(EclQuery)}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
@@ -635,31 +618,25 @@ def load_library():
     return lib
 
 
-def ground_track_entry(lib, name: str = "nyx_hip_traj_ground_track"):
-    """An entry of include/nyx_hip_groundtrack.h, or a clear error when the loaded library predates it."""
+def _series_entry(lib, name: str, report: str):
+    """An entry of the header of `report` (a key of SERIES_ENTRIES), or a clear error when the loaded library predates it."""
     fn = getattr(lib, name, None)
     if fn is None:
-        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the ground tracks were added - rebuild the HIP extension "
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before {SERIES_ENTRIES[report][2]} were added - rebuild the HIP extension "
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     return fn
+
+
+def ground_track_entry(lib, name: str = "nyx_hip_traj_ground_track"):
+    return _series_entry(lib, name, "ground_track")   # (include/nyx_hip_groundtrack.h)
 
 
 def aer_entry(lib, name: str = "nyx_hip_traj_aer"):
-    """An entry of include/nyx_hip_aer.h, or a clear error when the loaded library predates it."""
-    fn = getattr(lib, name, None)
-    if fn is None:
-        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the station views were added - rebuild the HIP extension "
-                           "(python -c 'import __graft_entry__ as g; g.build()')")
-    return fn
+    return _series_entry(lib, name, "aer")            # (include/nyx_hip_aer.h)
 
 
 def eclipse_entry(lib, name: str = "nyx_hip_traj_eclipse"):
-    """An entry of include/nyx_hip_eclipse.h, or a clear error when the loaded library predates it."""
-    fn = getattr(lib, name, None)
-    if fn is None:
-        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the eclipses were added - rebuild the HIP extension "
-                           "(python -c 'import __graft_entry__ as g; g.build()')")
-    return fn
+    return _series_entry(lib, name, "eclipse")        # (include/nyx_hip_eclipse.h)
 
 
 def last_error() -> str:

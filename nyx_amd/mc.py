@@ -209,8 +209,20 @@ class Run:
     result: object  # PropResult or PropagationError
 
 
+class _Series:
+    """What the series of the array reports share (`of`: those with `params`).  No field of its own: the dataclasses below keep
+    theirs, and their order."""
+
+    def epochs(self, j: int) -> np.ndarray:
+        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
+
+    def of(self, param) -> np.ndarray:
+        """values[K, runs] of one parameter."""
+        return self.values[self.params.index(param)]
+
+
 @dataclass
-class ValueSeries:
+class ValueSeries(_Series):
     """`Results.values_of`: sample k of run j (position in `Results.runs`) of parameter p is `values[p, k, j]`, taken at
     `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after them NaN.  A failed run (`ok[j]` False) has
     len 0 and holds the caller's substitute in every slot."""
@@ -221,9 +233,6 @@ class ValueSeries:
     epoch0_ns: np.ndarray   # [runs] int64
     step_ns: int
     ok: np.ndarray          # [runs] bool
-
-    def epochs(self, j: int) -> np.ndarray:
-        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
 
     def flat(self, param, value_if_run_failed: Optional[float] = None) -> List[float]:
         """One parameter as the list reports lay it out (results.rs:86-160): run after run; a failed run is skipped, or
@@ -239,12 +248,13 @@ class ValueSeries:
 
 
 @dataclass
-class RicSeries:
+class RicSeries(_Series):
     """`Results.ric_dispersions`: component c (dR, dI, dC in km, dvR, dvI, dvC in km/s) of sample k of run j (position in
     `Results.runs`) is `values[c, k, j]`, taken at `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after
     them NaN.  A failed run (`ok[j]` False) is a column of NaN with len 0.  `count[k]` runs have sample k; `mean[k]` and the
     unbiased `cov[k]` are taken over them (NaN where count < 1 / < 2).  They are indexed by SAMPLE: a time series of the
-    ensemble when all `epoch0_ns` agree - every run and the nominal starting at one epoch, the Monte Carlo case."""
+    ensemble when all `epoch0_ns` agree - every run and the nominal starting at one epoch, the Monte Carlo case.
+    (No `params` here, so `of` does not apply: component c is `values[c]`.)"""
 
     values: np.ndarray      # [6, K, runs]
     len: np.ndarray         # [runs] int32
@@ -256,12 +266,9 @@ class RicSeries:
     cov: np.ndarray         # [K, 6, 6]
     moments: np.ndarray     # [K, 28] what they are made of: count, sum d[6], the row-major upper triangle of sum d d^T
 
-    def epochs(self, j: int) -> np.ndarray:
-        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
-
 
 @dataclass
-class GroundTrackSeries:
+class GroundTrackSeries(_Series):
     """`Results.ground_tracks`: sample k of run j (position in `Results.runs`) of parameter p is `values[p, k, j]`, taken at
     `epoch0_ns[j] + k * step_ns` in the body-fixed `frame`; `len[j]` samples are valid, the slots after them NaN.  A failed
     run (`ok[j]` False) is a column of NaN with len 0: an empty series."""
@@ -274,16 +281,9 @@ class GroundTrackSeries:
     ok: np.ndarray          # [runs] bool
     frame: object = None
 
-    def epochs(self, j: int) -> np.ndarray:
-        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
-
-    def of(self, param) -> np.ndarray:
-        """values[K, runs] of one parameter."""
-        return self.values[self.params.index(param)]
-
 
 @dataclass
-class AerSeries:
+class AerSeries(_Series):
     """`Results.station_views`: sample k of run j (position in `Results.runs`) of parameter p seen from station s is
     `values[s, p, k, j]`, taken at `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid (the same for every station), the
     slots after them NaN.  A failed run (`ok[j]` False) is a column of NaN with len 0: an empty series."""
@@ -295,9 +295,6 @@ class AerSeries:
     epoch0_ns: np.ndarray   # [runs] int64
     step_ns: int
     ok: np.ndarray          # [runs] bool
-
-    def epochs(self, j: int) -> np.ndarray:
-        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
 
     def of(self, station, param) -> np.ndarray:
         """values[K, runs] of one parameter seen from one station (a GroundStation of `stations`, or its position)."""
@@ -326,7 +323,7 @@ class AerSeries:
 
 
 @dataclass
-class EclipseSeries:
+class EclipseSeries(_Series):
     """`Results.eclipses`: sample k of run j (position in `Results.runs`) of parameter p is `values[p, k, j]`, taken at
     `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after them NaN.  A failed run (`ok[j]` False) is a
     column of NaN with len 0: an empty series.  A parameter is an EclipseParameter or a pair (per-body parameter, body)."""
@@ -338,12 +335,6 @@ class EclipseSeries:
     epoch0_ns: np.ndarray   # [runs] int64
     step_ns: int
     ok: np.ndarray          # [runs] bool
-
-    def epochs(self, j: int) -> np.ndarray:
-        return int(self.epoch0_ns[j]) + int(self.step_ns) * np.arange(int(self.len[j]), dtype=np.int64)
-
-    def of(self, param) -> np.ndarray:
-        return self.values[self.params.index(param)]
 
     def _held(self) -> np.ndarray:
         return np.arange(self.values.shape[1])[:, None] < self.len[None, :].astype(np.int64)
@@ -602,6 +593,51 @@ class Results:
 
         return self._report(param, states_of_run, value_if_run_failed)
 
+    def _composed(self, step: int, start_ns: Optional[int], end_ns: Optional[int], value):
+        """The `composed` of a report for `_series`: `value(run, rv[len, 6], epochs[len])` -> values[n_rows, <= len] on the resampled
+        states of every run - without a window ONE `traj_every` of all the runs of this process, with one a `traj_at` per run."""
+        def composed(tb, rows):
+            first = series_bounds(tb, start_ns, end_ns)[0]
+            res = self._every_batch(step) if start_ns is None else None
+
+            def column(run, row):
+                rv = res.trajectory(row)[1] if start_ns is None else self._states_between(run, step, start_ns, end_ns)
+                return value(run, rv, int(first[row]) + step * np.arange(len(rv), dtype=np.int64))
+
+            return column, first
+
+        return composed
+
+    def _series(self, name: str, n_rows: int, fill: float, start_ns: Optional[int], end_ns: Optional[int], check, entry: str, fused, composed):
+        """The one path of the array reports (`values_of`, `ric_dispersions`, `ground_tracks`, `station_views`, `eclipses`), which
+        describe their own part with three closures:
+        `check()` raises what the report refuses, after the window check and before `_need_traj` (a check that has more to refuse after
+        `_need_traj` calls it itself, as that of `ric_dispersions` does to keep its order of refusals);
+        `fused(tb, rows)` serves an evaluator that has the fused `entry` with one launch over the batch `tb` (`rows`: those of the
+        successful local runs), `composed(tb, rows)` any other by composition (`_composed`) - that is the definition, the device is
+        tested against it; both return (column(run, row) -> values[n_rows, len] of one successful run, first epoch of every row of `tb`).
+        -> what `_gather_series` returns.  A failed run is a column of `fill` with len 0.  Whatever the preparation raises is
+        carried to `_gather_series`, which raises on every rank before the first collective."""
+        runs = self._local_runs()
+        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
+        cols = [None] * len(runs)                            # values[n_rows, len] of every successful run
+        err = None
+        try:
+            if (start_ns is None) != (end_ns is None):
+                raise ValueError(f"{name}: a window needs both start_ns and end_ns")
+            check()
+            self._need_traj()
+            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
+            rows = [self._traj_rows[runs[k].index] for k in ok]
+            if ok:
+                column, first = (fused if hasattr(self._traj_ctx, entry) else composed)(self._traj_batch, rows)
+                for k, row in zip(ok, rows):
+                    cols[k] = column(runs[k], row)
+                    _fill_head(head, k, cols[k].shape[1], first[row])
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
+            err = e
+        return self._gather_series(err, head, cols, n_rows, fill)
+
     def values_of(self, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                   value_if_run_failed: Optional[float] = None) -> "ValueSeries":
         """The array form of the list reports: `params` (a sequence of StateParameter) of every run every `step_ns`, from the
@@ -617,50 +653,35 @@ class Results:
         `state_value`: that composition is the definition of the result, the device path is tested against it."""
         params = list(params)
         step = int(step_ns)
-        fill = np.nan if value_if_run_failed is None else float(value_if_run_failed)
-        runs = self._local_runs()
-        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
-        cols = [None] * len(runs)                            # values[P, len] of every successful run
-        err = None
-        try:
-            if (start_ns is None) != (end_ns is None):
-                raise ValueError("values_of: a window needs both start_ns and end_ns")
+        orbit = [k for k, p in enumerate(params) if getattr(p, "name", None) in _abi.STATE_PARAM]
+
+        def check():   # (no refusal of a non-positive step here: the list reports have none either)
             for p in params:
                 if p in (StateParameter.Isp, StateParameter.Thrust) or not isinstance(p, StateParameter):
                     raise StateError(p)
-            self._need_traj()
-            orbit = [k for k, p in enumerate(params) if p.name in _abi.STATE_PARAM]
-            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
-            rows = [self._traj_rows[runs[k].index] for k in ok]
-            tb = self._traj_batch
-            dev = res = None
-            if ok and hasattr(self._traj_ctx, "traj_values"):
-                ask = [params[k] for k in orbit] or [StateParameter.X]   # (the lengths of the series come from the launch too)
-                vals, length = self._traj_ctx.traj_values(tb, ask, step, start_ns, end_ns, mu_km3_s2=self.mu_km3_s2 if self.mu_km3_s2 > 0 else None)
-                dev = lambda row: vals[:len(orbit), :min(int(length[row]), vals.shape[1]), row]
-            elif ok:
-                res = self._every_batch(step) if start_ns is None else None
-            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
-            for k, row in zip(ok, rows):
-                run = runs[k]
-                if dev is not None:
-                    got = dev(row)
-                    n_k = got.shape[1]
-                    rv = None
-                else:
-                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(run, step, start_ns, end_ns)
-                    n_k = len(rv)
-                col = np.empty((len(params), n_k))
-                for j, p in enumerate(params):
-                    if p.name in _abi.STATE_PARAM and dev is not None:
-                        col[j] = got[orbit.index(j)]
-                    else:   # host: the constants of the run (any rv of the right length does), or the whole composition
-                        col[j] = self._value(p, run, rv if rv is not None else np.zeros((n_k, 6)))
-                cols[k] = col
-                _fill_head(head, k, n_k, first[row])
-        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
-            err = e
-        values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), fill)
+
+        def fused(tb, rows):
+            ask = [params[k] for k in orbit] or [StateParameter.X]   # (the lengths of the series come from the launch too)
+            vals, length = self._traj_ctx.traj_values(tb, ask, step, start_ns, end_ns, mu_km3_s2=self.mu_km3_s2 if self.mu_km3_s2 > 0 else None)
+
+            def column(run, row):
+                got = vals[:len(orbit), :min(int(length[row]), vals.shape[1]), row]
+                col = np.empty((len(params), got.shape[1]))
+                for j, p in enumerate(params):   # Cr, Cd and the masses are constants of the run: any rv of the right length does
+                    col[j] = got[orbit.index(j)] if j in orbit else self._value(p, run, np.zeros((got.shape[1], 6)))
+                return col
+
+            return column, series_bounds(tb, start_ns, end_ns)[0]
+
+        def value(run, rv, ep):
+            col = np.empty((len(params), len(rv)))
+            for j, p in enumerate(params):
+                col[j] = self._value(p, run, rv)
+            return col
+
+        fill = np.nan if value_if_run_failed is None else float(value_if_run_failed)
+        values, length, epoch0, ok, _, _ = self._series("values_of", len(params), fill, start_ns, end_ns, check, "traj_values", fused,
+                                                        self._composed(step, start_ns, end_ns, value))
         return ValueSeries(params, values, length, epoch0, step, ok)
 
     def _ric_of_run(self, row: int, ref, lo: int, hi: int, step: int, frame_of, transport: bool, window: int) -> np.ndarray:
@@ -700,45 +721,41 @@ class Results:
         `ric_difference` + `smooth_ric` + numpy sums: that composition is the definition, the device path is tested against it."""
         step = int(step_ns)
         window = int(smooth_window)
-        runs = self._local_runs()
-        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
-        cols = [None] * len(runs)                            # d[6, len] of every successful run
-        mom = None
-        err = None
-        try:
-            if (start_ns is None) != (end_ns is None):
-                raise ValueError("ric_dispersions: a window needs both start_ns and end_ns")
+        ref = mom = None
+        made = []                                            # d[6, len] of the local runs, when they are composed here
+
+        def check():
+            nonlocal ref
             if frame_of not in FRAME_OF:
                 raise ValueError(f"ric_dispersions: frame_of must be 'run' / 0 or 'reference' / 1, not {frame_of!r}")
             if window < 0 or window > _abi.RIC_MAX_WINDOW or (window and window % 2 == 0) or step <= 0:
                 raise ValueError(f"ric_dispersions: a positive step and smooth_window 0 or odd up to {_abi.RIC_MAX_WINDOW}")
-            self._need_traj()
+            self._need_traj()                                # (results without trajectories are refused before the nominal is looked at)
             ref = nominal._single() if hasattr(nominal, "_single") else nominal
             if ref.n != 1:
                 raise ValueError("ric_dispersions: one nominal trajectory")
-            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
-            rows = [self._traj_rows[runs[k].index] for k in ok]
-            tb = self._traj_batch
-            if ok and hasattr(self._traj_ctx, "traj_ric_diff"):
-                live = copy.copy(tb)                         # the same arrays; the rows of the failed runs emptied: no series, no share in the sums
-                live.len = np.zeros_like(tb.len)
-                live.len[rows] = tb.len[rows]
-                vals, length, epoch0, mom = self._traj_ctx.traj_ric_diff(live, ref, step, start_ns, end_ns, frame_of=frame_of, transport=transport,
-                                                                         smooth_window=window, moments=True)
-                for k, row in zip(ok, rows):
-                    cols[k] = vals[:, :min(int(length[row]), vals.shape[1]), row]
-                first = epoch0
-            elif ok:
-                first, last = ric_bounds(tb, ref, start_ns, end_ns)
-                for k, row in zip(ok, rows):
-                    cols[k] = self._ric_of_run(row, ref, int(first[row]), int(last[row]), step, frame_of, bool(transport), window)
-            for k, row in zip(ok, rows):
-                _fill_head(head, k, cols[k].shape[1], first[row])
-        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
-            err = e
-        values, length, epoch0, ok, k_max, bounds = self._gather_series(err, head, cols, 6, np.nan)
+
+        def fused(tb, rows):
+            nonlocal mom
+            live = copy.copy(tb)                             # the same arrays; the rows of the failed runs emptied: no series, no share in the sums
+            live.len = np.zeros_like(tb.len)
+            live.len[rows] = tb.len[rows]
+            vals, length, epoch0, mom = self._traj_ctx.traj_ric_diff(live, ref, step, start_ns, end_ns, frame_of=frame_of, transport=transport,
+                                                                     smooth_window=window, moments=True)
+            return (lambda run, row: vals[:, :min(int(length[row]), vals.shape[1]), row]), epoch0
+
+        def composed(tb, rows):
+            first, last = ric_bounds(tb, ref, start_ns, end_ns)
+
+            def column(run, row):
+                made.append(self._ric_of_run(row, ref, int(first[row]), int(last[row]), step, frame_of, bool(transport), window))
+                return made[-1]
+
+            return column, first
+
+        values, length, epoch0, ok, k_max, bounds = self._series("ric_dispersions", 6, np.nan, start_ns, end_ns, check, "traj_ric_diff", fused, composed)
         if mom is None:
-            mom = ric_moments(cols, k_max)
+            mom = ric_moments(made, k_max)
         else:   # (the device sized its sums by the longest LOCAL series)
             mom = np.concatenate([mom[:k_max], np.zeros((max(k_max - len(mom), 0), _abi.RIC_MOMENTS))])
         if bounds is not None and k_max:
@@ -760,13 +777,8 @@ class Results:
         `traj_at` + `groundtrack.ground_track_value`: that composition is the definition, the device path is tested against it."""
         params = list(params)
         step = int(step_ns)
-        runs = self._local_runs()
-        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
-        cols = [None] * len(runs)                            # values[P, len] of every successful run
-        err = None
-        try:
-            if (start_ns is None) != (end_ns is None):
-                raise ValueError("ground_tracks: a window needs both start_ns and end_ns")
+
+        def check():
             if step <= 0:
                 raise ValueError("ground_tracks: a positive step")
             for p in params:
@@ -776,26 +788,17 @@ class Results:
                 raise ValueError("ground_tracks: at least one parameter")
             central = getattr(getattr(self._traj_ctx, "compiled", None), "central", None)
             check_frame(frame, central.naif_id if central is not None else None, params)
-            self._need_traj()
-            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
-            rows = [self._traj_rows[runs[k].index] for k in ok]
-            tb = self._traj_batch
-            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
-            if ok and hasattr(self._traj_ctx, "traj_ground_track"):
-                vals, length = self._traj_ctx.traj_ground_track(tb, frame, params, step, start_ns, end_ns)
-                for k, row in zip(ok, rows):
-                    cols[k] = vals[:, :min(int(length[row]), vals.shape[1]), row]
-            elif ok:
-                res = self._every_batch(step) if start_ns is None else None
-                for k, row in zip(ok, rows):
-                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(runs[k], step, start_ns, end_ns)
-                    yf = to_body_fixed(rv, int(first[row]) + step * np.arange(len(rv), dtype=np.int64), frame)
-                    cols[k] = np.stack([body_fixed_value(p, yf, frame.mean_equatorial_radius_km, frame.flattening) for p in params]).reshape(len(params), len(rv))
-            for k, row in zip(ok, rows):
-                _fill_head(head, k, cols[k].shape[1], first[row])
-        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
-            err = e
-        values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), np.nan)
+
+        def fused(tb, rows):
+            vals, length = self._traj_ctx.traj_ground_track(tb, frame, params, step, start_ns, end_ns)
+            return (lambda run, row: vals[:, :min(int(length[row]), vals.shape[1]), row]), series_bounds(tb, start_ns, end_ns)[0]
+
+        def value(run, rv, ep):
+            yf = to_body_fixed(rv, ep, frame)
+            return np.stack([body_fixed_value(p, yf, frame.mean_equatorial_radius_km, frame.flattening) for p in params]).reshape(len(params), len(rv))
+
+        values, length, epoch0, ok, _, _ = self._series("ground_tracks", len(params), np.nan, start_ns, end_ns, check, "traj_ground_track", fused,
+                                                        self._composed(step, start_ns, end_ns, value))
         return GroundTrackSeries(params, values, length, epoch0, step, ok, frame)
 
     def station_views(self, stations, step_ns: int, params=AER_DEFAULT, start_ns: Optional[int] = None,
@@ -813,14 +816,9 @@ class Results:
         `traj_at` + `stations.aer_value`: that composition is the definition, the device path is tested against it."""
         stations, params = list(stations), list(params)
         step = int(step_ns)
-        rows_out = len(stations) * len(params)
-        runs = self._local_runs()
-        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
-        cols = [None] * len(runs)                            # values[S * P, len] of every successful run
-        err = None
-        try:
-            if (start_ns is None) != (end_ns is None):
-                raise ValueError("station_views: a window needs both start_ns and end_ns")
+        rows_out = len(stations) * len(params)               # the gather sees values[S * P, len] of every run
+
+        def check():
             if step <= 0:
                 raise ValueError("station_views: a positive step")
             for p in params:
@@ -829,29 +827,27 @@ class Results:
             if not params:
                 raise ValueError("station_views: at least one parameter")
             central = getattr(getattr(self._traj_ctx, "compiled", None), "central", None)
-            frame = check_stations(stations, central.naif_id if central is not None else None)
-            self._need_traj()
-            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
-            rows = [self._traj_rows[runs[k].index] for k in ok]
-            tb = self._traj_batch
-            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
-            if ok and hasattr(self._traj_ctx, "traj_aer"):
-                vals, length = self._traj_ctx.traj_aer(tb, stations, params, step, start_ns, end_ns)
-                for k, row in zip(ok, rows):
-                    m = min(int(length[row]), vals.shape[2])
-                    cols[k] = vals[:, :, :m, row].reshape(rows_out, m)
-            elif ok:
-                consts = [station_consts(st) for st in stations]
-                res = self._every_batch(step) if start_ns is None else None
-                for k, row in zip(ok, rows):
-                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(runs[k], step, start_ns, end_ns)
-                    yf = to_body_fixed(rv, int(first[row]) + step * np.arange(len(rv), dtype=np.int64), frame)
-                    cols[k] = np.stack([sez_value(p, yf, c) for c in consts for p in params]).reshape(rows_out, len(rv))
-            for k, row in zip(ok, rows):
-                _fill_head(head, k, cols[k].shape[1], first[row])
-        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
-            err = e
-        values, length, epoch0, ok, k_max, _ = self._gather_series(err, head, cols, rows_out, np.nan)
+            check_stations(stations, central.naif_id if central is not None else None)
+
+        def fused(tb, rows):
+            vals, length = self._traj_ctx.traj_aer(tb, stations, params, step, start_ns, end_ns)
+
+            def column(run, row):
+                m = min(int(length[row]), vals.shape[2])
+                return vals[:, :, :m, row].reshape(rows_out, m)
+
+            return column, series_bounds(tb, start_ns, end_ns)[0]
+
+        def composed(tb, rows):
+            consts = [station_consts(st) for st in stations]
+
+            def value(run, rv, ep):
+                yf = to_body_fixed(rv, ep, stations[0].frame)    # (the one frame of all of them: check_stations)
+                return np.stack([sez_value(p, yf, c) for c in consts for p in params]).reshape(rows_out, len(rv))
+
+            return self._composed(step, start_ns, end_ns, value)(tb, rows)
+
+        values, length, epoch0, ok, k_max, _ = self._series("station_views", rows_out, np.nan, start_ns, end_ns, check, "traj_aer", fused, composed)
         return AerSeries(stations, params, values.reshape(len(stations), len(params), k_max, values.shape[2]), length, epoch0, step, ok)
 
     def eclipses(self, model, step_ns: int, params=ECLIPSE_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> "EclipseSeries":
@@ -866,45 +862,30 @@ class Results:
         `traj_every` / `traj_at` + `eclipse.eclipse_value`: that composition is the definition, the device path is tested against it."""
         params = list(params)
         step = int(step_ns)
-        runs = self._local_runs()
-        head = np.zeros((len(runs), 3))                      # len, first epoch (bit pattern), run succeeded
-        cols = [None] * len(runs)                            # values[P, len] of every successful run
-        err = None
-        try:
-            if (start_ns is None) != (end_ns is None):
-                raise ValueError("eclipses: a window needs both start_ns and end_ns")
+        compiled = getattr(self._traj_ctx, "compiled", None)
+        almanac, central = getattr(compiled, "almanac", None), getattr(compiled, "central", None)
+        pairs = [p if isinstance(p, tuple) else (p, None) for p in params]
+
+        def check():
             if step <= 0:
                 raise ValueError("eclipses: a positive step")
             if not params:
                 raise ValueError("eclipses: at least one parameter")
-            compiled = getattr(self._traj_ctx, "compiled", None)
-            almanac, central = getattr(compiled, "almanac", None), getattr(compiled, "central", None)
             if almanac is None or central is None:
                 raise ValueError("eclipses: the evaluator does not know the almanac and the central frame of the runs")
             check_shadow_model(model, almanac, central)
-            self._need_traj()
-            ok = [k for k, run in enumerate(runs) if isinstance(run.result, PropResult)]
-            rows = [self._traj_rows[runs[k].index] for k in ok]
-            tb = self._traj_batch
-            first = series_bounds(tb, start_ns, end_ns)[0] if ok else None
-            if ok and hasattr(self._traj_ctx, "traj_eclipse"):
-                vals, length = self._traj_ctx.traj_eclipse(tb, model, params, step, start_ns, end_ns)
-                for k, row in zip(ok, rows):
-                    cols[k] = vals[:, :min(int(length[row]), vals.shape[1]), row]
-            elif ok:
-                res = self._every_batch(step) if start_ns is None else None
-                pairs = [p if isinstance(p, tuple) else (p, None) for p in params]
-                for k, row in zip(ok, rows):
-                    rv = res.trajectory(row)[1] if start_ns is None else self._states_between(runs[k], step, start_ns, end_ns)
-                    ep = int(first[row]) + step * np.arange(len(rv), dtype=np.int64)
-                    col = np.stack([eclipse_value(p, rv, ep, model, almanac, central, body=b) for p, b in pairs]).reshape(len(params), len(rv))
-                    bad = np.nonzero(np.isnan(col).any(axis=0))[0]   # (a sample outside the ephemerides ends the series)
-                    cols[k] = col[:, :int(bad[0])] if len(bad) else col
-            for k, row in zip(ok, rows):
-                _fill_head(head, k, cols[k].shape[1], first[row])
-        except Exception as e:  # noqa: BLE001 - re-raised on every rank by _sync_errors
-            err = e
-        values, length, epoch0, ok, _, _ = self._gather_series(err, head, cols, len(params), np.nan)
+
+        def fused(tb, rows):
+            vals, length = self._traj_ctx.traj_eclipse(tb, model, params, step, start_ns, end_ns)
+            return (lambda run, row: vals[:, :min(int(length[row]), vals.shape[1]), row]), series_bounds(tb, start_ns, end_ns)[0]
+
+        def value(run, rv, ep):
+            col = np.stack([eclipse_value(p, rv, ep, model, almanac, central, body=b) for p, b in pairs]).reshape(len(params), len(rv))
+            bad = np.nonzero(np.isnan(col).any(axis=0))[0]   # (a sample outside the ephemerides ends the series)
+            return col[:, :int(bad[0])] if len(bad) else col
+
+        values, length, epoch0, ok, _, _ = self._series("eclipses", len(params), np.nan, start_ns, end_ns, check, "traj_eclipse", fused,
+                                                        self._composed(step, start_ns, end_ns, value))
         return EclipseSeries(model, params, values, length, epoch0, step, ok)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:

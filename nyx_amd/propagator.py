@@ -863,34 +863,15 @@ class GpuContext:
         if not codes:
             raise ValueError("traj_aer: at least one parameter")
         frame = check_stations(stations, self.compiled.central.naif_id)
-        if (start_ns is None) != (end_ns is None):
-            raise ValueError("traj_aer: a window needs both start_ns and end_ns")
-        cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
-        values = np.empty((len(stations), len(codes), max(cap, 0), traj.n), dtype=np.float64)
-        length = np.zeros(traj.n, dtype=np.int32)
-        cin = traj.as_c()
-        for s0 in range(0, len(stations), _abi.MAX_STATIONS):
-            group = stations[s0:s0 + _abi.MAX_STATIONS]
-            for p0 in range(0, len(codes), _abi.MAX_AER_PARAMS):
-                chunk = codes[p0:p0 + _abi.MAX_AER_PARAMS]
-                q = _abi.AerQuery()
-                q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
-                q.param[:len(chunk)] = chunk
-                if start_ns is not None:
-                    q.start_ns, q.end_ns = int(start_ns), int(end_ns)
-                fill_gt_frame(q, frame)
-                q.n_stations = len(group)
-                for k, st in enumerate(group):
-                    q.stations[k].latitude_deg, q.stations[k].longitude_deg = float(st.latitude_deg), float(st.longitude_deg)
-                    q.stations[k].height_km, q.stations[k].elevation_mask_deg = float(st.height_km), float(st.elevation_mask_deg)
-                whole = len(chunk) == len(codes)
-                part = values[s0:s0 + len(group)] if whole else np.empty((len(group), len(chunk), max(cap, 0), traj.n))   # (contiguous: in place)
-                rc = fn(self._h, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
-                if rc != 0:
-                    raise RuntimeError(f"nyx_hip_traj_aer failed (rc={rc}): {_abi.last_error()}")
-                if not whole:
-                    values[s0:s0 + len(group), p0:p0 + len(chunk)] = part
-        return values, length
+
+        def fill_stations(q, group):
+            q.n_stations = len(group)
+            for k, st in enumerate(group):
+                q.stations[k].latitude_deg, q.stations[k].longitude_deg = float(st.latitude_deg), float(st.longitude_deg)
+                q.stations[k].height_km, q.stations[k].elevation_mask_deg = float(st.height_km), float(st.elevation_mask_deg)
+
+        return _param_series("traj_aer", fn, self._h, _abi.AerQuery, _abi.MAX_AER_PARAMS, lambda q: fill_gt_frame(q, frame), traj, codes, step_ns, start_ns,
+                             end_ns, capacity, groups=(stations, _abi.MAX_STATIONS, fill_stations))
 
     def traj_eclipse(self, traj: _abi.TrajBatch, model, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                      capacity: Optional[int] = None):
@@ -967,29 +948,40 @@ class GpuContext:
         return out, stats
 
 
-def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity):
-    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`) of the context `handle` over the parameter
-    codes, `per_call` of them per launch: (values[len(codes), capacity, n], len[n]).  `query_cls` is the entry's query, `fill(q)` sets the
-    fields that only this entry has."""
+def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity, groups=None):
+    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`, `traj_aer`, `traj_eclipse`) of the context `handle`
+    over the parameter codes, `per_call` of them per launch: (values[len(codes), capacity, n], len[n]).  `query_cls` is the entry's query,
+    `fill(q)` sets the fields that only this entry has.  `groups=(items, per_call, fill_group)` adds an outer axis (the stations of
+    `traj_aer`): `fill_group(q, some of the items)` names those of a launch, and the values are [len(items), len(codes), capacity, n]."""
     if (start_ns is None) != (end_ns is None):
         raise ValueError(f"{name}: a window needs both start_ns and end_ns")
     cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
-    values = np.empty((len(codes), max(cap, 0), traj.n), dtype=np.float64)
+    items, per_group, fill_group = groups if groups is not None else ([None], 1, None)
+    values = np.empty((len(items), len(codes), max(cap, 0), traj.n), dtype=np.float64)
     length = np.zeros(traj.n, dtype=np.int32)
     cin = traj.as_c()
-    for lo in range(0, len(codes), per_call):
-        chunk = codes[lo:lo + per_call]
-        q = query_cls()
-        q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
-        q.param[:len(chunk)] = chunk
-        if start_ns is not None:
-            q.start_ns, q.end_ns = int(start_ns), int(end_ns)
-        fill(q)
-        part = values[lo:lo + len(chunk)]   # (a contiguous block of the result: written in place)
-        rc = fn(handle, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
-        if rc != 0:
-            raise RuntimeError(f"nyx_hip_{name} failed (rc={rc}): {_abi.last_error()}")
-    return values, length
+    for g0 in range(0, len(items), per_group):
+        group = items[g0:g0 + per_group]
+        for lo in range(0, len(codes), per_call):
+            chunk = codes[lo:lo + per_call]
+            q = query_cls()
+            q.n_params, q.has_window, q.step_ns = len(chunk), int(start_ns is not None), int(step_ns)
+            q.param[:len(chunk)] = chunk
+            if start_ns is not None:
+                q.start_ns, q.end_ns = int(start_ns), int(end_ns)
+            fill(q)
+            if groups is not None:
+                fill_group(q, group)
+            # a launch without groups, or one that covers all the parameters, fills a contiguous block of the result: written in place
+            whole = groups is None or len(chunk) == len(codes)
+            block = values[g0:g0 + len(group), lo:lo + len(chunk)]
+            part = block if whole else np.empty(block.shape)
+            rc = fn(handle, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
+            if rc != 0:
+                raise RuntimeError(f"nyx_hip_{name} failed (rc={rc}): {_abi.last_error()}")
+            if not whole:
+                block[...] = part
+    return (values if groups is not None else values[0]), length
 
 
 def report_param_code(param) -> int:
@@ -1289,43 +1281,37 @@ class Traj:
         n = int(bad[0]) if len(bad) else len(q)
         return q[:n], states[:n, 0]
 
+    def _series(self, got, step_ns: int, start_ns, end_ns):
+        """(epochs[K], values[..., K]) of this trajectory from what a parameter series of `_single()` returned: (values[..., capacity, 1], len[1])."""
+        values, length = got
+        k = int(length[0])
+        lo, _ = series_bounds(self._single(), start_ns, end_ns)
+        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[..., :k, 0].copy()
+
     def values_every(self, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
         """(epochs[K], values[P, K]) of the orbit-derived `params` every `step_ns` (between `start_ns` and `end_ns` when given):
         `every` / `every_between` and the parameter evaluation fused on the device (GpuContext.traj_values)."""
-        params = list(params)
-        values, length = self._ctx.traj_values(self._single(), params, int(step_ns), start_ns, end_ns)
-        k = int(length[0])
-        lo, _ = series_bounds(self._single(), start_ns, end_ns)
-        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
+        return self._series(self._ctx.traj_values(self._single(), list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
 
     def ground_track(self, frame: "Frame", step_ns: int, params=GROUND_TRACK_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
         """(epochs[K], values[P, K]) of the ground track in the body-fixed `frame` every `step_ns` (between `start_ns` and `end_ns`
         when given): `to_groundtrack_parquet` (sc_traj.rs:131-155) without the file - by default its four fields, geodetic
         latitude, longitude, height and |r| -, resampled, rotated at each sample's epoch and evaluated on the device
         (GpuContext.traj_ground_track)."""
-        values, length = self._ctx.traj_ground_track(self._single(), frame, list(params), int(step_ns), start_ns, end_ns)
-        k = int(length[0])
-        lo, _ = series_bounds(self._single(), start_ns, end_ns)
-        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
+        return self._series(self._ctx.traj_ground_track(self._single(), frame, list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
 
     def station_view(self, stations, step_ns: int, params=AER_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
         """(epochs[K], values[S, P, K]) of this trajectory seen from `stations` (GroundStation, all of one frame) every `step_ns`
         (between `start_ns` and `end_ns` when given): by default azimuth, elevation, range and range rate - what
         `TrackingDevice::measure_instantaneous` reads (trk_device.rs:158-208), without noise or light time -, resampled, rotated at
         each sample's epoch and evaluated on the device (GpuContext.traj_aer)."""
-        values, length = self._ctx.traj_aer(self._single(), list(stations), list(params), int(step_ns), start_ns, end_ns)
-        k = int(length[0])
-        lo, _ = series_bounds(self._single(), start_ns, end_ns)
-        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :, :k, 0].copy()
+        return self._series(self._ctx.traj_aer(self._single(), list(stations), list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
 
     def eclipse(self, model, step_ns: int, params=ECLIPSE_DEFAULT, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
         """(epochs[K], values[P, K]) of the shadow `model` (eclipse.ShadowModel) along this trajectory every `step_ns` (between
         `start_ns` and `end_ns` when given): by default the percentage of the light source hidden and the eclipse state -
         `ShadowModel::compute` (cosmic/eclipse.rs:69-83) -, resampled and evaluated on the device (GpuContext.traj_eclipse)."""
-        values, length = self._ctx.traj_eclipse(self._single(), model, list(params), int(step_ns), start_ns, end_ns)
-        k = int(length[0])
-        lo, _ = series_bounds(self._single(), start_ns, end_ns)
-        return int(lo[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
+        return self._series(self._ctx.traj_eclipse(self._single(), model, list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
 
     def ric_diff(self, other: "Traj", step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="run",
                  transport: bool = True, smooth_window: int = 5):

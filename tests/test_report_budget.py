@@ -1,71 +1,18 @@
-"""CPU-side fence around the report kernels (report_kernel.hip), the twin of tests/test_code_budget.py for the kernels with
-the `nyxrep_` prefix: VGPRs, scratch bytes per lane, static spill counts and .text bytes of every one of them
-(tools/kernel_meta.py) are held to tests/golden/report_budget.json - a figure above its budget fails with the number, a
-figure more than 25 % BELOW its budget fails too (stale budget: `python tools/series_budget.py report --update`), and the tests skip
-under another hipcc than the one the budgets were written under.  On top of that the evaluation kernel, which runs the
-interpolation of nyx_traj_eval_kernel plus the parameter block, may not use more scratch or spill more VGPRs than that
-sibling's own budget (tests/golden/code_budget.json): the parameter block must not push HRMINT's tables out of registers.
-No GPU needed."""
-import json
-import os
-import shutil
-import sys
+"""The fence around the report kernels (report_kernel.hip, prefix `nyxrep_`, budgets in tests/golden/report_budget.json) is the one of
+tests/test_series_budget.py, family `report`, which that file runs as its `[report]` cases.  These three only keep the names the tests
+had here, so that their records go on: nothing to add to when a family comes, and nothing is lost when they go."""
+import test_series_budget as fence
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-LIB = os.path.join(ROOT, "nyx_amd", "libnyx_hip.so")
-BUDGET = os.path.join(ROOT, "tests", "golden", "report_budget.json")
-SIBLING = os.path.join(ROOT, "tests", "golden", "code_budget.json")
-
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf") or shutil.which("objcopy") is None,
-                                reason="no built library or no LLVM binutils here")
-
-_CACHE = {}
-
-
-def measured():
-    import code_budget
-    import series_budget
-    want = json.load(open(BUDGET)).get("hipcc")
-    have = code_budget.toolchain()
-    if want and have and want != have:
-        pytest.skip(f"budgets were written under hipcc {want}, this is {have}: python tools/series_budget.py report --update")
-    if "m" not in _CACHE:
-        _CACHE["m"] = series_budget.measure(LIB, "report")
-    return _CACHE["m"]
+pytestmark = fence.NEEDS
 
 
 def test_every_report_kernel_is_inside_its_budget():
-    budget = json.load(open(BUDGET))["kernels"]
-    got = measured()
-    assert set(budget) == {"init_kernel", "values_kernel", "seal_kernel"}
-    problems = []
-    for kernel, b in budget.items():
-        assert kernel in got, f"{kernel}: not in the library any more (python tools/series_budget.py report --update)"
-        for key, limit in b.items():
-            v = got[kernel][key]
-            if v > limit:
-                problems.append(f"{kernel}.{key}: {v} > budget {limit}")
-            elif key in ("scratch_bytes", "vgpr_spills", "text_bytes") and limit > 64 and v < 0.75 * limit:
-                problems.append(f"{kernel}.{key}: {v} is more than 25 % under its budget {limit} - tighten it")
-    new = sorted(set(got) - set(budget))
-    assert not new, f"report kernels without a budget: {new}"
-    assert not problems, "\n".join(problems)
+    fence.test_every_kernel_is_inside_its_budget("report")
 
 
 def test_the_parameter_block_does_not_push_the_interpolation_into_scratch():
-    sibling = json.load(open(SIBLING))["kernels"]["traj_eval_kernel"]
-    got = measured()["values_kernel"]
-    assert got["scratch_bytes"] <= sibling["scratch_bytes"], (got, sibling)
-    assert got["vgpr_spills"] <= sibling["vgpr_spills"], (got, sibling)
+    fence.test_the_evaluation_kernel_does_not_push_the_interpolation_into_scratch("report")
 
 
 def test_report_kernels_stay_out_of_the_other_fence():
-    """tools/code_budget.py takes every kernel whose name contains `nyx_`: the report kernels carry another prefix."""
-    import code_budget
-    import kernel_meta
-    names = [k.get("name", "") for k in kernel_meta.kernels(LIB)]
-    mine = [n for n in names if "nyxrep_" in n]
-    assert len(mine) == 3 and not [n for n in mine if "nyx_" in n], mine
+    fence.test_the_kernels_stay_out_of_the_other_fences("report")

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """The code-object fences of the five fused trajectory reports - the report kernels (report_kernel.hip), the RIC kernels
 (ric_kernel.hip), the ground-track kernels (groundtrack_kernel.hip), the station-view kernels (aer_kernel.hip) and the eclipse
-kernels (eclipse_kernel.hip): what tests/test_report_budget.py, tests/test_ric_budget.py, tests/test_groundtrack_budget.py,
-tests/test_aer_budget.py and tests/test_eclipse_budget.py measure on the built library, and the tool that writes the committed budgets:
+kernels (eclipse_kernel.hip): what tests/test_series_budget.py measures on the built library, and the tool that writes the committed budgets:
 `python tools/series_budget.py FAMILY --update [slack]` (FAMILY = report, ric, groundtrack, aer or ecl) = measured figures x (1 + slack,
 default 0.08), to be run - and its diff read - when a change of those kernels is INTENDED to move them.  Same figures and rules as
 tools/code_budget.py; each family carries a kernel-name prefix and a budget file of its own."""
