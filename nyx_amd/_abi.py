@@ -355,6 +355,20 @@ class EclQuery(C.Structure):
                 ("_pad", C.c_int32), ("bodies", EclBody * MAX_ECL_BODIES)]
 
 
+# ---- include/nyx_hip_frame.h (the encounter report: an ensemble seen from another body) ----
+FRAME_VERSION = 1
+MAX_FRAME_PARAMS = 8
+# enum nyx_hip_frame_param: the members of frames.FrameParameter, by name; 0 .. 18 are STATE_PARAM
+FRAME_PARAM = dict(STATE_PARAM, C3=19, BdotT=20, BdotR=21, BAngle=22, BMagnitude=23, VInfinity=24)
+FRAME_COUNT = 25
+
+
+class FrameQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("has_window", C.c_int32), ("param", C.c_int32 * MAX_FRAME_PARAMS), ("step_ns", C.c_int64),
+                ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("n_chain", C.c_int32), ("chain_segment", C.c_int32 * MAX_CHAIN),
+                ("chain_sign", C.c_int32 * MAX_CHAIN), ("_pad", C.c_int32), ("mu_km3_s2", C.c_double)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -521,10 +535,14 @@ AER_EXPORTS = ["nyx_hip_traj_aer", "nyx_hip_traj_aer_device", "nyx_hip_aer_sizeo
 # the entries of include/nyx_hip_eclipse.h, likewise
 ECLIPSE_EXPORTS = ["nyx_hip_traj_eclipse", "nyx_hip_traj_eclipse_device", "nyx_hip_ecl_sizeof"]
 
+# the entries of include/nyx_hip_frame.h, likewise
+FRAME_EXPORTS = ["nyx_hip_traj_frame_values", "nyx_hip_traj_frame_values_device", "nyx_hip_frame_sizeof"]
+
 # the parameter-series entries nyx_hip_traj_<name>, nyx_hip_traj_<name>_device and nyx_hip_<sizeof>_sizeof share one signature but for the
 # query: name -> (sizeof, query, what a library built before them lacks - None: every library has them)
 SERIES_ENTRIES = {"values": ("reports", ValuesQuery, None), "ground_track": ("groundtrack", GtQuery, "the ground tracks"),
-                  "aer": ("aer", AerQuery, "the station views"), "eclipse": ("ecl", EclQuery, "the eclipses")}
+                  "aer": ("aer", AerQuery, "the station views"), "eclipse": ("ecl", EclQuery, "the eclipses"),
+                  "frame_values": ("frame", FrameQuery, "the encounter reports")}
 
 
 def load_library():
@@ -612,6 +630,8 @@ def load_library():
     if getattr(lib, "nyx_hip_ecl_sizeof", None) is not None:
         if lib.nyx_hip_ecl_sizeof(0) != C.sizeof(EclQuery) or lib.nyx_hip_ecl_sizeof(5) != C.sizeof(EclBody):
             raise RuntimeError(f"{lib_path()}: nyx_hip_ecl_query_t is {lib.nyx_hip_ecl_sizeof(0)} bytes, the ctypes mirror {C.sizeof(EclQuery)}")
+    if getattr(lib, "nyx_hip_frame_sizeof", None) is not None and lib.nyx_hip_frame_sizeof(0) != C.sizeof(FrameQuery):
+        raise RuntimeError(f"{lib_path()}: nyx_hip_frame_query_t is {lib.nyx_hip_frame_sizeof(0)} bytes, the ctypes mirror {C.sizeof(FrameQuery)}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -637,6 +657,10 @@ def aer_entry(lib, name: str = "nyx_hip_traj_aer"):
 
 def eclipse_entry(lib, name: str = "nyx_hip_traj_eclipse"):
     return _series_entry(lib, name, "eclipse")        # (include/nyx_hip_eclipse.h)
+
+
+def frame_entry(lib, name: str = "nyx_hip_traj_frame_values"):
+    return _series_entry(lib, name, "frame_values")   # (include/nyx_hip_frame.h)
 
 
 def last_error() -> str:

@@ -31,6 +31,7 @@
 #include "ric_args.h"
 #include "aer_args.h"
 #include "eclipse_args.h"
+#include "frame_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
 #include "run_host.h"
@@ -45,6 +46,7 @@ extern "C" hipError_t nyx_launch_ric_diff(const RicArgs *args, hipStream_t strea
 extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_aer(const AerArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_eclipse(const EclArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
+extern "C" hipError_t nyx_launch_traj_frame_values(const FrmArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1308,6 +1310,50 @@ extern "C" int32_t nyx_hip_traj_eclipse(nyx_hip_ctx *ctx, const nyx_hip_traj_t *
     return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "eclipse",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_eclipse_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
+                       });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Encounter report (include/nyx_hip_frame.h): frame_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_frame_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_frame_query_t);
+    case 1: return NYX_HIP_FRAME_VERSION;
+    case 2: return NYX_HIP_FRM_COUNT;
+    case 3: return NYX_HIP_MAX_FRAME_PARAMS;
+    default: return -1;
+    }
+}
+
+// check_frame_series never reads the context; what the query asks of the context - its segments, no integration-frame swap - is
+// checked behind it
+static Refusal check_frame(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_frame_query_t *q, int64_t capacity,
+                           const double *values, const int32_t *len) {
+    if (Refusal r = check_frame_series(ctx, traj, n, q, capacity, values, len)) return r;
+    return check_frame_context(*q, ctx->host_cfg.n_seg, ctx->swap_n_chain != 0);
+}
+
+extern "C" int32_t nyx_hip_traj_frame_values_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_frame_query_t *q,
+                                                    int64_t capacity, double *values, int32_t *len, void *hip_stream) {
+    if (Refusal r = check_frame(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    FrmArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    a.records = ctx->d_records;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_traj_frame_values(&a, ctx->host_cfg.seg, stream); });
+}
+
+extern "C" int32_t nyx_hip_traj_frame_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_frame_query_t *q,
+                                             int64_t capacity, double *values, int32_t *len) {
+    if (Refusal r = check_frame(ctx, traj, n, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "encounter",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
+                           return nyx_hip_traj_frame_values_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
 }
 

@@ -1,5 +1,5 @@
-// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the six series kernels,
-// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the five fused reports (values, ground track, station views, eclipses, RIC) refuse, the
+// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the seven series kernels,
+// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the six fused reports (values, ground track, station views, eclipses, encounters, RIC) refuse, the
 // one output block of a report's host flavour, and the chunks of consecutive samples a launch cuts a span into.
 #pragma once
 #include <climits>
@@ -11,6 +11,7 @@
 
 #include "aer_args.h"
 #include "eclipse_args.h"
+#include "frame_args.h"
 #include "groundtrack_args.h"
 #include "report_args.h"
 #include "ric_args.h"
@@ -192,6 +193,38 @@ inline Refusal check_ecl_context(const nyx_hip_ecl_query_t &q, int n_seg, bool f
     if (frame_swapped) {
         Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
                             "trajectories is in another frame than the rest, an eclipse series of them is not defined", name);
+        r.rc = NYX_HIP_RC_UNSUPPORTED;
+        return r;
+    }
+    return {};
+}
+
+// The encounter report (include/nyx_hip_frame.h): the pattern of the eclipses with ONE chain, the target's.  check_frame_series never
+// dereferences the context; check_frame_context is what the query asks of it, for the reason check_ecl_context gives.
+inline Refusal check_frame_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_frame_query_t *q, int64_t capacity,
+                                  const double *values, const int32_t *len) {
+    const char *name = "traj_frame_values";
+    int32_t need = 0;
+    if (Refusal r = series_open(name, ctx, traj, false, nullptr, q, n)) return r;
+    if (Refusal r = series_params(name, *q, NYX_HIP_MAX_FRAME_PARAMS, frm_param_needs, "nyx_hip_frame_param", &need)) return r;
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    if (q->n_chain < 0 || q->n_chain > NYX_HIP_MAX_CHAIN) return bad_arg("%s: n_chain = %d, 0 .. %d segments", name, q->n_chain, NYX_HIP_MAX_CHAIN);
+    for (int k = 0; k < q->n_chain; ++k) {
+        if (q->chain_segment[k] < 0) return bad_arg("%s: chain_segment[%d] = %d is not a segment of the context", name, k, q->chain_segment[k]);
+        if (q->chain_sign[k] != 1 && q->chain_sign[k] != -1) return bad_arg("%s: chain_sign[%d] = %d, +1 or -1", name, k, q->chain_sign[k]);
+    }
+    if (!(std::isfinite(q->mu_km3_s2) && q->mu_km3_s2 > 0.0)) return bad_arg("%s: mu_km3_s2 must be finite and > 0", name);
+    return series_outputs(name, values, len);
+}
+// (of a query check_frame_series has accepted)
+inline Refusal check_frame_context(const nyx_hip_frame_query_t &q, int n_seg, bool frame_swapped) {
+    const char *name = "traj_frame_values";
+    for (int k = 0; k < q.n_chain; ++k)
+        if (q.chain_segment[k] >= n_seg)
+            return bad_arg("%s: chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, k, q.chain_segment[k], n_seg - 1);
+    if (frame_swapped) {
+        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
+                            "trajectories is in another frame than the rest, a series of them about another centre is not defined", name);
         r.rc = NYX_HIP_RC_UNSUPPORTED;
         return r;
     }

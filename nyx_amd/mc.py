@@ -32,6 +32,7 @@ from .params import FRAME_OF, StateError, StateParameter, ric_difference, smooth
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, body_fixed_value, check_frame, to_body_fixed
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations, sez_value, station_consts
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, EclipseParameter, check_shadow_model, eclipse_value, state_changes
+from .frames import FrameParameter, check_target, frame_param, frame_value
 from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
@@ -370,6 +371,58 @@ class EclipseSeries(_Series):
         if EclipseParameter.Occultation not in self.params:
             raise ValueError("state_changes: the series does not hold Occultation")
         return state_changes(self.of(EclipseParameter.Occultation), self.len)
+
+
+@dataclass
+class FrameSeries(_Series):
+    """`Results.frame_values`: sample k of run j (position in `Results.runs`) of parameter p, about `target`, is `values[p, k, j]`,
+    taken at `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after them NaN.  A failed run (`ok[j]` False) is a
+    column of NaN with len 0: an empty series.  A held sample that is not hyperbolic about the target has NaN B-plane values."""
+
+    target: object
+    params: list            # FrameParameter members
+    values: np.ndarray      # [P, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+
+    def _held(self) -> np.ndarray:
+        return np.arange(self.values.shape[1])[:, None] < self.len[None, :].astype(np.int64)
+
+    def of(self, param) -> np.ndarray:
+        """values[K, runs] of one parameter (a FrameParameter, or the StateParameter of the same name)."""
+        return self.values[self.params.index(frame_param(param))]
+
+    def closest_approach(self):
+        """(sample[runs] int64, rmag[runs]): per run the sample index and the value of the minimum of `Rmag` over the run's `len`
+        samples (the first one when several tie); (-1, NaN) for an empty series.  Raises when the series does not hold Rmag."""
+        if FrameParameter.Rmag not in self.params:
+            raise ValueError("closest_approach: the series does not hold Rmag")
+        rmag = np.where(self._held(), self.of(FrameParameter.Rmag), np.inf)
+        if rmag.shape[0] == 0:
+            return np.full(rmag.shape[1], -1, dtype=np.int64), np.full(rmag.shape[1], np.nan)
+        k = np.argmin(rmag, axis=0).astype(np.int64)
+        best = rmag[k, np.arange(rmag.shape[1])]
+        empty = self.len <= 0
+        return np.where(empty, -1, k), np.where(empty, np.nan, best)
+
+    def hyperbolic_fraction(self) -> np.ndarray:
+        """[runs]: the share of the produced samples of a run that are hyperbolic about the target (a B-plane value, VInfinity or
+        Eccentricity > 1 tells); NaN for an empty series.  Raises when the series holds none of them."""
+        for p in (FrameParameter.BdotT, FrameParameter.BdotR, FrameParameter.BAngle, FrameParameter.BMagnitude, FrameParameter.VInfinity):
+            if p in self.params:
+                hyp = ~np.isnan(self.of(p))
+                break
+        else:
+            if FrameParameter.Eccentricity not in self.params:
+                raise ValueError("hyperbolic_fraction: the series holds neither a B-plane parameter, VInfinity nor Eccentricity")
+            with np.errstate(invalid="ignore"):
+                hyp = self.of(FrameParameter.Eccentricity) > 1.0
+        held = self._held()
+        count = held.sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (hyp & held).sum(axis=0) / np.where(count > 0, count, np.nan)
 
 
 def _fill_head(head: np.ndarray, k: int, n_k: int, first_epoch_ns) -> None:
@@ -887,6 +940,49 @@ class Results:
         values, length, epoch0, ok, _, _ = self._series("eclipses", len(params), np.nan, start_ns, end_ns, check, "traj_eclipse", fused,
                                                         self._composed(step, start_ns, end_ns, value))
         return EclipseSeries(model, params, values, length, epoch0, step, ok)
+
+    def frame_values(self, target, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None) -> "FrameSeries":
+        """The ensemble seen from another body: `params` (FrameParameter members, or the orbit-derived StateParameter of the same
+        name) of every run about `target` - a Frame of the runs' orientation with another ephemeris id and its own mu - every
+        `step_ns`, from the start to the end of its trajectory or between max(start, first epoch) and min(end, last epoch) when a
+        window is given -> FrameSeries.  `Traj::to_frame` (sc_traj.rs:88-129) then the elements and the B-plane (cosmic/bplane.rs)
+        about the target.
+
+        With a device evaluator one fused launch per eight parameters (`traj_frame_values`: resampled, the almanac evaluated at each
+        sample's epoch, the state translated, the parameters evaluated; only the values copied back).  A failed run is a column of
+        NaN with len 0; a sample outside the ephemerides ends a series, one that is not hyperbolic has NaN B-plane values and does
+        not.  Sharded ensemble: a collective call.  An evaluator without `traj_frame_values` (the injected CPU evaluators of the
+        tests) is served by `traj_every` / `traj_at` + `frames.frame_value`: that composition is the definition, the device path is
+        tested against it."""
+        params = list(params)
+        step = int(step_ns)
+        compiled = getattr(self._traj_ctx, "compiled", None)
+        almanac, central = getattr(compiled, "almanac", None), getattr(compiled, "central", None)
+        codes = []
+
+        def check():
+            if step <= 0:
+                raise ValueError("frame_values: a positive step")
+            if not params:
+                raise ValueError("frame_values: at least one parameter")
+            codes[:] = [frame_param(p) for p in params]
+            if almanac is None or central is None:
+                raise ValueError("frame_values: the evaluator does not know the almanac and the central frame of the runs")
+            check_target(target, almanac, central)
+
+        def fused(tb, rows):
+            vals, length = self._traj_ctx.traj_frame_values(tb, target, codes, step, start_ns, end_ns)
+            return (lambda run, row: vals[:, :min(int(length[row]), vals.shape[1]), row]), series_bounds(tb, start_ns, end_ns)[0]
+
+        def value(run, rv, ep):
+            moved = np.asarray(frame_value(FrameParameter.X, rv, ep, target, almanac, central)).reshape(len(rv))
+            col = np.stack([frame_value(p, rv, ep, target, almanac, central) for p in codes]).reshape(len(codes), len(rv))
+            bad = np.nonzero(np.isnan(moved))[0]             # (a sample outside the ephemerides ends the series; a NaN B-plane value does not)
+            return col[:, :int(bad[0])] if len(bad) else col
+
+        values, length, epoch0, ok, _, _ = self._series("frame_values", len(params), np.nan, start_ns, end_ns, check, "traj_frame_values", fused,
+                                                        self._composed(step, start_ns, end_ns, value))
+        return FrameSeries(target, codes, values, length, epoch0, step, ok)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

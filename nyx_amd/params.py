@@ -129,6 +129,45 @@ def state_value(param: StateParameter, rv: np.ndarray, mu_km3_s2: float, cr=None
     raise StateError(param)
 
 
+def bplane_of_state(rv, mu_km3_s2: float):
+    """(BdotT, BdotR) of every row of `rv` ([..., 6]) about a centre of `mu_km3_s2`: `bplane` on evec, ecc, h, hmag and sma exactly as
+    `state_value` forms them."""
+    rv = np.asarray(rv, dtype=np.float64)
+    r, v = rv[..., :3], rv[..., 3:]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rmag = np.linalg.norm(r, axis=-1)
+        vmag = np.linalg.norm(v, axis=-1)
+        h = np.cross(r, v)
+        hmag = np.linalg.norm(h, axis=-1)
+        energy = 0.5 * vmag * vmag - mu_km3_s2 / rmag
+        sma = -mu_km3_s2 / (2.0 * energy)
+        evec = ((vmag * vmag - mu_km3_s2 / rmag)[..., None] * r - np.sum(r * v, axis=-1)[..., None] * v) / mu_km3_s2
+        ecc = np.linalg.norm(evec, axis=-1)
+    return bplane(evec, ecc, h, hmag, sma)
+
+
+def bplane(evec, ecc, h, hmag, sma):
+    """(BdotT, BdotR) of cosmic/bplane.rs:55-136 from the intermediates of `state_value`, NaN where ecc <= 1 (`BPlane::new`:
+    NotHyperbolic).  e^ = evec / ecc, h^ = h / hmag, n^ = h^ x e^, f = sqrt(1 - (1 / ecc)(1 / ecc)); the incoming asymptote
+    s = e^ / ecc + f n^; b = |sma| sqrt(ecc ecc - 1), the semi-minor axis; B = b (f e^ - (1 / ecc) n^); t = s^ x (0, 0, 1), r^ = s^ x t^.
+    Sums of three as ((a0 + a1) + a2): the definition csrc/frame_dev.h (`frm_bplane`) restates operation for operation."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        inv_e = 1.0 / ecc
+        eh, hh = evec / ecc[..., None], h / hmag[..., None]
+        nh = _cross3(hh, eh)
+        f = np.sqrt(1.0 - inv_e * inv_e)
+        s = eh / ecc[..., None] + f[..., None] * nh
+        sh = s / np.sqrt(_dot3(s, s))[..., None]
+        b = np.abs(sma) * np.sqrt(ecc * ecc - 1.0)
+        big_b = b[..., None] * (f[..., None] * eh - inv_e[..., None] * nh)
+        t0, t1 = sh[..., 1], -sh[..., 0]                       # t = s^ x (0, 0, 1) = (s^_1, -s^_0, 0)
+        tmag = np.sqrt(t0 * t0 + t1 * t1)
+        th = np.stack([t0 / tmag, t1 / tmag, 0.0 / tmag], axis=-1)
+        rh = _cross3(sh, th)
+        hyp = ecc > 1.0
+        return np.where(hyp, _dot3(big_b, th), np.nan), np.where(hyp, _dot3(big_b, rh), np.nan)
+
+
 # ---- RIC differences (Traj::ric_diff_to_parquet, md/trajectory/traj.rs:407-600) ----
 FRAME_OF = {"run": 0, "reference": 1, 0: 0, 1: 1}
 

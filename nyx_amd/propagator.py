@@ -32,6 +32,7 @@ from . import _abi
 from .params import FRAME_OF, StateError, StateParameter
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, check_frame
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations
+from . import frames
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
 
 NS_PER_S = 1_000_000_000
@@ -909,6 +910,33 @@ class GpuContext:
         return _param_series("traj_eclipse", fn, self._h, _abi.EclQuery, _abi.MAX_ECL_PARAMS, fill, traj, [c for c, _ in codes], step_ns, start_ns,
                              end_ns, capacity)
 
+    def traj_frame_values(self, traj: _abi.TrajBatch, target: "Frame", params, step_ns: int, start_ns: Optional[int] = None,
+                          end_ns: Optional[int] = None, capacity: Optional[int] = None):
+        """``nyx_hip_traj_frame_values`` (include/nyx_hip_frame.h): the `params` (FrameParameter members, or the orbit-derived
+        StateParameter of the same name) of every trajectory of the batch SEEN FROM `target` - a Frame of the context's orientation
+        with another ephemeris id and its own mu - every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` /
+        `end_ns` are given - resampled, the state of the target evaluated from the almanac this context was compiled from at each
+        sample's epoch and subtracted (`Traj::to_frame`), the parameters evaluated about the target on the device in one pass:
+        (values[P, capacity, n], len[n]).  `len[i]` counts the samples produced for trajectory i; slots from `len[i]` on are NaN; a
+        sample outside the ephemerides ends the series, a sample that is not hyperbolic has NaN B-plane values and does not.
+        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches."""
+        fn = _abi.frame_entry(self._lib)
+        almanac, central = self.compiled.almanac, self.compiled.central
+        if almanac is None:
+            raise ValueError("traj_frame_values: the context was not compiled from an almanac (CompiledConfig.almanac)")
+        chain = frames.check_target(target, almanac, central)
+        codes = [int(frames.frame_param(p)) for p in params]
+        if not codes:
+            raise ValueError("traj_frame_values: at least one parameter")
+
+        def fill(q):
+            q.n_chain, q.mu_km3_s2 = len(chain), float(target.mu_km3_s2)
+            for k, (seg, sign) in enumerate(chain):
+                q.chain_segment[k], q.chain_sign[k] = seg, sign
+
+        return _param_series("traj_frame_values", fn, self._h, _abi.FrameQuery, _abi.MAX_FRAME_PARAMS, fill, traj, codes, step_ns, start_ns, end_ns,
+                             capacity)
+
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                       capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
         """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
@@ -949,7 +977,7 @@ class GpuContext:
 
 
 def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity, groups=None):
-    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`, `traj_aer`, `traj_eclipse`) of the context `handle`
+    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`, `traj_aer`, `traj_eclipse`, `traj_frame_values`) of the context `handle`
     over the parameter codes, `per_call` of them per launch: (values[len(codes), capacity, n], len[n]).  `query_cls` is the entry's query,
     `fill(q)` sets the fields that only this entry has.  `groups=(items, per_call, fill_group)` adds an outer axis (the stations of
     `traj_aer`): `fill_group(q, some of the items)` names those of a launch, and the values are [len(items), len(codes), capacity, n]."""
@@ -1312,6 +1340,27 @@ class Traj:
         `start_ns` and `end_ns` when given): by default the percentage of the light source hidden and the eclipse state -
         `ShadowModel::compute` (cosmic/eclipse.rs:69-83) -, resampled and evaluated on the device (GpuContext.traj_eclipse)."""
         return self._series(self._ctx.traj_eclipse(self._single(), model, list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
+
+    def frame_values(self, target: "Frame", params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None):
+        """(epochs[K], values[P, K]) of `params` (FrameParameter members) of this trajectory seen from `target` every `step_ns`
+        (between `start_ns` and `end_ns` when given): `to_frame` and the parameter evaluation about the target, resampled and
+        evaluated on the device (GpuContext.traj_frame_values)."""
+        return self._series(self._ctx.traj_frame_values(self._single(), target, list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
+
+    def to_frame(self, target: "Frame") -> "Traj":
+        """`Traj::to_frame` (sc_traj.rs:88-129) between two frames of one orientation, on the host: the STORED states at their stored
+        epochs about `target` (frames.to_frame), as a new Traj of the same evaluator.  Raises ValueError on an epoch outside the
+        ephemerides of the almanac the evaluator was compiled from."""
+        compiled = getattr(self._ctx, "compiled", None)
+        almanac, central = getattr(compiled, "almanac", None), getattr(compiled, "central", None)
+        if almanac is None or central is None:
+            raise ValueError("to_frame: the evaluator does not know the almanac and the central frame of this trajectory")
+        frames.check_target(target, almanac, central)
+        states = frames.to_frame(self.states, self.epochs_ns, target, almanac, central)
+        bad = np.nonzero(np.isnan(states).any(axis=-1) & ~np.isnan(self.states).any(axis=-1))[0]
+        if len(bad):
+            raise ValueError(f"to_frame: epoch {int(self.epochs_ns[bad[0]])} ns lies outside the ephemerides of frame {int(target.naif_id)}")
+        return Traj.from_arrays(self._ctx, self.epochs_ns, states)
 
     def ric_diff(self, other: "Traj", step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="run",
                  transport: bool = True, smooth_window: int = 5):

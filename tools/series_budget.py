@@ -19,7 +19,12 @@ FAMILIES = {"report": ("nyxrep_", "report_budget.json"), "ric": ("nyxric_", "ric
 
 
 def measure(lib, family):
-    prefix = FAMILIES[family][0]
+    return measure_prefix(lib, FAMILIES[family][0])
+
+
+def measure_prefix(lib, prefix):
+    """The figures of every kernel of `lib` whose name holds `prefix` (a family of FAMILIES, or one with a tool of its own:
+    tools/frame_budget.py)."""
     out = {}
     for k in kernel_meta.kernels(lib):
         name = k.get("name", "")
