@@ -369,6 +369,23 @@ class FrameQuery(C.Structure):
                 ("chain_sign", C.c_int32 * MAX_CHAIN), ("_pad", C.c_int32), ("mu_km3_s2", C.c_double)]
 
 
+# ---- include/nyx_hip_link.h (the link report: range, Doppler and line of sight from a transmitter to an ensemble) ----
+LINK_VERSION = 1
+MAX_LINK_PARAMS = 8
+MAX_LINK_BODIES = 8
+# enum nyx_hip_link_param: the members of links.LinkParameter, by name
+LINK_PARAM = {"Range": 0, "RangeRate": 1, "ReferenceDoppler": 2, "Visible": 3, "ObstructingBody": 4, "Clearance": 5, "RelativeSpeed": 6,
+              "LosX": 7, "LosY": 8, "LosZ": 9, "BodyClearance": 10, "BodyObstructs": 11}
+LINK_COUNT = 12
+LINK_FIRST_PER_BODY = 10
+
+
+class LinkQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("param", C.c_int32 * MAX_LINK_PARAMS), ("param_body", C.c_int32 * MAX_LINK_PARAMS), ("has_window", C.c_int32),
+                ("step_ns", C.c_int64), ("start_ns", C.c_int64), ("end_ns", C.c_int64), ("n_bodies", C.c_int32), ("_pad", C.c_int32),
+                ("bodies", EclBody * MAX_LINK_BODIES)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -538,11 +555,16 @@ ECLIPSE_EXPORTS = ["nyx_hip_traj_eclipse", "nyx_hip_traj_eclipse_device", "nyx_h
 # the entries of include/nyx_hip_frame.h, likewise
 FRAME_EXPORTS = ["nyx_hip_traj_frame_values", "nyx_hip_traj_frame_values_device", "nyx_hip_frame_sizeof"]
 
+# the entries of include/nyx_hip_link.h, likewise
+LINK_EXPORTS = ["nyx_hip_traj_link", "nyx_hip_traj_link_device", "nyx_hip_link_sizeof"]
+
 # the parameter-series entries nyx_hip_traj_<name>, nyx_hip_traj_<name>_device and nyx_hip_<sizeof>_sizeof share one signature but for the
 # query: name -> (sizeof, query, what a library built before them lacks - None: every library has them)
 SERIES_ENTRIES = {"values": ("reports", ValuesQuery, None), "ground_track": ("groundtrack", GtQuery, "the ground tracks"),
                   "aer": ("aer", AerQuery, "the station views"), "eclipse": ("ecl", EclQuery, "the eclipses"),
-                  "frame_values": ("frame", FrameQuery, "the encounter reports")}
+                  "frame_values": ("frame", FrameQuery, "the encounter reports"), "link": ("link", LinkQuery, "the link reports")}
+# those of them that take a second batch (`ref`, n_ref) behind the first and return the first epochs behind `len`
+REF_SERIES = frozenset(["link"])
 
 
 def load_library():
@@ -623,8 +645,9 @@ def load_library():
         if since is not None and getattr(lib, f"nyx_hip_traj_{name}", None) is None:   # (absent from a library built before that report)
             continue
         host, device, size = (getattr(lib, n) for n in (f"nyx_hip_traj_{name}", f"nyx_hip_traj_{name}_device", f"nyx_hip_{sizeof}_sizeof"))
-        host.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(query), C.c_int64, c_double_p, c_int32_p]
-        device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, C.POINTER(query), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        ref = [C.POINTER(Traj), C.c_int64] if name in REF_SERIES else []
+        host.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, *ref, C.POINTER(query), C.c_int64, c_double_p, c_int32_p] + ([c_int64_p] if ref else [])
+        device.argtypes = [C.c_void_p, C.POINTER(Traj), C.c_int64, *ref, C.POINTER(query), C.c_int64, C.c_void_p, C.c_void_p] + ([C.c_void_p] if ref else []) + [C.c_void_p]
         size.argtypes = [C.c_int32]
         host.restype = device.restype = size.restype = C.c_int32
     if getattr(lib, "nyx_hip_ecl_sizeof", None) is not None:
@@ -632,6 +655,8 @@ def load_library():
             raise RuntimeError(f"{lib_path()}: nyx_hip_ecl_query_t is {lib.nyx_hip_ecl_sizeof(0)} bytes, the ctypes mirror {C.sizeof(EclQuery)}")
     if getattr(lib, "nyx_hip_frame_sizeof", None) is not None and lib.nyx_hip_frame_sizeof(0) != C.sizeof(FrameQuery):
         raise RuntimeError(f"{lib_path()}: nyx_hip_frame_query_t is {lib.nyx_hip_frame_sizeof(0)} bytes, the ctypes mirror {C.sizeof(FrameQuery)}")
+    if getattr(lib, "nyx_hip_link_sizeof", None) is not None and lib.nyx_hip_link_sizeof(0) != C.sizeof(LinkQuery):
+        raise RuntimeError(f"{lib_path()}: nyx_hip_link_query_t is {lib.nyx_hip_link_sizeof(0)} bytes, the ctypes mirror {C.sizeof(LinkQuery)}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -661,6 +686,10 @@ def eclipse_entry(lib, name: str = "nyx_hip_traj_eclipse"):
 
 def frame_entry(lib, name: str = "nyx_hip_traj_frame_values"):
     return _series_entry(lib, name, "frame_values")   # (include/nyx_hip_frame.h)
+
+
+def link_entry(lib, name: str = "nyx_hip_traj_link"):
+    return _series_entry(lib, name, "link")           # (include/nyx_hip_link.h)
 
 
 def last_error() -> str:

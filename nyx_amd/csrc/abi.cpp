@@ -31,6 +31,7 @@
 #include "ric_args.h"
 #include "aer_args.h"
 #include "eclipse_args.h"
+#include "link_args.h"
 #include "frame_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
@@ -47,6 +48,7 @@ extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipSt
 extern "C" hipError_t nyx_launch_traj_aer(const AerArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_eclipse(const EclArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_frame_values(const FrmArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
+extern "C" hipError_t nyx_launch_traj_link(const LnkArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1395,6 +1397,53 @@ extern "C" int32_t nyx_hip_traj_ric_diff(nyx_hip_ctx *ctx, const nyx_hip_traj_t 
     return series_host(ctx, traj, n, ref, n_ref, 6, capacity, {values, len, epoch0_ns, moments}, "RIC",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *nominal, const SeriesOut &d) {
                            return nyx_hip_traj_ric_diff_device(ctx, src, n, nominal, n_ref, q, capacity, d.values, d.len, d.epoch0, d.moments, nullptr);
+                       });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Link report (include/nyx_hip_link.h): link_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_link_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_link_query_t);
+    case 1: return NYX_HIP_LINK_VERSION;
+    case 2: return NYX_HIP_LNK_COUNT;
+    case 3: return NYX_HIP_MAX_LINK_PARAMS;
+    case 4: return NYX_HIP_MAX_LINK_BODIES;
+    default: return -1;
+    }
+}
+
+// check_link_series never reads the context; what the query asks of the context - its segments, no integration-frame swap - is
+// checked behind it
+static Refusal check_link(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                          const nyx_hip_link_query_t *q, int64_t capacity, const double *values, const int32_t *len) {
+    if (Refusal r = check_link_series(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return r;
+    return check_link_context(*q, ctx->host_cfg.n_seg, ctx->swap_n_chain != 0);
+}
+
+extern "C" int32_t nyx_hip_traj_link_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                                            const nyx_hip_link_query_t *q, int64_t capacity, double *values, int32_t *len, int64_t *epoch0_ns,
+                                            void *hip_stream) {
+    if (Refusal r = check_link(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    LnkArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.ref = *ref; a.n = n; a.n_ref = n_ref; a.capacity = capacity;
+    a.values = values; a.len = len; a.epoch0 = epoch0_ns; a.q = *q;
+    a.records = ctx->d_records;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_traj_link(&a, ctx->host_cfg.seg, stream); });
+}
+
+extern "C" int32_t nyx_hip_traj_link(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                                     const nyx_hip_link_query_t *q, int64_t capacity, double *values, int32_t *len, int64_t *epoch0_ns) {
+    if (Refusal r = check_link(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    return series_host(ctx, traj, n, ref, n_ref, q->n_params, capacity, {values, len, epoch0_ns, nullptr}, "link",
+                       [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *tx, const SeriesOut &d) {
+                           return nyx_hip_traj_link_device(ctx, src, n, tx, n_ref, q, capacity, d.values, d.len, d.epoch0, nullptr);
                        });
 }
 

@@ -76,26 +76,29 @@ static inline void ecl_needs(EclArgs &a) {
 // an Earth-centred context: it is evaluated once per sample.  The chain order is kept, so the sums are those of the oracle's
 // body_position.  Returns false (nothing usable in `a`) when the chains name more than ECL_MAX_USEG distinct segments, which a query
 // check_ecl_series has accepted cannot.
+// (ecl_reduce_chain is the step of ONE body, over the distinct segments found so far: the link report, link_args.h, shares it)
+static inline bool ecl_reduce_chain(const nyx_hip_ecl_body_t &src, EclChain &dst, int32_t &n_useg, int32_t *seg_index, DevSeg *seg,
+                                    const DevSeg *ctx_seg) {
+    dst.n_chain = src.n_chain;
+    dst.radius_km = src.mean_radius_km;
+    for (int k = 0; k < NYX_HIP_MAX_CHAIN; ++k) { dst.useg[k] = 0; dst.sign[k] = 0.0; }
+    for (int k = 0; k < src.n_chain; ++k) {
+        int u = 0;
+        while (u < n_useg && seg_index[u] != src.chain_segment[k]) ++u;
+        if (u == n_useg) {
+            if (n_useg == ECL_MAX_USEG) return false;
+            seg_index[u] = src.chain_segment[k];
+            seg[u] = ctx_seg[src.chain_segment[k]];
+            ++n_useg;
+        }
+        dst.useg[k] = u;
+        dst.sign[k] = (double)src.chain_sign[k];
+    }
+    return true;
+}
 static inline bool ecl_reduce_chains(EclArgs &a, const DevSeg *ctx_seg) {
     a.n_useg = 0;
-    for (int b = -1; b < a.q.n_bodies; ++b) {
-        const nyx_hip_ecl_body_t &src = b < 0 ? a.q.light : a.q.bodies[b];
-        EclChain &dst = b < 0 ? a.light : a.body[b];
-        dst.n_chain = src.n_chain;
-        dst.radius_km = src.mean_radius_km;
-        for (int k = 0; k < NYX_HIP_MAX_CHAIN; ++k) { dst.useg[k] = 0; dst.sign[k] = 0.0; }
-        for (int k = 0; k < src.n_chain; ++k) {
-            int u = 0;
-            while (u < a.n_useg && a.seg_index[u] != src.chain_segment[k]) ++u;
-            if (u == a.n_useg) {
-                if (a.n_useg == ECL_MAX_USEG) return false;
-                a.seg_index[u] = src.chain_segment[k];
-                a.seg[u] = ctx_seg[src.chain_segment[k]];
-                ++a.n_useg;
-            }
-            dst.useg[k] = u;
-            dst.sign[k] = (double)src.chain_sign[k];
-        }
-    }
+    for (int b = -1; b < a.q.n_bodies; ++b)
+        if (!ecl_reduce_chain(b < 0 ? a.q.light : a.q.bodies[b], b < 0 ? a.light : a.body[b], a.n_useg, a.seg_index, a.seg, ctx_seg)) return false;
     return true;
 }

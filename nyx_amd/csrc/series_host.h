@@ -1,5 +1,5 @@
-// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the seven series kernels,
-// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the six fused reports (values, ground track, station views, eclipses, encounters, RIC) refuse, the
+// series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the eight series kernels,
+// tests/cxx/series_host_check.cpp): what traj_at / traj_every and the seven fused reports (values, ground track, station views, eclipses, encounters, RIC, links) refuse, the
 // one output block of a report's host flavour, and the chunks of consecutive samples a launch cuts a span into.
 #pragma once
 #include <climits>
@@ -13,6 +13,7 @@
 #include "eclipse_args.h"
 #include "frame_args.h"
 #include "groundtrack_args.h"
+#include "link_args.h"
 #include "report_args.h"
 #include "ric_args.h"
 #include "traj_args.h"
@@ -244,6 +245,50 @@ inline Refusal check_ric_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *tr
     if (q->smooth_window < 0 || q->smooth_window > NYX_HIP_RIC_MAX_WINDOW || (q->smooth_window != 0 && q->smooth_window % 2 == 0))
         return bad_arg("%s: smooth_window = %d, 0 or an odd window up to %d", name, q->smooth_window, NYX_HIP_RIC_MAX_WINDOW);
     return series_outputs(name, values, len);
+}
+
+// The link report (include/nyx_hip_link.h): the opening of the RIC report (two trajectories, n_ref = 1 or n), then the pattern of the
+// eclipses without a light source: the bodies may be none.  check_link_series never dereferences the context; check_link_context is
+// what the query asks of it, for the reason check_ecl_context gives.  (epoch0_ns is optional)
+inline Refusal check_link_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                                 const nyx_hip_link_query_t *q, int64_t capacity, const double *values, const int32_t *len) {
+    const char *name = "traj_link";
+    int32_t need = 0;
+    if (Refusal r = series_open(name, ctx, traj, true, ref, q, n)) return r;
+    if (n_ref != 1 && n_ref != n)
+        return bad_arg("%s: n_ref = %lld, one transmitter trajectory or one per run (n = %lld)", name, (long long)n_ref, (long long)n);
+    if (Refusal r = series_params(name, *q, NYX_HIP_MAX_LINK_PARAMS, lnk_param_needs, "nyx_hip_link_param", &need)) return r;
+    if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
+    if (q->n_bodies < 0 || q->n_bodies > NYX_HIP_MAX_LINK_BODIES)
+        return bad_arg("%s: n_bodies = %d, 0 .. %d bodies per call", name, q->n_bodies, NYX_HIP_MAX_LINK_BODIES);
+    for (int b = 0; b < q->n_bodies; ++b)
+        if (Refusal r = check_ecl_body(name, "bodies", b, q->bodies[b], 0)) return r;
+    for (int p = 0; p < q->n_params; ++p) {
+        if (!lnk_param_per_body(q->param[p])) continue;
+        if (q->n_bodies == 0) return bad_arg("%s: param[%d] is a per-body parameter and the query names no body (n_bodies = 0)", name, p);
+        if (q->param_body[p] < 0 || q->param_body[p] >= q->n_bodies)
+            return bad_arg("%s: param_body[%d] = %d, param[%d] is a per-body parameter of bodies[0 .. %d]", name, p, q->param_body[p], p, q->n_bodies - 1);
+    }
+    return series_outputs(name, values, len);
+}
+// (of a query check_link_series has accepted)
+inline Refusal check_link_context(const nyx_hip_link_query_t &q, int n_seg, bool frame_swapped) {
+    const char *name = "traj_link";
+    for (int b = 0; b < q.n_bodies; ++b) {
+        const nyx_hip_ecl_body_t &body = q.bodies[b];
+        char who[32];
+        ecl_body_name(who, "bodies", b);
+        for (int k = 0; k < body.n_chain; ++k)
+            if (body.chain_segment[k] >= n_seg)
+                return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, who, k, body.chain_segment[k], n_seg - 1);
+    }
+    if (frame_swapped) {
+        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
+                            "trajectories is in another frame than the rest, a link series of them is not defined", name);
+        r.rc = NYX_HIP_RC_UNSUPPORTED;
+        return r;
+    }
+    return {};
 }
 
 // ---- the one output block of a report's host flavour: values[n_params][capacity][n] (station views: one row per station and

@@ -33,6 +33,7 @@ from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackPara
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations, sez_value, station_consts
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, EclipseParameter, check_shadow_model, eclipse_value, state_changes
 from .frames import FrameParameter, check_target, frame_param, frame_value
+from .links import DEFAULT_PARAMS as LINK_DEFAULT, LinkParameter, check_link_bodies, default_bodies, link_param, link_value, outside_ephemerides
 from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
@@ -425,6 +426,55 @@ class FrameSeries(_Series):
             return (hyp & held).sum(axis=0) / np.where(count > 0, count, np.nan)
 
 
+@dataclass
+class LinkSeries(_Series):
+    """`Results.link_views`: sample k of run j (position in `Results.runs`) of parameter p of the link from the transmitter to that
+    run is `values[p, k, j]`, taken at `epoch0_ns[j] + k * step_ns`; `len[j]` samples are valid, the slots after them NaN.  A failed
+    run (`ok[j]` False) is a column of NaN with len 0: an empty series.  A parameter is a LinkParameter or a pair (per-body
+    parameter, body)."""
+
+    bodies: list
+    params: list
+    values: np.ndarray      # [P, K, runs]
+    len: np.ndarray         # [runs] int32
+    epoch0_ns: np.ndarray   # [runs] int64
+    step_ns: int
+    ok: np.ndarray          # [runs] bool
+
+    def _held(self) -> np.ndarray:
+        return np.arange(self.values.shape[1])[:, None] < self.len[None, :].astype(np.int64)
+
+    def visible_fraction(self) -> np.ndarray:
+        """[K]: per sample, the share of the runs HOLDING that sample (k < len[j]) that see the transmitter, as
+        `AerSeries.visible_fraction`; NaN where no run holds the sample.  Formed on the host from `Visible`, or from
+        `ObstructingBody` / `Clearance` when that is what the series holds."""
+        if LinkParameter.Visible in self.params:
+            seen = self.of(LinkParameter.Visible) > 0.0
+        elif LinkParameter.ObstructingBody in self.params:
+            seen = self.of(LinkParameter.ObstructingBody) < 0.0
+        elif LinkParameter.Clearance in self.params:
+            seen = self.of(LinkParameter.Clearance) > 0.0
+        else:
+            raise ValueError("visible_fraction: the series holds none of Visible, ObstructingBody and Clearance")
+        held = self._held()
+        count = held.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (seen & held).sum(axis=1) / np.where(count > 0, count, np.nan)
+
+    def closest_range(self):
+        """(range_km[runs], epoch_ns[runs] int64): per run the minimum of `Range` over the run's `len` samples and the epoch it is
+        taken at (the first one when several tie); (NaN, 0) for an empty series.  Raises when the series does not hold Range."""
+        if LinkParameter.Range not in self.params:
+            raise ValueError("closest_range: the series does not hold Range")
+        rng = np.where(self._held(), self.of(LinkParameter.Range), np.inf)
+        runs = rng.shape[1]
+        if rng.shape[0] == 0:
+            return np.full(runs, np.nan), np.zeros(runs, dtype=np.int64)
+        k = np.argmin(rng, axis=0).astype(np.int64)
+        empty = self.len <= 0
+        return np.where(empty, np.nan, rng[k, np.arange(runs)]), np.where(empty, 0, self.epoch0_ns + k * int(self.step_ns))
+
+
 def _fill_head(head: np.ndarray, k: int, n_k: int, first_epoch_ns) -> None:
     """Row k of the head of an array report - what every rank must know of a successful run before the columns are gathered:
     its len, the bit pattern of its first epoch (0 for an empty series), and that it succeeded."""
@@ -662,7 +712,7 @@ class Results:
         return composed
 
     def _series(self, name: str, n_rows: int, fill: float, start_ns: Optional[int], end_ns: Optional[int], check, entry: str, fused, composed):
-        """The one path of the array reports (`values_of`, `ric_dispersions`, `ground_tracks`, `station_views`, `eclipses`), which
+        """The one path of the array reports (`values_of`, `ric_dispersions`, `ground_tracks`, `station_views`, `eclipses`, `frame_values`, `link_views`), which
         describe their own part with three closures:
         `check()` raises what the report refuses, after the window check and before `_need_traj` (a check that has more to refuse after
         `_need_traj` calls it itself, as that of `ric_dispersions` does to keep its order of refusals);
@@ -737,11 +787,11 @@ class Results:
                                                         self._composed(step, start_ns, end_ns, value))
         return ValueSeries(params, values, length, epoch0, step, ok)
 
-    def _ric_of_run(self, row: int, ref, lo: int, hi: int, step: int, frame_of, transport: bool, window: int) -> np.ndarray:
-        """d[6, len] of one run against the nominal by composition: two `traj_at` on the common grid, cut at the first epoch
-        either cannot be interpolated at, `ric_difference`, `smooth_ric`."""
+    def _states_of_pair(self, row: int, ref, lo: int, hi: int, step: int):
+        """(rx[len, 6], tx[len, 6], epochs[len]) of one run and the batch `ref` of one trajectory on their common grid: two
+        `traj_at`, cut at the first epoch either cannot be interpolated at."""
         if hi < lo:
-            return np.zeros((6, 0))
+            return np.zeros((0, 6)), np.zeros((0, 6)), np.zeros(0, dtype=np.int64)
         tb = self._traj_batch
         q = lo + step * np.arange((hi - lo) // step + 1, dtype=np.int64)
         m = min(int(tb.len[row]), tb.capacity)
@@ -753,7 +803,14 @@ class Results:
         b, sb = self._traj_ctx.traj_at(ref, q)
         bad = np.nonzero(_abi.interp_failed(sa[:, 0]) | _abi.interp_failed(sb[:, 0]))[0]
         k = int(bad[0]) if len(bad) else len(q)
-        d = ric_difference(a[:k, 0], b[:k, 0], frame_of=frame_of, transport=transport)
+        return a[:k, 0], b[:k, 0], q[:k]
+
+    def _ric_of_run(self, row: int, ref, lo: int, hi: int, step: int, frame_of, transport: bool, window: int) -> np.ndarray:
+        """d[6, len] of one run against the nominal by composition: `_states_of_pair`, `ric_difference`, `smooth_ric`."""
+        if hi < lo:
+            return np.zeros((6, 0))
+        a, b, _ = self._states_of_pair(row, ref, lo, hi, step)
+        d = ric_difference(a, b, frame_of=frame_of, transport=transport)
         return (smooth_ric(d, window) if window >= 3 else d).T
 
     def ric_dispersions(self, nominal, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None, frame_of="reference",
@@ -983,6 +1040,64 @@ class Results:
         values, length, epoch0, ok, _, _ = self._series("frame_values", len(params), np.nan, start_ns, end_ns, check, "traj_frame_values", fused,
                                                         self._composed(step, start_ns, end_ns, value))
         return FrameSeries(target, codes, values, length, epoch0, step, ok)
+
+    def link_views(self, transmitter, step_ns: int, params=LINK_DEFAULT, bodies=None, start_ns: Optional[int] = None,
+                   end_ns: Optional[int] = None) -> "LinkSeries":
+        """The ensemble seen from another spacecraft: `params` (a LinkParameter, or a pair (per-body LinkParameter, frame or index);
+        by default range, range rate and visibility) of the link from `transmitter` (a Traj, or a TrajBatch of one trajectory) to
+        every run every `step_ns` over the overlap of the two spans (clamped to the window when given) -> LinkSeries.  `bodies`:
+        the Frames that can block the line; None: the runs' centre with its mean equatorial radius, what the reference's
+        `InterlinkTxSpacecraft::measure_instantaneous` (od/interlink/trk_device.rs) obstructs with.  The instantaneous geometry
+        only: no noise, no light time, no integration-time average.
+
+        With a device evaluator one fused launch per eight parameters (`traj_link`: both trajectories resampled, the almanac
+        evaluated at each sample's epoch, the SIGHT test; only the values copied back).  A failed run is a column of NaN with len 0.
+        Sharded ensemble: a collective call, every rank passes the same transmitter.  An evaluator without `traj_link` (the injected
+        CPU evaluators of the tests) is served by `traj_at` + `links.link_value`: that composition is the definition, the device path
+        is tested against it."""
+        params = list(params)
+        step = int(step_ns)
+        compiled = getattr(self._traj_ctx, "compiled", None)
+        almanac, central = getattr(compiled, "almanac", None), getattr(compiled, "central", None)
+        ref = None
+        who, pairs = [], []
+
+        def check():
+            nonlocal ref
+            if step <= 0:
+                raise ValueError("link_views: a positive step")
+            if not params:
+                raise ValueError("link_views: at least one parameter")
+            if central is None:
+                raise ValueError("link_views: the evaluator does not know the central frame of the runs")
+            who[:] = default_bodies(central) if bodies is None else list(bodies)
+            check_link_bodies(who, almanac, central)
+            pairs[:] = [link_param(p, who) for p in params]
+            self._need_traj()                                # (results without trajectories are refused before the transmitter is looked at)
+            ref = transmitter._single() if hasattr(transmitter, "_single") else transmitter
+            if ref.n != 1:
+                raise ValueError("link_views: one transmitter trajectory")
+
+        def fused(tb, rows):
+            live = copy.copy(tb)                             # the same arrays; the rows of the failed runs emptied: no series
+            live.len = np.zeros_like(tb.len)
+            live.len[rows] = tb.len[rows]
+            vals, length, epoch0 = self._traj_ctx.traj_link(live, ref, params, step, start_ns, end_ns, bodies=who)
+            return (lambda run, row: vals[:, :min(int(length[row]), vals.shape[1]), row]), epoch0
+
+        def composed(tb, rows):
+            first, last = ric_bounds(tb, ref, start_ns, end_ns)
+
+            def column(run, row):
+                rx, tx, ep = self._states_of_pair(row, ref, int(first[row]), int(last[row]), step)
+                col = np.stack([link_value(p, rx, tx, ep, who, almanac, central, body=b) for p, b in pairs]).reshape(len(pairs), len(ep))
+                bad = np.nonzero(outside_ephemerides(ep, who, almanac, central))[0]   # (a sample outside the ephemerides ends the series)
+                return col[:, :int(bad[0])] if len(bad) else col
+
+            return column, first
+
+        values, length, epoch0, ok, _, _ = self._series("link_views", len(params), np.nan, start_ns, end_ns, check, "traj_link", fused, composed)
+        return LinkSeries(list(who), params, values, length, epoch0, step, ok)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

@@ -34,6 +34,7 @@ from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackPara
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations
 from . import frames
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
+from . import links
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -937,6 +938,44 @@ class GpuContext:
         return _param_series("traj_frame_values", fn, self._h, _abi.FrameQuery, _abi.MAX_FRAME_PARAMS, fill, traj, codes, step_ns, start_ns, end_ns,
                              capacity)
 
+    def traj_link(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                  capacity: Optional[int] = None, bodies=None):
+        """``nyx_hip_traj_link`` (include/nyx_hip_link.h): the `params` of the link from the transmitter `ref` (one trajectory for all,
+        or one per run) to every trajectory of `traj`, the receivers, every `step_ns` over the overlap of the two spans (clamped to
+        `start_ns` / `end_ns` when given) - both resampled, the `bodies` that can block the line (Frames; None: the context's centre
+        with its mean equatorial radius, what the reference obstructs with) placed from the almanac this context was compiled from at
+        each sample's epoch, range, Doppler and the SIGHT test evaluated on the device in one pass:
+        (values[P, capacity, n], len[n], epoch0_ns[n]).  A parameter is a LinkParameter, a per-body one a pair
+        `(LinkParameter.BodyClearance, frame_or_index)`.  `len[i]` counts the samples produced for run i; slots from `len[i]` on are
+        NaN; a sample outside the ephemerides of a body ends the series.  `capacity=None` sizes the series from the epochs of the
+        two batches.  More than eight parameters take several launches.  An almanac is needed only when a body has a chain."""
+        fn = _abi.link_entry(self._lib)
+        almanac, central = self.compiled.almanac, self.compiled.central
+        bodies = links.default_bodies(central) if bodies is None else list(bodies)
+        links.check_link_bodies(bodies, almanac, central)
+        codes = [links.link_param(p, bodies) for p in params]
+        if not codes:
+            raise ValueError("traj_link: at least one parameter")
+        if (start_ns is None) != (end_ns is None):
+            raise ValueError("traj_link: a window needs both start_ns and end_ns")
+        chains = [links.link_chain(frame, almanac, central) for frame in bodies]
+        of_body = [b for _, b in codes]
+
+        def fill(q):
+            q.n_bodies = len(bodies)
+            for b, (frame, chain) in enumerate(zip(bodies, chains)):
+                q.bodies[b].n_chain, q.bodies[b].mean_radius_km = len(chain), float(frame.mean_equatorial_radius_km)
+                for k, (seg, sign) in enumerate(chain):
+                    q.bodies[b].chain_segment[k], q.bodies[b].chain_sign[k] = seg, sign
+            for k in range(q.n_params):   # (_param_series stored the pairs' codes; the bodies ride in a list of their own)
+                q.param_body[k] = of_body.pop(0)
+
+        cap = int(capacity) if capacity is not None else ric_capacity(traj, ref, int(step_ns), start_ns, end_ns)
+        epoch0 = np.zeros(traj.n, dtype=np.int64)
+        values, length = _param_series("traj_link", fn, self._h, _abi.LinkQuery, _abi.MAX_LINK_PARAMS, fill, traj, [int(c) for c, _ in codes], step_ns,
+                                       start_ns, end_ns, cap, ref=ref, epoch0=epoch0)
+        return values, length, epoch0
+
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                       capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
         """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
@@ -976,11 +1015,14 @@ class GpuContext:
         return out, stats
 
 
-def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity, groups=None):
-    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`, `traj_aer`, `traj_eclipse`, `traj_frame_values`) of the context `handle`
+def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity, groups=None,
+                  ref: Optional[_abi.TrajBatch] = None, epoch0: Optional[np.ndarray] = None):
+    """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`, `traj_aer`, `traj_eclipse`, `traj_frame_values`, `traj_link`) of the context `handle`
     over the parameter codes, `per_call` of them per launch: (values[len(codes), capacity, n], len[n]).  `query_cls` is the entry's query,
     `fill(q)` sets the fields that only this entry has.  `groups=(items, per_call, fill_group)` adds an outer axis (the stations of
-    `traj_aer`): `fill_group(q, some of the items)` names those of a launch, and the values are [len(items), len(codes), capacity, n]."""
+    `traj_aer`): `fill_group(q, some of the items)` names those of a launch, and the values are [len(items), len(codes), capacity, n].
+    `ref` (with `epoch0`, int64[n], filled by every launch) is the second batch of an entry that has one (`traj_link`: `ref`, its n
+    behind `traj`, the first epochs behind `len`); such an entry is given its `capacity`."""
     if (start_ns is None) != (end_ns is None):
         raise ValueError(f"{name}: a window needs both start_ns and end_ns")
     cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
@@ -988,6 +1030,10 @@ def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _
     values = np.empty((len(items), len(codes), max(cap, 0), traj.n), dtype=np.float64)
     length = np.zeros(traj.n, dtype=np.int32)
     cin = traj.as_c()
+    second, tail = [], []
+    if ref is not None:
+        cref = ref.as_c()
+        second, tail = [C.byref(cref), ref.n], [epoch0.ctypes.data_as(_abi.c_int64_p)]
     for g0 in range(0, len(items), per_group):
         group = items[g0:g0 + per_group]
         for lo in range(0, len(codes), per_call):
@@ -1004,7 +1050,7 @@ def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _
             whole = groups is None or len(chunk) == len(codes)
             block = values[g0:g0 + len(group), lo:lo + len(chunk)]
             part = block if whole else np.empty(block.shape)
-            rc = fn(handle, C.byref(cin), traj.n, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p))
+            rc = fn(handle, C.byref(cin), traj.n, *second, C.byref(q), cap, part.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p), *tail)
             if rc != 0:
                 raise RuntimeError(f"nyx_hip_{name} failed (rc={rc}): {_abi.last_error()}")
             if not whole:
@@ -1346,6 +1392,16 @@ class Traj:
         (between `start_ns` and `end_ns` when given): `to_frame` and the parameter evaluation about the target, resampled and
         evaluated on the device (GpuContext.traj_frame_values)."""
         return self._series(self._ctx.traj_frame_values(self._single(), target, list(params), int(step_ns), start_ns, end_ns), step_ns, start_ns, end_ns)
+
+    def link_view(self, other: "Traj", step_ns: int, params=links.DEFAULT_PARAMS, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
+                  bodies=None):
+        """(epochs[K], values[P, K]) of the link from the transmitter `other` to this trajectory, the receiver, every `step_ns` over
+        the overlap of the two (between `start_ns` and `end_ns` when given): by default range, range rate and whether the centre
+        blocks the line - what `InterlinkTxSpacecraft::measure_instantaneous` (od/interlink/trk_device.rs) reads, without noise or
+        light time -, both resampled and evaluated on the device (GpuContext.traj_link)."""
+        values, length, epoch0 = self._ctx.traj_link(self._single(), other._single(), list(params), int(step_ns), start_ns, end_ns, bodies=bodies)
+        k = int(length[0])
+        return int(epoch0[0]) + int(step_ns) * np.arange(k, dtype=np.int64), values[:, :k, 0].copy()
 
     def to_frame(self, target: "Frame") -> "Traj":
         """`Traj::to_frame` (sc_traj.rs:88-129) between two frames of one orientation, on the host: the STORED states at their stored
