@@ -386,6 +386,23 @@ class LinkQuery(C.Structure):
                 ("bodies", EclBody * MAX_LINK_BODIES)]
 
 
+# include/nyx_hip_stats.h: the statistics of a report's values block
+STATS_VERSION = 1
+STAT_FIXED = 10
+MAX_STAT_PROBS = 8
+# enum nyx_hip_series_kind: the report nyx_hip_traj_series_stats runs
+SERIES_VALUES, SERIES_GROUND_TRACK, SERIES_AER, SERIES_ECLIPSE, SERIES_FRAME, SERIES_LINK, SERIES_RIC, SERIES_COUNT = range(8)
+
+
+# the kind of the report behind every GpuContext.traj_* method
+SERIES_KINDS = {"traj_values": SERIES_VALUES, "traj_ground_track": SERIES_GROUND_TRACK, "traj_aer": SERIES_AER, "traj_eclipse": SERIES_ECLIPSE,
+                "traj_frame_values": SERIES_FRAME, "traj_link": SERIES_LINK, "traj_ric_diff": SERIES_RIC}
+
+
+class StatsQuery(C.Structure):
+    _fields_ = [("n_probs", C.c_int32), ("reserved", C.c_int32), ("prob", C.c_double * MAX_STAT_PROBS)]
+
+
 class TrajBatch:
     """Dense output of a batch: entry k of trajectory i at [k, i]; k = 0 is the start state (step-major, as the ABI)."""
 
@@ -558,6 +575,9 @@ FRAME_EXPORTS = ["nyx_hip_traj_frame_values", "nyx_hip_traj_frame_values_device"
 # the entries of include/nyx_hip_link.h, likewise
 LINK_EXPORTS = ["nyx_hip_traj_link", "nyx_hip_traj_link_device", "nyx_hip_link_sizeof"]
 
+# the entries of include/nyx_hip_stats.h, likewise
+STATS_EXPORTS = ["nyx_hip_series_stats", "nyx_hip_series_stats_device", "nyx_hip_traj_series_stats", "nyx_hip_stats_sizeof"]
+
 # the parameter-series entries nyx_hip_traj_<name>, nyx_hip_traj_<name>_device and nyx_hip_<sizeof>_sizeof share one signature but for the
 # query: name -> (sizeof, query, what a library built before them lacks - None: every library has them)
 SERIES_ENTRIES = {"values": ("reports", ValuesQuery, None), "ground_track": ("groundtrack", GtQuery, "the ground tracks"),
@@ -657,6 +677,17 @@ def load_library():
         raise RuntimeError(f"{lib_path()}: nyx_hip_frame_query_t is {lib.nyx_hip_frame_sizeof(0)} bytes, the ctypes mirror {C.sizeof(FrameQuery)}")
     if getattr(lib, "nyx_hip_link_sizeof", None) is not None and lib.nyx_hip_link_sizeof(0) != C.sizeof(LinkQuery):
         raise RuntimeError(f"{lib_path()}: nyx_hip_link_query_t is {lib.nyx_hip_link_sizeof(0)} bytes, the ctypes mirror {C.sizeof(LinkQuery)}")
+    if getattr(lib, "nyx_hip_stats_sizeof", None) is not None:   # (absent from a library built before the statistics)
+        lib.nyx_hip_series_stats.argtypes = [C.c_void_p, c_double_p, c_int32_p, c_int32_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(StatsQuery), c_double_p]
+        lib.nyx_hip_series_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(StatsQuery),
+                                                    C.c_void_p, C.c_void_p]
+        lib.nyx_hip_traj_series_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Traj), C.c_int64, C.POINTER(Traj), C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                  c_int32_p, C.POINTER(StatsQuery), c_double_p, c_int32_p, c_int64_p]
+        lib.nyx_hip_stats_sizeof.argtypes = [C.c_int32]
+        for n in STATS_EXPORTS:
+            getattr(lib, n).restype = C.c_int32
+        if lib.nyx_hip_stats_sizeof(0) != C.sizeof(StatsQuery):
+            raise RuntimeError(f"{lib_path()}: nyx_hip_stats_query_t is {lib.nyx_hip_stats_sizeof(0)} bytes, the ctypes mirror {C.sizeof(StatsQuery)}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -690,6 +721,29 @@ def frame_entry(lib, name: str = "nyx_hip_traj_frame_values"):
 
 def link_entry(lib, name: str = "nyx_hip_traj_link"):
     return _series_entry(lib, name, "link")           # (include/nyx_hip_link.h)
+
+
+def stats_entry(lib, name: str = "nyx_hip_series_stats"):
+    """An entry of include/nyx_hip_stats.h, or a clear error when the loaded library predates it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the ensemble statistics were added - rebuild the HIP extension "
+                           "(python -c 'import __graft_entry__ as g; g.build()')")
+    return fn
+
+
+def stats_query(probs) -> StatsQuery:
+    """The StatsQuery of `probs`; what the library would refuse is refused here with the same words."""
+    probs = [float(p) for p in probs]
+    if len(probs) > MAX_STAT_PROBS:
+        raise ValueError(f"series_stats: n_probs = {len(probs)}, 0 .. {MAX_STAT_PROBS} probabilities per call")
+    for j, p in enumerate(probs):
+        if not 0.0 <= p <= 1.0:   # (a NaN fails both)
+            raise ValueError(f"series_stats: prob[{j}] must lie in [0, 1]")
+    q = StatsQuery()
+    q.n_probs = len(probs)
+    q.prob[:len(probs)] = probs
+    return q
 
 
 def last_error() -> str:

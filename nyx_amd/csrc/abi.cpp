@@ -35,6 +35,7 @@
 #include "frame_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
+#include "stats_host.h"
 #include "run_host.h"
 
 extern "C" size_t nyx_kernel_lds_bytes(int n_waves, int rec_doubles, int stm, int reuse_fields);
@@ -49,6 +50,7 @@ extern "C" hipError_t nyx_launch_traj_aer(const AerArgs *args, hipStream_t strea
 extern "C" hipError_t nyx_launch_traj_eclipse(const EclArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_frame_values(const FrmArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_link(const LnkArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
+extern "C" hipError_t nyx_launch_series_stats(const StatArgs *args, int64_t n_rows, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
 extern "C" hipError_t nyx_launch_frame_shift(const DevCfg *cfg, const double *records, const int32_t *chain_seg, const double *chain_sign,
                                              int n_chain, int64_t n, const int64_t *epoch_ns, double *x, double *y, double *z, double *vx,
@@ -1445,6 +1447,123 @@ extern "C" int32_t nyx_hip_traj_link(nyx_hip_ctx *ctx, const nyx_hip_traj_t *tra
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *tx, const SeriesOut &d) {
                            return nyx_hip_traj_link_device(ctx, src, n, tx, n_ref, q, capacity, d.values, d.len, d.epoch0, nullptr);
                        });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ensemble statistics of a report (include/nyx_hip_stats.h): stats_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_stats_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_stats_query_t);
+    case 1: return NYX_HIP_STATS_VERSION;
+    case 2: return NYX_HIP_STAT_FIXED;
+    case 3: return NYX_HIP_MAX_STAT_PROBS;
+    case 4: return NYX_HIP_SERIES_COUNT;
+    default: return -1;
+    }
+}
+
+// (n == 0 is launched: every (row, sample) gets the empty pattern)
+extern "C" int32_t nyx_hip_series_stats_device(nyx_hip_ctx *ctx, const double *values, const int32_t *len, const int32_t *status, int64_t n_rows,
+                                               int64_t capacity, int64_t n, const nyx_hip_stats_query_t *q, double *stats, void *hip_stream) {
+    if (Refusal r = check_series_stats(ctx, values, len, n_rows, capacity, n, q, stats)) return refused(r);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    StatArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.values = values; a.len = len; a.status = status; a.stats = stats; a.capacity = capacity; a.n = (int32_t)n; a.q = *q;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_series_stats(&a, n_rows, stream); });
+}
+
+extern "C" int32_t nyx_hip_series_stats(nyx_hip_ctx *ctx, const double *values, const int32_t *len, const int32_t *status, int64_t n_rows,
+                                        int64_t capacity, int64_t n, const nyx_hip_stats_query_t *q, double *stats) {
+    if (Refusal r = check_series_stats(ctx, values, len, n_rows, capacity, n, q, stats)) return refused(r);
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const StatsBlock b = stats_block(n_rows, capacity, n, q->n_probs, status != nullptr);
+    DevBuf blk;
+    if (int rc = blk.alloc(b.total)) return rc;
+    char *base = blk.as<char>();
+    if (b.values) HIP_TRY(hipMemcpy(base + b.values_at, values, b.values, hipMemcpyHostToDevice));
+    if (b.len) HIP_TRY(hipMemcpy(base + b.len_at, len, b.len, hipMemcpyHostToDevice));
+    if (b.status) HIP_TRY(hipMemcpy(base + b.status_at, status, b.status, hipMemcpyHostToDevice));
+    if (int rc = nyx_hip_series_stats_device(ctx, (const double *)(base + b.values_at), (const int32_t *)(base + b.len_at),
+                                             b.status ? (const int32_t *)(base + b.status_at) : nullptr, n_rows, capacity, n, q,
+                                             (double *)(base + b.stats_at), nullptr))
+        return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("statistics kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    HIP_TRY(hipMemcpy(stats, base + b.stats_at, b.stats, hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
+
+// the refusals of the report itself, by its own check function (`values` / `len`: any non-null pointers, none is read)
+static Refusal check_kind(const nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                          const void *query, int64_t capacity, const double *values, const int32_t *len) {
+    switch (kind) {
+    case NYX_HIP_SERIES_VALUES: return check_values_series(ctx, traj, n, (const nyx_hip_values_query_t *)query, capacity, values, len);
+    case NYX_HIP_SERIES_GROUND_TRACK: return check_gt_series(ctx, traj, n, (const nyx_hip_gt_query_t *)query, capacity, values, len);
+    case NYX_HIP_SERIES_AER: return check_aer_series(ctx, traj, n, (const nyx_hip_aer_query_t *)query, capacity, values, len);
+    case NYX_HIP_SERIES_ECLIPSE: return check_ecl(ctx, traj, n, (const nyx_hip_ecl_query_t *)query, capacity, values, len);
+    case NYX_HIP_SERIES_FRAME: return check_frame(ctx, traj, n, (const nyx_hip_frame_query_t *)query, capacity, values, len);
+    case NYX_HIP_SERIES_LINK: return check_link(ctx, traj, n, ref, n_ref, (const nyx_hip_link_query_t *)query, capacity, values, len);
+    default: return check_ric_series(ctx, traj, n, ref, n_ref, (const nyx_hip_ric_query_t *)query, capacity, values, len);
+    }
+}
+
+// the *_device entry of the report, on the default stream
+static int kind_device(nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                       const void *query, int64_t capacity, double *values, int32_t *len, int64_t *epoch0) {
+    switch (kind) {
+    case NYX_HIP_SERIES_VALUES: return nyx_hip_traj_values_device(ctx, traj, n, (const nyx_hip_values_query_t *)query, capacity, values, len, nullptr);
+    case NYX_HIP_SERIES_GROUND_TRACK: return nyx_hip_traj_ground_track_device(ctx, traj, n, (const nyx_hip_gt_query_t *)query, capacity, values, len, nullptr);
+    case NYX_HIP_SERIES_AER: return nyx_hip_traj_aer_device(ctx, traj, n, (const nyx_hip_aer_query_t *)query, capacity, values, len, nullptr);
+    case NYX_HIP_SERIES_ECLIPSE: return nyx_hip_traj_eclipse_device(ctx, traj, n, (const nyx_hip_ecl_query_t *)query, capacity, values, len, nullptr);
+    case NYX_HIP_SERIES_FRAME: return nyx_hip_traj_frame_values_device(ctx, traj, n, (const nyx_hip_frame_query_t *)query, capacity, values, len, nullptr);
+    case NYX_HIP_SERIES_LINK: return nyx_hip_traj_link_device(ctx, traj, n, ref, n_ref, (const nyx_hip_link_query_t *)query, capacity, values, len, epoch0, nullptr);
+    default: return nyx_hip_traj_ric_diff_device(ctx, traj, n, ref, n_ref, (const nyx_hip_ric_query_t *)query, capacity, values, len, epoch0, nullptr, nullptr);
+    }
+}
+
+// The fused host entry: the trajectories staged as series_host stages them, the report's device entry into a device block, the reducer
+// behind it on the same stream; only the statistics, the lengths and the first epochs come back.
+extern "C" int32_t nyx_hip_traj_series_stats(nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref,
+                                             int64_t n_ref, const void *query, int64_t query_size, int64_t capacity, const int32_t *status,
+                                             const nyx_hip_stats_query_t *sq, double *stats, int32_t *len, int64_t *epoch0_ns) {
+    if (Refusal r = check_traj_series_stats(ctx, kind, traj, ref, query, query_size, sq, stats, len)) return refused(r);
+    if (Refusal r = check_kind(ctx, kind, traj, n, ref, n_ref, query, capacity, stats, len)) return refused(r);
+    if (n > INT32_MAX) return refused(bad_arg("traj_series_stats: n must be 0 .. 2^31 - 1"));
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t rows = series_kind_rows(kind, query);
+    const StatsBlock b = stats_block(rows, capacity, n, sq->n_probs, status != nullptr);
+    DevTraj src, second;
+    DevBuf blk, first;
+    if (n > 0) {
+        if (int rc = src.alloc(traj->capacity, n)) return rc;
+        if (int rc = src.upload(traj)) return rc;
+        if (ref) {
+            if (int rc = second.alloc(ref->capacity, n_ref)) return rc;
+            if (int rc = second.upload(ref)) return rc;
+        }
+    }
+    if (int rc = blk.alloc(b.total)) return rc;
+    char *base = blk.as<char>();
+    double *d_values = (double *)(base + b.values_at), *d_stats = (double *)(base + b.stats_at);
+    int32_t *d_len = (int32_t *)(base + b.len_at), *d_status = b.status ? (int32_t *)(base + b.status_at) : nullptr;
+    const size_t first_bytes = (ref && epoch0_ns) ? (size_t)n * sizeof(int64_t) : 0;
+    if (first_bytes)
+        if (int rc = first.alloc(first_bytes)) return rc;
+    if (b.status) HIP_TRY(hipMemcpy(d_status, status, b.status, hipMemcpyHostToDevice));
+    if (n > 0)
+        if (int rc = kind_device(ctx, kind, &src.t, n, ref ? &second.t : nullptr, n_ref, query, capacity, d_values, d_len, first.as<int64_t>())) return rc;
+    if (int rc = nyx_hip_series_stats_device(ctx, d_values, d_len, d_status, rows, capacity, n, sq, d_stats, nullptr)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("report or statistics kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    HIP_TRY(hipMemcpy(stats, d_stats, b.stats, hipMemcpyDeviceToHost));
+    if (b.len) HIP_TRY(hipMemcpy(len, d_len, b.len, hipMemcpyDeviceToHost));
+    if (first_bytes) HIP_TRY(hipMemcpy(epoch0_ns, first.p, first_bytes, hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

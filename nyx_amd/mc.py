@@ -35,6 +35,7 @@ from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, EclipseParameter, check_
 from .frames import FrameParameter, check_target, frame_param, frame_value
 from .links import DEFAULT_PARAMS as LINK_DEFAULT, LinkParameter, check_link_bodies, default_bodies, link_param, link_value, outside_ephemerides
 from .propagator import Almanac, Propagator, Spacecraft, Traj, ric_bounds, series_bounds
+from . import stats as series_statistics
 
 # indices into the 9-vector [x, y, z, vx, vy, vz, Cr, Cd, prop mass] (cosmic/spacecraft.rs:451-473)
 STATE_DIM = 9
@@ -483,6 +484,39 @@ def _fill_head(head: np.ndarray, k: int, n_k: int, first_epoch_ns) -> None:
 
 
 RIC_TRIU = np.triu_indices(6)
+RIC_ROWS = ("dR", "dI", "dC", "dvR", "dvI", "dvC")
+
+# the array reports `Results.series_stats` serves, and the evaluator's entry behind each
+SERIES_REPORTS = {"values_of": "traj_values", "ric_dispersions": "traj_ric_diff", "ground_tracks": "traj_ground_track", "station_views": "traj_aer",
+                  "eclipses": "traj_eclipse", "frame_values": "traj_frame_values", "link_views": "traj_link"}
+
+
+class _StatsTap:
+    """The evaluator of a Results for the length of one `series_stats`: everything is the evaluator's own but `entry`, which is
+    called with `stats=` - the statistics (`stats`, `length`, `epoch0`) stay here, and the report that called gets an empty series
+    of the right shape, so that nothing else of it has to know."""
+
+    def __init__(self, ctx, entry: str, request):
+        self._ctx, self._entry, self._request = ctx, entry, request
+        self.stats = self.length = self.epoch0 = None
+
+    def __getattr__(self, name):
+        return getattr(self._ctx, name)
+
+    def _tapped(self, tb, *args, **kwargs):
+        kwargs.pop("moments", None)                          # (RIC's own sums are not asked for through the statistics)
+        got = getattr(self._ctx, self._entry)(tb, *args, stats=self._request, **kwargs)
+        self.stats, self.length = got[0], got[1]
+        with_ref = self._entry in ("traj_link", "traj_ric_diff")
+        self.epoch0 = got[2] if with_ref else series_bounds(tb, args[-2], args[-1])[0]
+        none = np.empty(self.stats.shape[:-2] + (0, tb.n)), np.zeros(tb.n, dtype=np.int32)
+        if self._entry == "traj_ric_diff":
+            return none + (self.epoch0, np.zeros((0, _abi.RIC_MOMENTS)))
+        return none + ((self.epoch0,) if with_ref else ())
+
+
+for _entry in SERIES_REPORTS.values():
+    setattr(_StatsTap, _entry, _StatsTap._tapped)
 
 
 def ric_moments(cols, k_max: int) -> np.ndarray:
@@ -1098,6 +1132,50 @@ class Results:
 
         values, length, epoch0, ok, _, _ = self._series("link_views", len(params), np.nan, start_ns, end_ns, check, "traj_link", fused, composed)
         return LinkSeries(list(who), params, values, length, epoch0, step, ok)
+
+    def series_stats(self, report: str, *args, probs=(), **kwargs) -> "series_statistics.SeriesStats":
+        """The statistics over the runs of one of the array reports (`report`: "values_of", "ric_dispersions", "ground_tracks",
+        "station_views", "eclipses", "frame_values" or "link_views", with the arguments of that report): per row and sample the
+        runs that hold it, the extremes and which runs they are, the sums behind mean and sigma and the exact quantiles `probs` ->
+        stats.SeriesStats (include/nyx_hip_stats.h; nyx_amd/stats.py is the definition).  A failed run is left out.
+
+        With a device evaluator, an ensemble that is not sharded and rows that all come from the device (no Cr, Cd or mass column
+        of `values_of`) the report and the reduction run back to back on the device (`nyx_hip_traj_series_stats`) and only the
+        statistics are copied back.  Otherwise - the injected CPU evaluators of the tests, a sharded ensemble on every rank - the
+        named report as it is, then `stats.series_stats` on its values: that composition is the definition, the device path is
+        tested against it.  Quantiles do not all-reduce: a distributed selection is out of scope."""
+        if report not in SERIES_REPORTS:
+            raise ValueError(f"series_stats: report must be one of {sorted(SERIES_REPORTS)}, not {report!r}")
+        probs = tuple(float(p) for p in series_statistics.check_probs(probs))
+        entry = SERIES_REPORTS[report]
+        ctx = self._traj_ctx
+        sharded = self._dist is not None and self._dist.get_world_size() > 1
+        device_rows = report != "values_of" or all(getattr(p, "name", None) in _abi.STATE_PARAM for p in (args[0] if args else kwargs.get("params", ())))
+        tap = None
+        if hasattr(ctx, "series_stats") and hasattr(ctx, entry) and not sharded and device_rows and self._traj_batch is not None:
+            status = np.ones(self._traj_batch.n, dtype=np.int32)
+            status[[self._traj_rows[r.index] for r in self.runs if isinstance(r.result, PropResult)]] = 0
+            tap = _StatsTap(ctx, entry, series_statistics.Request(probs, status))
+            self._traj_ctx = tap
+        try:
+            series = getattr(self, report)(*args, **kwargs)
+        finally:
+            self._traj_ctx = ctx
+        if report == "station_views":
+            rows = [(st, p) for st in series.stations for p in series.params]
+        else:
+            rows = list(series.params) if hasattr(series, "params") else list(RIC_ROWS)
+        if tap is not None and tap.stats is not None:
+            live = status == 0
+            k_max = int(np.minimum(tap.length[live], tap.stats.shape[-2]).max()) if live.any() else 0
+            got = tap.stats.reshape(len(rows), tap.stats.shape[-2], tap.stats.shape[-1])[:, :k_max]
+            first = tap.epoch0[live & (tap.length > 0)]
+        else:
+            values = series.values.reshape(len(rows), -1, series.values.shape[-1])
+            got = series_statistics.series_stats(values, series.len, probs, status=(~np.asarray(series.ok)).astype(np.int32))
+            first = series.epoch0_ns[np.asarray(series.ok) & (series.len > 0)]
+        same = len(first) > 0 and bool((first == first[0]).all())
+        return series_statistics.SeriesStats(got, rows, probs, step_ns=series.step_ns, epoch0_ns=int(first[0]) if same else None)
 
     def first_values_of(self, param: StateParameter, value_if_run_failed: Optional[float] = None) -> List[float]:
         """results.rs:162-190."""

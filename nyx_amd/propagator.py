@@ -35,6 +35,7 @@ from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_station
 from . import frames
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
 from . import links
+from . import stats as series_statistics
 
 NS_PER_S = 1_000_000_000
 SPEED_OF_LIGHT_KM_S = 299_792.458  # anise::constants::SPEED_OF_LIGHT_KM_S (reference cosmic/mod.rs:179-180)
@@ -820,45 +821,73 @@ class GpuContext:
             raise RuntimeError(f"nyx_hip_traj_every failed (rc={rc}): {_abi.last_error()}")
         return out
 
+    def series_stats(self, values, length, probs=(), status=None) -> np.ndarray:
+        """``nyx_hip_series_stats`` (include/nyx_hip_stats.h), the host flavour: the statistics over the runs of a values block
+        `values[R, K, n]` of any series report with its `length[n]` - per row and sample HELD, COUNT, MIN, MAX, ARGMIN, ARGMAX,
+        FINITE, SHIFT, SUM, SUMSQ (stats.Stat) and the exact quantiles `probs`: stats[R, K, 10 + len(probs)], as
+        `stats.series_stats` defines them.  A run with `status[i] != 0` is left out."""
+        fn = _abi.stats_entry(self._lib)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        if values.ndim != 3:
+            raise ValueError("series_stats: values must be [rows, capacity, n]")
+        rows, cap, n = values.shape
+        length = np.ascontiguousarray(length, dtype=np.int32).reshape(-1)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+        if len(length) != n or (status is not None and len(status) != n):
+            raise ValueError("series_stats: length and status hold one entry per run")
+        sq = _abi.stats_query(probs)
+        out = np.empty((rows, cap, _abi.STAT_FIXED + sq.n_probs), dtype=np.float64)
+        rc = fn(self._h, values.ctypes.data_as(_abi.c_double_p), length.ctypes.data_as(_abi.c_int32_p),
+                None if status is None else status.ctypes.data_as(_abi.c_int32_p), rows, cap, n, C.byref(sq), out.ctypes.data_as(_abi.c_double_p))
+        if rc != 0:
+            raise RuntimeError(f"nyx_hip_series_stats failed (rc={rc}): {_abi.last_error()}")
+        return out
+
     def traj_values(self, traj: _abi.TrajBatch, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
-                    capacity: Optional[int] = None, mu_km3_s2: Optional[float] = None):
+                    capacity: Optional[int] = None, mu_km3_s2: Optional[float] = None, stats=None):
         """``nyx_hip_traj_values`` (include/nyx_hip_reports.h): the orbit-derived `params` (StateParameter members) of every
         trajectory of the batch every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given -
         resampled and evaluated on the device in one pass: (values[P, capacity, n], len[n]).  `len[i]` counts the samples
         produced for trajectory i; slots from `len[i]` on are NaN.  `capacity=None` sizes the series from the batch's epochs;
-        `mu_km3_s2=None` is the context's central body.  More than eight parameters take several launches."""
+        `mu_km3_s2=None` is the context's central body.  More than eight parameters take several launches.  With `stats=` (probabilities, or a
+        stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in place of the values:
+        [.., capacity, 10 + len(probs)], reduced on the device."""
         codes = [report_param_code(p) for p in params]
 
         def fill(q):
             q.mu_km3_s2 = 0.0 if mu_km3_s2 is None else float(mu_km3_s2)   # (<= 0: the context's central body)
 
         return _param_series("traj_values", self._lib.nyx_hip_traj_values, self._h, _abi.ValuesQuery, _abi.MAX_REPORT_PARAMS, fill, traj, codes,
-                                  step_ns, start_ns, end_ns, capacity)
+                                  step_ns, start_ns, end_ns, capacity, stats=stats)
 
     def traj_ground_track(self, traj: _abi.TrajBatch, frame: "Frame", params, step_ns: int, start_ns: Optional[int] = None,
-                          end_ns: Optional[int] = None, capacity: Optional[int] = None):
+                          end_ns: Optional[int] = None, capacity: Optional[int] = None, stats=None):
         """``nyx_hip_traj_ground_track`` (include/nyx_hip_groundtrack.h): the `params` (GroundTrackParameter members) of every
         trajectory of the batch every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given -
         resampled, expressed in the body-fixed `frame` at each sample's epoch and evaluated on the device in one pass:
         (values[P, capacity, n], len[n]).  `len[i]` counts the samples produced for trajectory i; slots from `len[i]` on are
         NaN.  `frame` is an IAU-oriented frame of the context's centre (`frame.rotation is None`: the inertial state itself);
-        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches."""
+        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches.  With `stats=` (probabilities, or a
+        stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in place of the values:
+        [.., capacity, 10 + len(probs)], reduced on the device."""
         fn = _abi.ground_track_entry(self._lib)
         params = list(params)
         codes = [gt_param_code(p) for p in params]
         check_frame(frame, self.compiled.central.naif_id, params)
         return _param_series("traj_ground_track", fn, self._h, _abi.GtQuery, _abi.MAX_GT_PARAMS, lambda q: fill_gt_frame(q, frame), traj, codes,
-                                  step_ns, start_ns, end_ns, capacity)
+                                  step_ns, start_ns, end_ns, capacity, stats=stats)
 
     def traj_aer(self, traj: _abi.TrajBatch, stations, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
-                 capacity: Optional[int] = None):
+                 capacity: Optional[int] = None, stats=None):
         """``nyx_hip_traj_aer`` (include/nyx_hip_aer.h): the `params` (AerParameter members) of every trajectory of the batch seen
         from every one of `stations` (GroundStation, all of one IAU-oriented frame of the context's centre) every `step_ns` -
         `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given - resampled, expressed in the stations' frame
         at each sample's epoch and evaluated on the device in one pass, one interpolation and one rotation per sample serving all
         stations: (values[S, P, capacity, n], len[n]).  `len[i]` counts the samples produced for trajectory i (the same for every
         station); slots from `len[i]` on are NaN.  `capacity=None` sizes the series from the batch's epochs.  More than eight
-        parameters or sixteen stations take several launches."""
+        parameters or sixteen stations take several launches.  With `stats=` (probabilities, or a
+        stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in place of the values:
+        [.., capacity, 10 + len(probs)], reduced on the device."""
         fn = _abi.aer_entry(self._lib)
         stations, params = list(stations), list(params)
         codes = [aer_param_code(p) for p in params]
@@ -873,17 +902,19 @@ class GpuContext:
                 q.stations[k].height_km, q.stations[k].elevation_mask_deg = float(st.height_km), float(st.elevation_mask_deg)
 
         return _param_series("traj_aer", fn, self._h, _abi.AerQuery, _abi.MAX_AER_PARAMS, lambda q: fill_gt_frame(q, frame), traj, codes, step_ns, start_ns,
-                             end_ns, capacity, groups=(stations, _abi.MAX_STATIONS, fill_stations))
+                             end_ns, capacity, groups=(stations, _abi.MAX_STATIONS, fill_stations), stats=stats)
 
     def traj_eclipse(self, traj: _abi.TrajBatch, model, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
-                     capacity: Optional[int] = None):
+                     capacity: Optional[int] = None, stats=None):
         """``nyx_hip_traj_eclipse`` (include/nyx_hip_eclipse.h): the `params` of the shadow `model` (eclipse.ShadowModel) for every
         trajectory of the batch every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` / `end_ns` are given -
         resampled, the ephemerides of the almanac this context was compiled from evaluated at each sample's epoch, the occultation
         and the parameters evaluated on the device in one pass: (values[P, capacity, n], len[n]).  A parameter is an
         EclipseParameter, a per-body one a pair `(EclipseParameter.BodyOccultation, frame_or_index)`.  `len[i]` counts the samples
         produced for trajectory i; slots from `len[i]` on are NaN; a sample outside the ephemerides ends the series.
-        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches."""
+        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches.  With `stats=` (probabilities, or a
+        stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in place of the values:
+        [.., capacity, 10 + len(probs)], reduced on the device."""
         fn = _abi.eclipse_entry(self._lib)
         almanac, central = self.compiled.almanac, self.compiled.central
         if almanac is None:
@@ -909,10 +940,10 @@ class GpuContext:
 
         bodies = [b for _, b in codes]
         return _param_series("traj_eclipse", fn, self._h, _abi.EclQuery, _abi.MAX_ECL_PARAMS, fill, traj, [c for c, _ in codes], step_ns, start_ns,
-                             end_ns, capacity)
+                             end_ns, capacity, stats=stats)
 
     def traj_frame_values(self, traj: _abi.TrajBatch, target: "Frame", params, step_ns: int, start_ns: Optional[int] = None,
-                          end_ns: Optional[int] = None, capacity: Optional[int] = None):
+                          end_ns: Optional[int] = None, capacity: Optional[int] = None, stats=None):
         """``nyx_hip_traj_frame_values`` (include/nyx_hip_frame.h): the `params` (FrameParameter members, or the orbit-derived
         StateParameter of the same name) of every trajectory of the batch SEEN FROM `target` - a Frame of the context's orientation
         with another ephemeris id and its own mu - every `step_ns` - `Traj::every`, or `Traj::every_between` when `start_ns` /
@@ -920,7 +951,9 @@ class GpuContext:
         sample's epoch and subtracted (`Traj::to_frame`), the parameters evaluated about the target on the device in one pass:
         (values[P, capacity, n], len[n]).  `len[i]` counts the samples produced for trajectory i; slots from `len[i]` on are NaN; a
         sample outside the ephemerides ends the series, a sample that is not hyperbolic has NaN B-plane values and does not.
-        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches."""
+        `capacity=None` sizes the series from the batch's epochs.  More than eight parameters take several launches.  With `stats=` (probabilities, or a
+        stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in place of the values:
+        [.., capacity, 10 + len(probs)], reduced on the device."""
         fn = _abi.frame_entry(self._lib)
         almanac, central = self.compiled.almanac, self.compiled.central
         if almanac is None:
@@ -936,10 +969,10 @@ class GpuContext:
                 q.chain_segment[k], q.chain_sign[k] = seg, sign
 
         return _param_series("traj_frame_values", fn, self._h, _abi.FrameQuery, _abi.MAX_FRAME_PARAMS, fill, traj, codes, step_ns, start_ns, end_ns,
-                             capacity)
+                             capacity, stats=stats)
 
     def traj_link(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
-                  capacity: Optional[int] = None, bodies=None):
+                  capacity: Optional[int] = None, bodies=None, stats=None):
         """``nyx_hip_traj_link`` (include/nyx_hip_link.h): the `params` of the link from the transmitter `ref` (one trajectory for all,
         or one per run) to every trajectory of `traj`, the receivers, every `step_ns` over the overlap of the two spans (clamped to
         `start_ns` / `end_ns` when given) - both resampled, the `bodies` that can block the line (Frames; None: the context's centre
@@ -948,7 +981,9 @@ class GpuContext:
         (values[P, capacity, n], len[n], epoch0_ns[n]).  A parameter is a LinkParameter, a per-body one a pair
         `(LinkParameter.BodyClearance, frame_or_index)`.  `len[i]` counts the samples produced for run i; slots from `len[i]` on are
         NaN; a sample outside the ephemerides of a body ends the series.  `capacity=None` sizes the series from the epochs of the
-        two batches.  More than eight parameters take several launches.  An almanac is needed only when a body has a chain."""
+        two batches.  More than eight parameters take several launches.  An almanac is needed only when a body has a chain.  With `stats=` (probabilities, or a
+        stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in place of the values:
+        [.., capacity, 10 + len(probs)], reduced on the device."""
         fn = _abi.link_entry(self._lib)
         almanac, central = self.compiled.almanac, self.compiled.central
         bodies = links.default_bodies(central) if bodies is None else list(bodies)
@@ -973,17 +1008,20 @@ class GpuContext:
         cap = int(capacity) if capacity is not None else ric_capacity(traj, ref, int(step_ns), start_ns, end_ns)
         epoch0 = np.zeros(traj.n, dtype=np.int64)
         values, length = _param_series("traj_link", fn, self._h, _abi.LinkQuery, _abi.MAX_LINK_PARAMS, fill, traj, [int(c) for c, _ in codes], step_ns,
-                                       start_ns, end_ns, cap, ref=ref, epoch0=epoch0)
+                                       start_ns, end_ns, cap, ref=ref, epoch0=epoch0, stats=stats)
         return values, length, epoch0
 
     def traj_ric_diff(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
-                      capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False):
+                      capacity: Optional[int] = None, frame_of="reference", transport: bool = True, smooth_window: int = 5, moments: bool = False, stats=None):
         """``nyx_hip_traj_ric_diff`` (include/nyx_hip_ric.h): the RIC difference of every trajectory of `traj` to `ref` (one
         trajectory for all, or one per run) every `step_ns` over the overlap of the two spans (clamped to `start_ns` / `end_ns`
         when given) - both resampled, differenced (params.ric_difference), median-filtered (params.smooth_ric; `smooth_window`
         0 or 1: not) on the device in one pass: (values[6, capacity, n], len[n], epoch0_ns[n], moments[capacity, 28] or None).
         `len[i]` counts the samples produced for run i, slots from there on are NaN; moments[k] = count, sum d, upper triangle of
-        sum d d^T over the runs that have sample k.  `capacity=None` sizes the series from the epochs of the two batches."""
+        sum d d^T over the runs that have sample k.  `capacity=None` sizes the series from the epochs of the two batches.  With
+        `stats=` (probabilities, or a stats.Request with the runs' status) the statistics of include/nyx_hip_stats.h come back in
+        place of the values, reduced on the device: (stats[6, capacity, 10 + len(probs)], len[n], epoch0_ns[n]); the 28 sums are
+        not asked for through it."""
         if (start_ns is None) != (end_ns is None):
             raise ValueError("traj_ric_diff: a window needs both start_ns and end_ns")
         if frame_of not in FRAME_OF:
@@ -998,6 +1036,18 @@ class GpuContext:
         if start_ns is not None:
             q.start_ns, q.end_ns = int(start_ns), int(end_ns)
         cin, cref = traj.as_c(), ref.as_c()
+        if stats is not None:
+            if moments:
+                raise ValueError("traj_ric_diff: stats= and moments= exclude each other")
+            sq, status = _stats_request(stats, traj.n)
+            out = np.empty((6, max(cap, 0), _abi.STAT_FIXED + sq.n_probs), dtype=np.float64)
+            rc = _abi.stats_entry(self._lib, "nyx_hip_traj_series_stats")(
+                self._h, _abi.SERIES_RIC, C.byref(cin), traj.n, C.byref(cref), ref.n, C.byref(q), C.sizeof(q), cap,
+                None if status is None else status.ctypes.data_as(_abi.c_int32_p), C.byref(sq), out.ctypes.data_as(_abi.c_double_p),
+                length.ctypes.data_as(_abi.c_int32_p), epoch0.ctypes.data_as(_abi.c_int64_p))
+            if rc != 0:
+                raise RuntimeError(f"nyx_hip_traj_series_stats failed (rc={rc}): {_abi.last_error()}")
+            return out, length, epoch0
         rc = self._lib.nyx_hip_traj_ric_diff(self._h, C.byref(cin), traj.n, C.byref(cref), ref.n, C.byref(q), cap, values.ctypes.data_as(_abi.c_double_p),
                                              length.ctypes.data_as(_abi.c_int32_p), epoch0.ctypes.data_as(_abi.c_int64_p),
                                              None if mom is None else mom.ctypes.data_as(_abi.c_double_p))
@@ -1016,24 +1066,36 @@ class GpuContext:
 
 
 def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _abi.TrajBatch, codes, step_ns: int, start_ns, end_ns, capacity, groups=None,
-                  ref: Optional[_abi.TrajBatch] = None, epoch0: Optional[np.ndarray] = None):
+                  ref: Optional[_abi.TrajBatch] = None, epoch0: Optional[np.ndarray] = None, stats=None):
     """The host flavour `fn` of a parameter series (`traj_values`, `traj_ground_track`, `traj_aer`, `traj_eclipse`, `traj_frame_values`, `traj_link`) of the context `handle`
     over the parameter codes, `per_call` of them per launch: (values[len(codes), capacity, n], len[n]).  `query_cls` is the entry's query,
     `fill(q)` sets the fields that only this entry has.  `groups=(items, per_call, fill_group)` adds an outer axis (the stations of
     `traj_aer`): `fill_group(q, some of the items)` names those of a launch, and the values are [len(items), len(codes), capacity, n].
     `ref` (with `epoch0`, int64[n], filled by every launch) is the second batch of an entry that has one (`traj_link`: `ref`, its n
-    behind `traj`, the first epochs behind `len`); such an entry is given its `capacity`."""
+    behind `traj`, the first epochs behind `len`); such an entry is given its `capacity`.  `stats` (a sequence of probabilities, or a
+    stats.Request with the runs' status) sends every launch through the fused `nyx_hip_traj_series_stats` instead: the last axis of
+    the result is then the 10 + len(probs) statistics of include/nyx_hip_stats.h, not the runs, and only they cross the bus."""
     if (start_ns is None) != (end_ns is None):
         raise ValueError(f"{name}: a window needs both start_ns and end_ns")
     cap = int(capacity) if capacity is not None else values_capacity(traj, int(step_ns), start_ns, end_ns)
     items, per_group, fill_group = groups if groups is not None else ([None], 1, None)
-    values = np.empty((len(items), len(codes), max(cap, 0), traj.n), dtype=np.float64)
+    width = traj.n
+    if stats is not None:
+        sq, status = _stats_request(stats, traj.n)
+        fused, width = _abi.stats_entry(_abi.load_library(), "nyx_hip_traj_series_stats"), _abi.STAT_FIXED + sq.n_probs
+    values = np.empty((len(items), len(codes), max(cap, 0), width), dtype=np.float64)
     length = np.zeros(traj.n, dtype=np.int32)
     cin = traj.as_c()
     second, tail = [], []
     if ref is not None:
         cref = ref.as_c()
         second, tail = [C.byref(cref), ref.n], [epoch0.ctypes.data_as(_abi.c_int64_p)]
+    if stats is not None:   # (the fused entry takes the second batch and the first epochs of every kind: null where there is none)
+        second, tail = second or [None, 0], tail or [None]
+
+        def fn(handle, cin, n, cref, n_ref, q, cap, part, length, epoch0):
+            return fused(handle, _abi.SERIES_KINDS[name], cin, n, cref, n_ref, q, C.sizeof(query_cls), cap,
+                         None if status is None else status.ctypes.data_as(_abi.c_int32_p), C.byref(sq), part, length, epoch0)
     for g0 in range(0, len(items), per_group):
         group = items[g0:g0 + per_group]
         for lo in range(0, len(codes), per_call):
@@ -1056,6 +1118,15 @@ def _param_series(name: str, fn, handle, query_cls, per_call: int, fill, traj: _
             if not whole:
                 block[...] = part
     return (values if groups is not None else values[0]), length
+
+
+def _stats_request(stats, n: int):
+    """(StatsQuery, status int32[n] or None) of a `stats=` keyword."""
+    req = series_statistics.request(stats)
+    status = None if req.status is None else np.ascontiguousarray(req.status, dtype=np.int32).reshape(-1)
+    if status is not None and len(status) != n:
+        raise ValueError(f"stats: status holds {len(status)} entries, the batch {n} runs")
+    return _abi.stats_query(req.probs), status
 
 
 def report_param_code(param) -> int:
