@@ -11,6 +11,7 @@ from .groundtrack import GroundTrackParameter, geodetic, ground_track_value, iau
 from .stations import AerParameter, GroundStation, aer_value, check_stations, station_consts  # noqa: F401,E402
 from .frames import FrameParameter, body_state, cheby_state, frame_value, to_frame  # noqa: F401,E402
 from .links import LinkParameter, check_link_bodies, link_value  # noqa: F401,E402
+from .lambert import LambertGrid, LambertParameter, LambertSolution, LambertStatus, TransferKind, grid_definition, izzo  # noqa: F401,E402
 from .stats import SeriesStats, Stat, series_stats  # noqa: F401,E402
 from .eclipse import EclipseParameter, ShadowModel, check_shadow_model, eclipse_value, state_changes  # noqa: F401,E402
 from .rng import Pcg64Mcg  # noqa: F401,E402

@@ -386,6 +386,33 @@ class LinkQuery(C.Structure):
                 ("bodies", EclBody * MAX_LINK_BODIES)]
 
 
+# ---- include/nyx_hip_lambert.h (Lambert transfers: a batch of problems, a departure x arrival grid) ----
+LAMBERT_VERSION = 1
+MAX_LAMBERT_PARAMS = 8
+# enum nyx_hip_lambert_param: the members of lambert.LambertParameter, by name
+LAMBERT_PARAM = {"V1X": 0, "V1Y": 1, "V1Z": 2, "V2X": 3, "V2Y": 4, "V2Z": 5, "X": 6, "Iterations": 7, "TofS": 8, "TransferAngleDeg": 9, "C3": 10,
+                 "VinfDep": 11, "DlaDeg": 12, "RlaDeg": 13, "VinfArr": 14, "DvTotal": 15}
+LAMBERT_COUNT = 16
+# enum nyx_hip_lambert_way (lambert.TransferKind) and enum nyx_hip_lambert_status (lambert.LambertStatus)
+LAMBERT_WAY = {"Auto": 0, "ShortWay": 1, "LongWay": 2}
+LAMBERT_STATUS = {"OK": 0, "BAD_INPUT": 1, "DEGENERATE": 2, "NOT_FEASIBLE": 3, "TOO_CLOSE": 4, "MAX_ITER": 5, "EPHEM_RANGE": 6}
+
+
+class LambertQuery(C.Structure):
+    _fields_ = [("n_params", C.c_int32), ("param", C.c_int32 * MAX_LAMBERT_PARAMS), ("way", C.c_int32), ("n_revs", C.c_int32), ("high_path", C.c_int32),
+                ("max_iter", C.c_int32), ("_pad", C.c_int32), ("tol", C.c_double)]
+
+
+class LambertChain(C.Structure):
+    _fields_ = [("n_chain", C.c_int32), ("chain_segment", C.c_int32 * MAX_CHAIN), ("chain_sign", C.c_int32 * MAX_CHAIN), ("_pad", C.c_int32)]
+
+
+class LambertGridQuery(C.Structure):
+    _fields_ = [("solve", LambertQuery), ("dep", LambertChain), ("arr", LambertChain), ("centre", LambertChain), ("has_tof", C.c_int32), ("_pad", C.c_int32),
+                ("n_dep", C.c_int64), ("n_arr", C.c_int64), ("dep0_ns", C.c_int64), ("dep_step_ns", C.c_int64), ("arr0_ns", C.c_int64),
+                ("arr_step_ns", C.c_int64), ("tof0_ns", C.c_int64), ("tof_step_ns", C.c_int64), ("mu_km3_s2", C.c_double)]
+
+
 # include/nyx_hip_stats.h: the statistics of a report's values block
 STATS_VERSION = 1
 STAT_FIXED = 10
@@ -575,6 +602,9 @@ FRAME_EXPORTS = ["nyx_hip_traj_frame_values", "nyx_hip_traj_frame_values_device"
 # the entries of include/nyx_hip_link.h, likewise
 LINK_EXPORTS = ["nyx_hip_traj_link", "nyx_hip_traj_link_device", "nyx_hip_link_sizeof"]
 
+# the entries of include/nyx_hip_lambert.h, likewise
+LAMBERT_EXPORTS = ["nyx_hip_lambert_batch", "nyx_hip_lambert_batch_device", "nyx_hip_lambert_grid", "nyx_hip_lambert_grid_device", "nyx_hip_lambert_sizeof"]
+
 # the entries of include/nyx_hip_stats.h, likewise
 STATS_EXPORTS = ["nyx_hip_series_stats", "nyx_hip_series_stats_device", "nyx_hip_traj_series_stats", "nyx_hip_stats_sizeof"]
 
@@ -688,6 +718,19 @@ def load_library():
             getattr(lib, n).restype = C.c_int32
         if lib.nyx_hip_stats_sizeof(0) != C.sizeof(StatsQuery):
             raise RuntimeError(f"{lib_path()}: nyx_hip_stats_query_t is {lib.nyx_hip_stats_sizeof(0)} bytes, the ctypes mirror {C.sizeof(StatsQuery)}")
+    if getattr(lib, "nyx_hip_lambert_sizeof", None) is not None:   # (absent from a library built before the Lambert transfers)
+        lib.nyx_hip_lambert_batch.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_double, C.POINTER(LambertQuery), c_double_p, c_int32_p]
+        lib.nyx_hip_lambert_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(LambertQuery), C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
+        lib.nyx_hip_lambert_grid.argtypes = [C.c_void_p, C.POINTER(LambertGridQuery), c_double_p, c_int32_p]
+        lib.nyx_hip_lambert_grid_device.argtypes = [C.c_void_p, C.POINTER(LambertGridQuery), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.nyx_hip_lambert_sizeof.argtypes = [C.c_int32]
+        for n in LAMBERT_EXPORTS:
+            getattr(lib, n).restype = C.c_int32
+        got = [lib.nyx_hip_lambert_sizeof(k) for k in (0, 4, 5)]
+        if got != [C.sizeof(LambertQuery), C.sizeof(LambertGridQuery), C.sizeof(LambertChain)]:
+            raise RuntimeError(f"{lib_path()}: the structs of nyx_hip_lambert.h are {got} bytes, the ctypes mirrors "
+                               f"{[C.sizeof(LambertQuery), C.sizeof(LambertGridQuery), C.sizeof(LambertChain)]}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -721,6 +764,15 @@ def frame_entry(lib, name: str = "nyx_hip_traj_frame_values"):
 
 def link_entry(lib, name: str = "nyx_hip_traj_link"):
     return _series_entry(lib, name, "link")           # (include/nyx_hip_link.h)
+
+
+def lambert_entry(lib, name: str = "nyx_hip_lambert_grid"):
+    """An entry of include/nyx_hip_lambert.h, or a clear error when the loaded library predates it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the Lambert transfers were added - rebuild the HIP extension "
+                           "(python -c 'import __graft_entry__ as g; g.build()')")
+    return fn
 
 
 def stats_entry(lib, name: str = "nyx_hip_series_stats"):

@@ -33,6 +33,7 @@
 #include "eclipse_args.h"
 #include "link_args.h"
 #include "frame_args.h"
+#include "lambert_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
 #include "stats_host.h"
@@ -49,6 +50,8 @@ extern "C" hipError_t nyx_launch_ground_track(const GroundTrackArgs *args, hipSt
 extern "C" hipError_t nyx_launch_traj_aer(const AerArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_eclipse(const EclArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_frame_values(const FrmArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
+extern "C" hipError_t nyx_launch_lambert_batch(const LmbBatchArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_lambert_grid(const LmbGridArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_link(const LnkArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_series_stats(const StatArgs *args, int64_t n_rows, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
@@ -1359,6 +1362,92 @@ extern "C" int32_t nyx_hip_traj_frame_values(nyx_hip_ctx *ctx, const nyx_hip_tra
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_frame_values_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Lambert transfers (include/nyx_hip_lambert.h): lambert_kernel.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_lambert_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_lambert_query_t);
+    case 1: return NYX_HIP_LAMBERT_VERSION;
+    case 2: return NYX_HIP_LMB_COUNT;
+    case 3: return NYX_HIP_MAX_LAMBERT_PARAMS;
+    case 4: return (int32_t)sizeof(nyx_hip_lambert_grid_query_t);
+    case 5: return (int32_t)sizeof(nyx_hip_lambert_chain_t);
+    default: return -1;
+    }
+}
+
+extern "C" int32_t nyx_hip_lambert_batch_device(nyx_hip_ctx *ctx, const double *rv1, const double *rv2, const double *tof_s, int64_t n, double mu_km3_s2,
+                                                const nyx_hip_lambert_query_t *q, double *values, int32_t *status, void *hip_stream) {
+    if (Refusal r = check_lambert_batch(ctx, rv1, rv2, tof_s, n, mu_km3_s2, q, values, status)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    LmbBatchArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.rv1 = rv1; a.rv2 = rv2; a.tof_s = tof_s; a.n = n; a.mu = mu_km3_s2; a.q = *q; a.values = values; a.status = status;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_lambert_batch(&a, stream); });
+}
+
+extern "C" int32_t nyx_hip_lambert_batch(nyx_hip_ctx *ctx, const double *rv1, const double *rv2, const double *tof_s, int64_t n, double mu_km3_s2,
+                                         const nyx_hip_lambert_query_t *q, double *values, int32_t *status) {
+    if (Refusal r = check_lambert_batch(ctx, rv1, rv2, tof_s, n, mu_km3_s2, q, values, status)) return refused(r);
+    if (n == 0) return NYX_HIP_RC_OK;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one device block: rv1 [6][n], rv2 [6][n], tof_s [n], values [n_params][n], status [n]
+    const size_t row = (size_t)n * sizeof(double), in = 13 * row, vals = (size_t)q->n_params * row;
+    DevBuf blk;
+    if (int rc = blk.alloc(in + vals + (size_t)n * sizeof(int32_t))) return rc;
+    char *base = blk.as<char>();
+    HIP_TRY(hipMemcpy(base, rv1, 6 * row, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(base + 6 * row, rv2, 6 * row, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(base + 12 * row, tof_s, row, hipMemcpyHostToDevice));
+    if (int rc = nyx_hip_lambert_batch_device(ctx, (const double *)base, (const double *)(base + 6 * row), (const double *)(base + 12 * row), n, mu_km3_s2, q,
+                                              (double *)(base + in), (int32_t *)(base + in + vals), nullptr))
+        return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("lambert batch kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    HIP_TRY(hipMemcpy(values, base + in, vals, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, base + in + vals, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
+
+// check_lambert_grid never reads the context; what the query asks of the context - its segments, no integration-frame swap - is
+// checked behind it
+static Refusal check_lambert(const nyx_hip_ctx *ctx, const nyx_hip_lambert_grid_query_t *q, const double *values, const int32_t *status) {
+    if (Refusal r = check_lambert_grid(ctx, q, values, status)) return r;
+    return check_lambert_context(*q, ctx->host_cfg.n_seg, ctx->swap_n_chain != 0);
+}
+
+extern "C" int32_t nyx_hip_lambert_grid_device(nyx_hip_ctx *ctx, const nyx_hip_lambert_grid_query_t *q, double *values, int32_t *status, void *hip_stream) {
+    if (Refusal r = check_lambert(ctx, q, values, status)) return refused(r);
+    if (q->n_dep == 0 || q->n_arr == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    LmbGridArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.q = *q; a.records = ctx->d_records; a.values = values; a.status = status;
+    return timed_launch(ctx, stream, [&] { return nyx_launch_lambert_grid(&a, ctx->host_cfg.seg, stream); });
+}
+
+extern "C" int32_t nyx_hip_lambert_grid(nyx_hip_ctx *ctx, const nyx_hip_lambert_grid_query_t *q, double *values, int32_t *status) {
+    if (Refusal r = check_lambert(ctx, q, values, status)) return refused(r);
+    if (q->n_dep == 0 || q->n_arr == 0) return NYX_HIP_RC_OK;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)q->n_dep * (size_t)q->n_arr, vals = (size_t)q->solve.n_params * cells * sizeof(double);
+    DevBuf blk;
+    if (int rc = blk.alloc(vals + cells * sizeof(int32_t))) return rc;
+    char *base = blk.as<char>();
+    if (int rc = nyx_hip_lambert_grid_device(ctx, q, (double *)base, (int32_t *)(base + vals), nullptr)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("lambert grid kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
+    read_kernel_ms(ctx);
+    HIP_TRY(hipMemcpy(values, base, vals, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, base + vals, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

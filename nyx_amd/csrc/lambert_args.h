@@ -1,0 +1,126 @@
+// lambert_args.h — launch arguments of the Lambert kernels (lambert_kernel.hip), shared with abi.cpp, and what the two entries of
+// include/nyx_hip_lambert.h refuse before anything is launched (host and device text; no HIP).  The refusals are data (Refusal,
+// series_host.h) and are tested on the CPU (tests/test_lambert_abi.py through the C entries).
+#pragma once
+#include <stdint.h>
+
+#include <cmath>
+
+#include "../../include/nyx_hip_lambert.h"
+#include "devcfg.h"
+#include "series_host.h"   // Refusal, bad_arg
+
+// One chain as the kernel walks it: state = sum_k sign[k] * (position and velocity of seg[k]), in chain order, from zero.  The
+// segment rows travel as kernel arguments (scalar loads, the same for every lane).
+struct LmbChain {
+    int32_t n_chain, _pad;
+    double sign[NYX_HIP_MAX_CHAIN];
+    DevSeg seg[NYX_HIP_MAX_CHAIN];
+};
+
+struct LmbBatchArgs {
+    const double *rv1, *rv2, *tof_s;  // device pointers, component-major [c * n + i]
+    int64_t n;
+    double mu;
+    nyx_hip_lambert_query_t q;
+    double *values;    // [n_params][n]
+    int32_t *status;   // [n]
+};
+
+struct LmbGridArgs {
+    nyx_hip_lambert_grid_query_t q;
+    const double *records;   // the context's ephemeris records on the device (DevSeg.offset points into it)
+    LmbChain dep, arr, centre;
+    double *values;    // [n_params][n_dep][n_arr]
+    int32_t *status;   // [n_dep][n_arr]
+};
+static_assert(sizeof(LmbGridArgs) <= 4096, "LmbGridArgs must fit the kernel-argument segment");
+
+static inline LmbChain lmb_chain(const nyx_hip_lambert_chain_t &c, const DevSeg *ctx_seg) {
+    LmbChain out = {};
+    out.n_chain = c.n_chain;
+    for (int k = 0; k < c.n_chain; ++k) {
+        out.sign[k] = (double)c.chain_sign[k];
+        out.seg[k] = ctx_seg[c.chain_segment[k]];
+    }
+    return out;
+}
+
+// ---- refusals.  The solver's settings first, in the order of the header's list
+inline Refusal check_lambert_query(const char *name, const nyx_hip_ctx *ctx, const nyx_hip_lambert_query_t *q, double mu_km3_s2) {
+    if (!ctx) return bad_arg("null ctx");
+    if (!q) return bad_arg("%s: null query", name);
+    if (q->n_params < 1 || q->n_params > NYX_HIP_MAX_LAMBERT_PARAMS)
+        return bad_arg("%s: n_params = %d, 1 .. %d parameters per call", name, q->n_params, NYX_HIP_MAX_LAMBERT_PARAMS);
+    for (int p = 0; p < q->n_params; ++p)
+        if (q->param[p] < 0 || q->param[p] >= NYX_HIP_LMB_COUNT) return bad_arg("%s: param[%d] = %d is not a nyx_hip_lambert_param", name, p, q->param[p]);
+    if (q->way < 0 || q->way >= NYX_HIP_LMB_WAY_COUNT) return bad_arg("%s: way = %d is not a nyx_hip_lambert_way", name, q->way);
+    if (q->n_revs < 0 || q->n_revs > NYX_HIP_LMB_MAX_REVS) return bad_arg("%s: n_revs = %d, 0 .. %d", name, q->n_revs, NYX_HIP_LMB_MAX_REVS);
+    if (q->high_path != 0 && q->high_path != 1) return bad_arg("%s: high_path = %d, 0 or 1", name, q->high_path);
+    if (!(q->tol >= NYX_HIP_LMB_TOL_MIN && q->tol <= NYX_HIP_LMB_TOL_MAX)) return bad_arg("%s: tol = %g, 1e-13 .. 1e-2", name, q->tol);
+    if (q->max_iter < 1 || q->max_iter > NYX_HIP_LMB_MAX_ITER) return bad_arg("%s: max_iter = %d, 1 .. %d", name, q->max_iter, NYX_HIP_LMB_MAX_ITER);
+    if (!(std::isfinite(mu_km3_s2) && mu_km3_s2 > 0.0)) return bad_arg("%s: mu_km3_s2 must be finite and > 0", name);
+    return {};
+}
+
+inline Refusal check_lambert_batch(const nyx_hip_ctx *ctx, const double *rv1, const double *rv2, const double *tof_s, int64_t n, double mu_km3_s2,
+                                   const nyx_hip_lambert_query_t *q, const double *values, const int32_t *status) {
+    const char *name = "lambert_batch";
+    if (Refusal r = check_lambert_query(name, ctx, q, mu_km3_s2)) return r;
+    if (n < 0) return bad_arg("negative n");
+    if (!rv1 || !rv2 || !tof_s) return bad_arg("%s: rv1, rv2 and tof_s arrays required", name);
+    if (!values || !status) return bad_arg("%s: values and status arrays required", name);
+    return {};
+}
+
+inline bool lmb_same_chain(const nyx_hip_lambert_chain_t &a, const nyx_hip_lambert_chain_t &b) {
+    if (a.n_chain != b.n_chain) return false;
+    for (int k = 0; k < a.n_chain; ++k)
+        if (a.chain_segment[k] != b.chain_segment[k] || a.chain_sign[k] != b.chain_sign[k]) return false;
+    return true;
+}
+
+inline Refusal check_lambert_chain(const char *name, const char *who, const nyx_hip_lambert_chain_t &c) {
+    if (c.n_chain < 0 || c.n_chain > NYX_HIP_MAX_CHAIN) return bad_arg("%s: %s.n_chain = %d, 0 .. %d segments", name, who, c.n_chain, NYX_HIP_MAX_CHAIN);
+    for (int k = 0; k < c.n_chain; ++k) {
+        if (c.chain_segment[k] < 0) return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context", name, who, k, c.chain_segment[k]);
+        if (c.chain_sign[k] != 1 && c.chain_sign[k] != -1) return bad_arg("%s: %s.chain_sign[%d] = %d, +1 or -1", name, who, k, c.chain_sign[k]);
+    }
+    return {};
+}
+
+// check_lambert_grid never dereferences the context; check_lambert_context is what the query asks of it (of a query the first accepted)
+inline Refusal check_lambert_grid(const nyx_hip_ctx *ctx, const nyx_hip_lambert_grid_query_t *q, const double *values, const int32_t *status) {
+    const char *name = "lambert_grid";
+    if (!ctx) return bad_arg("null ctx");
+    if (!q) return bad_arg("%s: null query", name);
+    if (Refusal r = check_lambert_query(name, ctx, &q->solve, q->mu_km3_s2)) return r;
+    if (q->n_dep < 0 || q->n_arr < 0 || q->n_dep > INT32_MAX || q->n_arr > INT32_MAX)
+        return bad_arg("%s: n_dep = %lld, n_arr = %lld, 0 .. 2^31 - 1 each", name, (long long)q->n_dep, (long long)q->n_arr);
+    if (q->has_tof != 0 && q->has_tof != 1) return bad_arg("%s: has_tof = %d, 0 or 1", name, q->has_tof);
+    if (q->dep_step_ns <= 0) return bad_arg("%s: dep_step_ns must be > 0", name);
+    if (q->has_tof ? q->tof_step_ns <= 0 : q->arr_step_ns <= 0) return bad_arg("%s: %s must be > 0", name, q->has_tof ? "tof_step_ns" : "arr_step_ns");
+    if (!values || !status) return bad_arg("%s: values and status arrays required", name);
+    if (Refusal r = check_lambert_chain(name, "dep", q->dep)) return r;
+    if (Refusal r = check_lambert_chain(name, "arr", q->arr)) return r;
+    if (Refusal r = check_lambert_chain(name, "centre", q->centre)) return r;
+    if (lmb_same_chain(q->dep, q->centre)) return bad_arg("%s: the departure body's chain is the centre's: its radius is zero by construction", name);
+    if (lmb_same_chain(q->arr, q->centre)) return bad_arg("%s: the arrival body's chain is the centre's: its radius is zero by construction", name);
+    return {};
+}
+inline Refusal check_lambert_context(const nyx_hip_lambert_grid_query_t &q, int n_seg, bool frame_swapped) {
+    const char *name = "lambert_grid";
+    const nyx_hip_lambert_chain_t *chains[3] = {&q.dep, &q.arr, &q.centre};
+    const char *who[3] = {"dep", "arr", "centre"};
+    for (int b = 0; b < 3; ++b)
+        for (int k = 0; k < chains[b]->n_chain; ++k)
+            if (chains[b]->chain_segment[k] >= n_seg)
+                return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, who[b], k, chains[b]->chain_segment[k], n_seg - 1);
+    if (frame_swapped) {
+        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): its chains are not those of "
+                            "the states it integrates", name);
+        r.rc = NYX_HIP_RC_UNSUPPORTED;
+        return r;
+    }
+    return {};
+}

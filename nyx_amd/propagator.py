@@ -33,6 +33,7 @@ from .params import FRAME_OF, StateError, StateParameter
 from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackParameter, check_frame
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations
 from . import frames
+from . import lambert
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
 from . import links
 from . import stats as series_statistics
@@ -970,6 +971,87 @@ class GpuContext:
 
         return _param_series("traj_frame_values", fn, self._h, _abi.FrameQuery, _abi.MAX_FRAME_PARAMS, fill, traj, codes, step_ns, start_ns, end_ns,
                              capacity, stats=stats)
+
+    @staticmethod
+    def _lambert_query(q, codes, way, n_revs, high_path, tol, max_iter):
+        q.n_params = len(codes)
+        for k, code in enumerate(codes):
+            q.param[k] = code
+        q.way, q.n_revs, q.high_path, q.tol, q.max_iter = int(way), int(n_revs), int(high_path), float(tol), int(max_iter)
+
+    def lambert_batch(self, rv1, rv2, tof_s, mu_km3_s2: float, params, kind=lambert.TransferKind.Auto, n_revs: int = 0, high_path: int = 0,
+                      tol: float = lambert.DEFAULT_TOL, max_iter: int = lambert.DEFAULT_MAX_ITER) -> "lambert.LambertGrid":
+        """``nyx_hip_lambert_batch`` (include/nyx_hip_lambert.h): n independent Lambert problems on the device, one per lane.  `rv1` /
+        `rv2` are the departure and arrival bodies' full states, component-major [6, n] (km, km/s), `tof_s` [n] the times of flight.
+        A LambertGrid with values[P, n] and status[n] (lambert.LambertStatus; every value of a problem that is not OK is NaN).  More
+        than eight parameters take several launches."""
+        fn = _abi.lambert_entry(self._lib, "nyx_hip_lambert_batch")
+        params = [lambert.lambert_param(p) for p in params]
+        if not params:
+            raise ValueError("lambert_batch: at least one parameter")
+        way, n_revs, high_path, tol, max_iter = lambert.check_solver(kind, n_revs, high_path, tol, max_iter)
+        rv1, rv2 = np.ascontiguousarray(rv1, dtype=np.float64), np.ascontiguousarray(rv2, dtype=np.float64)
+        tof_s = np.ascontiguousarray(tof_s, dtype=np.float64).reshape(-1)
+        n = len(tof_s)
+        if rv1.shape != (6, n) or rv2.shape != (6, n):
+            raise ValueError("lambert_batch: rv1 and rv2 are [6, n], tof_s is [n]")
+        values, status = np.empty((len(params), n)), np.zeros(n, dtype=np.int32)
+        for k0 in range(0, len(params), _abi.MAX_LAMBERT_PARAMS):
+            group = params[k0:k0 + _abi.MAX_LAMBERT_PARAMS]
+            q = _abi.LambertQuery()
+            self._lambert_query(q, [int(p) for p in group], way, n_revs, high_path, tol, max_iter)
+            part = np.empty((len(group), n))
+            rc = fn(self._h, rv1.ctypes.data_as(_abi.c_double_p), rv2.ctypes.data_as(_abi.c_double_p), tof_s.ctypes.data_as(_abi.c_double_p), n,
+                    float(mu_km3_s2), C.byref(q), part.ctypes.data_as(_abi.c_double_p), status.ctypes.data_as(_abi.c_int32_p))
+            if rc != 0:
+                raise RuntimeError(f"nyx_hip_lambert_batch failed (rc={rc}): {_abi.last_error()}")
+            values[k0:k0 + len(group)] = part
+        return lambert.LambertGrid(params, values, status)
+
+    def lambert_grid(self, dep_body: "Frame", arr_body: "Frame", centre: "Frame", params, n_dep: int, n_arr: int, dep0_ns: int, dep_step_ns: int,
+                     arr0_ns: Optional[int] = None, arr_step_ns: Optional[int] = None, tof0_ns: Optional[int] = None, tof_step_ns: Optional[int] = None,
+                     kind=lambert.TransferKind.Auto, n_revs: int = 0, high_path: int = 0, tol: float = lambert.DEFAULT_TOL,
+                     max_iter: int = lambert.DEFAULT_MAX_ITER) -> "lambert.LambertGrid":
+        """``nyx_hip_lambert_grid`` (include/nyx_hip_lambert.h): the porkchop of transfers from `dep_body` to `arr_body` about `centre`
+        (Frames of the almanac this context was compiled from; `centre.mu_km3_s2` is the gravitational parameter) in one launch:
+        departures at dep0_ns + i dep_step_ns, arrivals at arr0_ns + j arr_step_ns, or - with `tof0_ns` / `tof_step_ns` - at the
+        departure plus tof0_ns + j tof_step_ns.  The bodies' states are evaluated from the context's ephemerides on the device.  A
+        LambertGrid with values[P, n_dep, n_arr], status[n_dep, n_arr] and the epochs; `values` is a [rows, capacity, n] block that
+        `series_stats` takes.  More than eight parameters take several launches."""
+        fn = _abi.lambert_entry(self._lib, "nyx_hip_lambert_grid")
+        almanac, central = self.compiled.almanac, self.compiled.central
+        if almanac is None:
+            raise ValueError("lambert_grid: the context was not compiled from an almanac (CompiledConfig.almanac)")
+        params = [lambert.lambert_param(p) for p in params]
+        if not params:
+            raise ValueError("lambert_grid: at least one parameter")
+        way, n_revs, high_path, tol, max_iter = lambert.check_solver(kind, n_revs, high_path, tol, max_iter)
+        if (arr0_ns is None) == (tof0_ns is None):
+            raise ValueError("lambert_grid: arrivals by epoch (arr0_ns, arr_step_ns) or by time of flight (tof0_ns, tof_step_ns)")
+        chains = [lambert.check_chain(w, b.naif_id, almanac, central) for w, b in (("departure body", dep_body), ("arrival body", arr_body), ("centre", centre))]
+        n_dep, n_arr = int(n_dep), int(n_arr)
+        values, status = np.empty((len(params), n_dep, n_arr)), np.zeros((n_dep, n_arr), dtype=np.int32)
+        for k0 in range(0, len(params), _abi.MAX_LAMBERT_PARAMS):
+            group = params[k0:k0 + _abi.MAX_LAMBERT_PARAMS]
+            q = _abi.LambertGridQuery()
+            self._lambert_query(q.solve, [int(p) for p in group], way, n_revs, high_path, tol, max_iter)
+            for dst, chain in zip((q.dep, q.arr, q.centre), chains):
+                dst.n_chain = len(chain)
+                for k, (seg, sign) in enumerate(chain):
+                    dst.chain_segment[k], dst.chain_sign[k] = seg, sign
+            q.has_tof, q.n_dep, q.n_arr, q.dep0_ns, q.dep_step_ns = int(tof0_ns is not None), n_dep, n_arr, int(dep0_ns), int(dep_step_ns)
+            if tof0_ns is not None:
+                q.tof0_ns, q.tof_step_ns = int(tof0_ns), int(tof_step_ns)
+            else:
+                q.arr0_ns, q.arr_step_ns = int(arr0_ns), int(arr_step_ns)
+            q.mu_km3_s2 = float(centre.mu_km3_s2)
+            part = np.empty((len(group), n_dep, n_arr))
+            rc = fn(self._h, C.byref(q), part.ctypes.data_as(_abi.c_double_p), status.ctypes.data_as(_abi.c_int32_p))
+            if rc != 0:
+                raise RuntimeError(f"nyx_hip_lambert_grid failed (rc={rc}): {_abi.last_error()}")
+            values[k0:k0 + len(group)] = part
+        dep_ns, arr_ns = lambert.grid_epochs(n_dep, n_arr, dep0_ns, dep_step_ns, arr0_ns, arr_step_ns, tof0_ns, tof_step_ns)
+        return lambert.LambertGrid(params, values, status, dep_ns, arr_ns)
 
     def traj_link(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                   capacity: Optional[int] = None, bodies=None, stats=None):
