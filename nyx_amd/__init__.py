@@ -12,6 +12,7 @@ from .stations import AerParameter, GroundStation, aer_value, check_stations, st
 from .frames import FrameParameter, body_state, cheby_state, frame_value, to_frame  # noqa: F401,E402
 from .links import LinkParameter, check_link_bodies, link_value  # noqa: F401,E402
 from .lambert import LambertGrid, LambertParameter, LambertSolution, LambertStatus, TransferKind, grid_definition, izzo  # noqa: F401,E402
+from .targeter import BPlaneTarget, Objective, TargetStatus, Targeter, TargeterSolutions, Variable, Vary, target_definition  # noqa: F401,E402
 from .stats import SeriesStats, Stat, series_stats  # noqa: F401,E402
 from .eclipse import EclipseParameter, ShadowModel, check_shadow_model, eclipse_value, state_changes  # noqa: F401,E402
 from .rng import Pcg64Mcg  # noqa: F401,E402

@@ -413,6 +413,31 @@ class LambertGridQuery(C.Structure):
                 ("arr_step_ns", C.c_int64), ("tof0_ns", C.c_int64), ("tof_step_ns", C.c_int64), ("mu_km3_s2", C.c_double)]
 
 
+# ---- include/nyx_hip_target.h (the differential-correction targeter of a batch) ----
+TARGET_VERSION = 1
+MAX_TARGET_VARS = 6
+MAX_TARGET_OBJS = 6
+# enum nyx_hip_target_status: the members of targeter.TargetStatus, by name
+TARGET_STATUS = {"OK_CONVERGED": 0, "TOO_MANY_ITERATIONS": 1, "INEFFECTIVE": 2, "SINGULAR": 3, "NOT_FINITE": 4, "PROP_FAILED": 5, "EPHEM_RANGE": 6}
+TARGET_STATUS_COUNT = 7
+
+
+class TargetQuery(C.Structure):
+    _fields_ = [("n_vars", C.c_int32), ("n_objs", C.c_int32), ("iterations", C.c_int32), ("correction_frame", C.c_int32),
+                ("var_component", C.c_int32 * MAX_TARGET_VARS), ("var_perturbation", C.c_double * MAX_TARGET_VARS),
+                ("var_init_guess", C.c_double * MAX_TARGET_VARS), ("var_max_step", C.c_double * MAX_TARGET_VARS),
+                ("var_max_value", C.c_double * MAX_TARGET_VARS), ("var_min_value", C.c_double * MAX_TARGET_VARS),
+                ("obj_param", C.c_int32 * MAX_TARGET_OBJS), ("obj_desired", C.c_double * MAX_TARGET_OBJS), ("obj_tolerance", C.c_double * MAX_TARGET_OBJS),
+                ("obj_mult", C.c_double * MAX_TARGET_OBJS), ("obj_add", C.c_double * MAX_TARGET_OBJS), ("n_chain", C.c_int32),
+                ("chain_segment", C.c_int32 * MAX_CHAIN), ("chain_sign", C.c_int32 * MAX_CHAIN), ("_pad", C.c_int32), ("mu_km3_s2", C.c_double),
+                ("correction_epoch_ns", C.c_int64), ("achievement_epoch_ns", C.c_int64)]
+
+
+class TargetResult(C.Structure):
+    _fields_ = [("status", c_int32_p), ("iterations", c_int32_p), ("correction", c_double_p), ("achieved_errors", c_double_p),
+                ("corrected", States), ("achieved", States), ("iterations_run", C.c_int32), ("_pad", C.c_int32)]
+
+
 # include/nyx_hip_stats.h: the statistics of a report's values block
 STATS_VERSION = 1
 STAT_FIXED = 10
@@ -605,6 +630,9 @@ LINK_EXPORTS = ["nyx_hip_traj_link", "nyx_hip_traj_link_device", "nyx_hip_link_s
 # the entries of include/nyx_hip_lambert.h, likewise
 LAMBERT_EXPORTS = ["nyx_hip_lambert_batch", "nyx_hip_lambert_batch_device", "nyx_hip_lambert_grid", "nyx_hip_lambert_grid_device", "nyx_hip_lambert_sizeof"]
 
+# the entries of include/nyx_hip_target.h, likewise
+TARGET_EXPORTS = ["nyx_hip_target_batch", "nyx_hip_target_batch_device", "nyx_hip_target_sizeof"]
+
 # the entries of include/nyx_hip_stats.h, likewise
 STATS_EXPORTS = ["nyx_hip_series_stats", "nyx_hip_series_stats_device", "nyx_hip_traj_series_stats", "nyx_hip_stats_sizeof"]
 
@@ -731,6 +759,16 @@ def load_library():
         if got != [C.sizeof(LambertQuery), C.sizeof(LambertGridQuery), C.sizeof(LambertChain)]:
             raise RuntimeError(f"{lib_path()}: the structs of nyx_hip_lambert.h are {got} bytes, the ctypes mirrors "
                                f"{[C.sizeof(LambertQuery), C.sizeof(LambertGridQuery), C.sizeof(LambertChain)]}")
+    if getattr(lib, "nyx_hip_target_sizeof", None) is not None:   # (absent from a library built before the targeter)
+        lib.nyx_hip_target_batch.argtypes = [C.c_void_p, C.POINTER(States), C.POINTER(TargetQuery), C.POINTER(TargetResult)]
+        lib.nyx_hip_target_batch_device.argtypes = [C.c_void_p, C.POINTER(States), C.POINTER(TargetQuery), C.POINTER(TargetResult), C.c_void_p]
+        lib.nyx_hip_target_sizeof.argtypes = [C.c_int32]
+        for n in TARGET_EXPORTS:
+            getattr(lib, n).restype = C.c_int32
+        got = [lib.nyx_hip_target_sizeof(k) for k in (0, 4)]
+        if got != [C.sizeof(TargetQuery), C.sizeof(TargetResult)]:
+            raise RuntimeError(f"{lib_path()}: the structs of nyx_hip_target.h are {got} bytes, the ctypes mirrors "
+                               f"{[C.sizeof(TargetQuery), C.sizeof(TargetResult)]}")
     lib.nyx_hip_abi_sizeof.argtypes = [C.c_int32]
     lib.nyx_hip_abi_sizeof.restype = C.c_int64
     _LIB = lib
@@ -771,6 +809,15 @@ def lambert_entry(lib, name: str = "nyx_hip_lambert_grid"):
     fn = getattr(lib, name, None)
     if fn is None:
         raise RuntimeError(f"{lib_path()} has no {name}: it was built before the Lambert transfers were added - rebuild the HIP extension "
+                           "(python -c 'import __graft_entry__ as g; g.build()')")
+    return fn
+
+
+def target_entry(lib, name: str = "nyx_hip_target_batch"):
+    """An entry of include/nyx_hip_target.h, or a clear error when the loaded library predates it."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{lib_path()} has no {name}: it was built before the targeter was added - rebuild the HIP extension "
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     return fn
 

@@ -34,6 +34,7 @@
 #include "link_args.h"
 #include "frame_args.h"
 #include "lambert_args.h"
+#include "target_args.h"
 #include "groundtrack_args.h"
 #include "series_host.h"
 #include "stats_host.h"
@@ -52,6 +53,8 @@ extern "C" hipError_t nyx_launch_traj_eclipse(const EclArgs *args, const DevSeg 
 extern "C" hipError_t nyx_launch_traj_frame_values(const FrmArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_lambert_batch(const LmbBatchArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_lambert_grid(const LmbGridArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
+extern "C" hipError_t nyx_launch_target_seed(const TgtArgs *args, hipStream_t stream);
+extern "C" hipError_t nyx_launch_target_step(const TgtArgs *args, hipStream_t stream);
 extern "C" hipError_t nyx_launch_traj_link(const LnkArgs *args, const DevSeg *ctx_seg, hipStream_t stream);
 extern "C" hipError_t nyx_launch_series_stats(const StatArgs *args, int64_t n_rows, hipStream_t stream);
 extern "C" hipError_t nyx_launch_moments(const MomArgs &a, double *out, hipStream_t stream);
@@ -169,6 +172,9 @@ struct nyx_hip_ctx {
     int forced_quad = -1;  // STM layout: -1 = by ensemble size, 0 = 64 trajectories x D3 per workgroup, 1 = quad layout (16 x 4 lanes, D1)
     double role_handicap[3] = {0.0, 0.0, 0.0};  // integrator, almanac, perturbations (harmonics-term units)
     DevArrays in, out;
+    DevArrays work;            // the targeter's work block: (1 + V) n rows propagated in place (nyx_hip_target_batch), grown on demand
+    char *d_tgt = nullptr;     // what its runs keep between the rounds: [TGT_KEEP_ROWS][tgt_cap] doubles, flag[tgt_cap], active[NYX_HIP_TARGET_MAX_ITERATIONS + 2]
+    int64_t tgt_cap = 0;
     int64_t *d_prof = nullptr;
     CoopBox *d_coop = nullptr;  // cooperative-mode mailboxes, one per trajectory-owning workgroup, then the packed scan words
     int64_t coop_cap = 0;
@@ -501,6 +507,8 @@ extern "C" void nyx_hip_ctx_destroy(nyx_hip_ctx *ctx) {
     free_arrays(ctx->in);
     free_arrays(ctx->out);
     free_arrays(ctx->cal);
+    free_arrays(ctx->work);
+    (void)hipFree(ctx->d_tgt);
     (void)hipFree(ctx->d_swap);
     (void)hipFree(ctx->d_mom);
     mailbox_release(ctx->device, ctx->d_coop, ctx->coop_cap, !(ctx->tune.debug_flags & 0x100000));
@@ -1447,6 +1455,141 @@ extern "C" int32_t nyx_hip_lambert_grid(nyx_hip_ctx *ctx, const nyx_hip_lambert_
     read_kernel_ms(ctx);
     HIP_TRY(hipMemcpy(values, base, vals, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(status, base + vals, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The targeter (include/nyx_hip_target.h): target_kernel.hip around the propagator's own launches
+// ---------------------------------------------------------------------------------------------
+extern "C" int32_t nyx_hip_target_sizeof(int32_t which) {
+    switch (which) {
+    case 0: return (int32_t)sizeof(nyx_hip_target_query_t);
+    case 1: return NYX_HIP_TARGET_VERSION;
+    case 2: return NYX_HIP_TGT_STATUS_COUNT;
+    case 3: return NYX_HIP_MAX_TARGET_VARS;
+    case 4: return (int32_t)sizeof(nyx_hip_target_result_t);
+    case 5: return NYX_HIP_MAX_TARGET_OBJS;
+    default: return -1;
+    }
+}
+
+// check_target never reads the context; what the query asks of the context is checked behind it
+static Refusal check_tgt(const nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_hip_target_query_t *q, const nyx_hip_target_result_t *res) {
+    if (Refusal r = check_target(ctx, in, q, res)) return r;
+    return check_target_context(*q, ctx->host_cfg.n_seg, (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0, ctx->swap_n_chain != 0);
+}
+
+// what the runs keep between the rounds, their flags and the counters: one block of the context, grown on demand
+static int ensure_target_keep(nyx_hip_ctx *ctx, int64_t n) {
+    if (ctx->tgt_cap >= n) return NYX_HIP_RC_OK;
+    (void)hipFree(ctx->d_tgt);
+    ctx->d_tgt = nullptr; ctx->tgt_cap = 0;
+    const int64_t cap = (std::max<int64_t>(n, 1024) + 63) / 64 * 64;
+    const size_t bytes = (size_t)TGT_KEEP_ROWS * (size_t)cap * sizeof(double) + (size_t)cap * sizeof(int32_t) + (NYX_HIP_TARGET_MAX_ITERATIONS + 2) * sizeof(int32_t);
+    HIP_TRY(hipMalloc((void **)&ctx->d_tgt, bytes));
+    HIP_TRY(hipMemset(ctx->d_tgt, 0, bytes));
+    ctx->tgt_cap = cap;
+    return NYX_HIP_RC_OK;
+}
+
+// The loop on device arrays: one launch to the correction epoch, the seed, then per round one in-place propagation of the work block,
+// the step kernel and the 4-byte read of the runs still active.  Under the context's lock for its whole length.
+extern "C" int32_t nyx_hip_target_batch_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_hip_target_query_t *q, nyx_hip_target_result_t *res,
+                                               void *hip_stream) {
+    if (Refusal r = check_tgt(ctx, in, q, res)) return refused(r);
+    const int64_t n = in->n;
+    res->iterations_run = 0;
+    if (n == 0) return NYX_HIP_RC_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));  // (the blocks below may grow: nothing of this context is in flight then)
+    const int64_t rows = (int64_t)(1 + q->n_vars) * n;
+    if (int rc = ensure_arrays(ctx->out, n, true)) return rc;
+    if (int rc = ensure_arrays(ctx->work, rows, true)) return rc;
+    if (int rc = ensure_target_keep(ctx, n)) return rc;
+    nyx_hip_states_t xs, ws;
+    nyx_hip_step_stats_t xss, wss;
+    views_of(ctx->out, n, false, xs, xss);
+    views_of(ctx->work, rows, false, ws, wss);
+    ws.step_ns = nullptr;  // (every round starts from the context's initial step, as a fresh batch does)
+    LaunchReq leg;
+    leg.in = in; leg.out = &xs; leg.stats = &xss; leg.use_end = true; leg.end_epoch_ns = q->correction_epoch_ns; leg.stream = hip_stream;
+    if (int rc = launch(ctx, leg)) return rc;
+    TgtArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.q = *q; a.n = n; a.cap = ctx->tgt_cap;
+    a.start = tgt_rows(xs, xss.status);
+    a.work = tgt_rows(ws, wss.status);
+    a.keep = (double *)ctx->d_tgt;
+    a.flag = (int32_t *)(a.keep + (size_t)TGT_KEEP_ROWS * (size_t)ctx->tgt_cap);
+    a.active = a.flag + ctx->tgt_cap;
+    a.n_chain = q->n_chain;
+    for (int k = 0; k < q->n_chain; ++k) { a.sign[k] = (double)q->chain_sign[k]; a.seg[k] = ctx->host_cfg.seg[q->chain_segment[k]]; }
+    a.records = ctx->d_records;
+    a.o_status = res->status; a.o_iterations = res->iterations; a.o_correction = res->correction; a.o_errors = res->achieved_errors;
+    a.corrected = tgt_rows(res->corrected, nullptr);
+    a.achieved = tgt_rows(res->achieved, nullptr);
+    HIP_TRY(hipMemsetAsync(a.active, 0, (size_t)(q->iterations + 2) * sizeof(int32_t), stream));
+    HIP_TRY(nyx_launch_target_seed(&a, stream));
+    LaunchReq round;
+    round.in = &ws; round.out = &ws; round.stats = &wss; round.use_end = true; round.end_epoch_ns = q->achievement_epoch_ns; round.stream = hip_stream;
+    int32_t rounds = 0;
+    for (int it = 0; it <= q->iterations; ++it) {
+        if (int rc = launch(ctx, round)) return rc;
+        a.it = it;
+        HIP_TRY(nyx_launch_target_step(&a, stream));
+        int32_t live = 0;
+        HIP_TRY(hipMemcpyAsync(&live, a.active + it, sizeof live, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        rounds = it + 1;
+        if (live == 0) break;
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
+    res->iterations_run = rounds;
+    return NYX_HIP_RC_OK;
+}
+
+extern "C" int32_t nyx_hip_target_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_hip_target_query_t *q, nyx_hip_target_result_t *res) {
+    if (Refusal r = check_tgt(ctx, in, q, res)) return refused(r);
+    const int64_t n = in->n;
+    res->iterations_run = 0;
+    if (n == 0) return NYX_HIP_RC_OK;
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    Staged sg;
+    if (int rc = stage_batch(ctx, in, sg, false)) return rc;
+    // one device block for the outputs: correction [V][n], errors [O][n], corrected and achieved (epoch and 13 rows of n each), status [n], iterations [n]
+    const size_t row = (size_t)n * sizeof(double), corr = (size_t)q->n_vars * row, errs = (size_t)q->n_objs * row;
+    DevBuf blk;
+    if (int rc = blk.alloc(corr + errs + 28 * row + 2 * (size_t)n * sizeof(int32_t))) return rc;
+    char *base = blk.as<char>();
+    nyx_hip_target_result_t d;
+    std::memset(&d, 0, sizeof d);
+    d.correction = (double *)base;
+    d.achieved_errors = (double *)(base + corr);
+    nyx_hip_states_t *views[2] = {&d.corrected, &d.achieved};
+    for (int s = 0; s < 2; ++s) {
+        char *at = base + corr + errs + (size_t)s * 14 * row;
+        views[s]->n = n;
+        views[s]->epoch_ns = (int64_t *)at;
+        for (int k = 0; k < kStateRows; ++k) views[s]->*kStateRow[k].s = (double *)(at + (size_t)(1 + k) * row);
+    }
+    d.status = (int32_t *)(base + corr + errs + 28 * row);
+    d.iterations = d.status + n;
+    if (int rc = nyx_hip_target_batch_device(ctx, &sg.din, q, &d, nullptr)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("targeter kernels failed"); return NYX_HIP_RC_HIP_ERROR; }
+    HIP_TRY(hipMemcpy(res->correction, d.correction, corr, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(res->achieved_errors, d.achieved_errors, errs, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(res->status, d.status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(res->iterations, d.iterations, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const nyx_hip_states_t *host[2] = {&res->corrected, &res->achieved};
+    for (int s = 0; s < 2; ++s) {
+        HIP_TRY(hipMemcpy(host[s]->epoch_ns, views[s]->epoch_ns, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int k = 0; k < kStateRows; ++k)
+            if (double *h = host[s]->*kStateRow[k].s) HIP_TRY(hipMemcpy(h, views[s]->*kStateRow[k].s, row, hipMemcpyDeviceToHost));
+    }
+    res->iterations_run = d.iterations_run;
     return NYX_HIP_RC_OK;
 }
 

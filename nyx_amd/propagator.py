@@ -34,6 +34,7 @@ from .groundtrack import DEFAULT_PARAMS as GROUND_TRACK_DEFAULT, GroundTrackPara
 from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_stations
 from . import frames
 from . import lambert
+from . import targeter
 from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
 from . import links
 from . import stats as series_statistics
@@ -1052,6 +1053,63 @@ class GpuContext:
             values[k0:k0 + len(group)] = part
         dep_ns, arr_ns = lambert.grid_epochs(n_dep, n_arr, dep0_ns, dep_step_ns, arr0_ns, arr_step_ns, tof0_ns, tof_step_ns)
         return lambert.LambertGrid(params, values, status, dep_ns, arr_ns)
+
+    def target_query(self, variables, objectives, correction_epoch_ns: int, achievement_epoch_ns: int, objective_frame=None, correction_frame=None,
+                     iterations: int = 100) -> "_abi.TargetQuery":
+        """The nyx_hip_target_query_t of a targeter problem on this context; what the library would refuse of the variables and the
+        objectives is refused here with the same words (targeter.check_problem)."""
+        frame = targeter.check_problem(variables, objectives, correction_frame, iterations)
+        q = _abi.TargetQuery()
+        q.n_vars, q.n_objs, q.iterations, q.correction_frame = len(variables), len(objectives), int(iterations), frame
+        for j, v in enumerate(variables):
+            q.var_component[j], q.var_perturbation[j], q.var_init_guess[j] = int(v.component), float(v.perturbation), float(v.init_guess)
+            q.var_max_step[j], q.var_max_value[j], q.var_min_value[j] = float(v.max_step), float(v.max_value), float(v.min_value)
+        for o, obj in enumerate(objectives):
+            q.obj_param[o], q.obj_desired[o], q.obj_tolerance[o] = int(frames.frame_param(obj.parameter)), float(obj.desired_value), float(obj.tolerance)
+            q.obj_mult[o], q.obj_add[o] = float(obj.multiplicative_factor), float(obj.additive_factor)
+        q.mu_km3_s2 = float(self.compiled.central.mu_km3_s2)
+        if objective_frame is not None:
+            almanac, central = self.compiled.almanac, self.compiled.central
+            if almanac is None:
+                raise ValueError("target: the context was not compiled from an almanac (CompiledConfig.almanac)")
+            chain = frames.check_target(objective_frame, almanac, central)
+            q.n_chain, q.mu_km3_s2 = len(chain), float(objective_frame.mu_km3_s2)
+            for k, (seg, sign) in enumerate(chain):
+                q.chain_segment[k], q.chain_sign[k] = seg, sign
+        q.correction_epoch_ns, q.achievement_epoch_ns = int(correction_epoch_ns), int(achievement_epoch_ns)
+        return q
+
+    def target(self, batch: _abi.StateBatch, variables, objectives, correction_epoch_ns: int, achievement_epoch_ns: int, objective_frame=None,
+               correction_frame=None, iterations: int = 100) -> "targeter.TargeterSolutions":
+        """``nyx_hip_target_batch`` (include/nyx_hip_target.h): the differential-correction targeter of every run of `batch`, the whole
+        Newton loop on the device - per round one propagation launch of the (1 + V) n work rows, one kernel that evaluates the
+        objectives and takes every run's step, and a 4-byte read.  `variables` (targeter.Variable) are corrected at
+        `correction_epoch_ns` (in the inertial frame, or with correction_frame="VNC") until the `objectives` (targeter.Objective;
+        about `objective_frame`, a Frame of the context's almanac, or about the context's centre) hold at `achievement_epoch_ns`.
+        A TargeterSolutions, as `targeter.target_definition` defines it."""
+        fn = _abi.target_entry(self._lib)
+        variables, objectives = list(variables), list(objectives)
+        q = self.target_query(variables, objectives, correction_epoch_ns, achievement_epoch_ns, objective_frame, correction_frame, iterations)
+        n = batch.n
+        src = batch
+        if batch.stm is not None:   # (the hyperdual targeter is not on this path: the states without their STMs)
+            src = batch.copy()
+            src.stm = None
+        status, its = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        correction, errors = np.zeros((len(variables), n)), np.full((len(objectives), n), np.nan)
+        corrected, achieved = src.copy(), src.copy()
+        res = _abi.TargetResult()
+        res.status, res.iterations = status.ctypes.data_as(_abi.c_int32_p), its.ctypes.data_as(_abi.c_int32_p)
+        res.correction, res.achieved_errors = correction.ctypes.data_as(_abi.c_double_p), errors.ctypes.data_as(_abi.c_double_p)
+        res.corrected, res.achieved = corrected.as_c(), achieved.as_c()
+        res.corrected.step_ns = res.achieved.step_ns = _abi.c_int64_p()
+        cin = src.as_c()
+        rc = fn(self._h, C.byref(cin), C.byref(q), C.byref(res))
+        if rc != 0:
+            raise RuntimeError(f"nyx_hip_target_batch failed (rc={rc}): {_abi.last_error()}")
+        corrected.step_ns[:] = 0
+        achieved.step_ns[:] = 0
+        return targeter.TargeterSolutions(variables, objectives, status, its, correction, errors, corrected, achieved, res.iterations_run)
 
     def traj_link(self, traj: _abi.TrajBatch, ref: _abi.TrajBatch, params, step_ns: int, start_ns: Optional[int] = None, end_ns: Optional[int] = None,
                   capacity: Optional[int] = None, bodies=None, stats=None):
