@@ -1524,8 +1524,7 @@ extern "C" int32_t nyx_hip_target_batch_device(nyx_hip_ctx *ctx, const nyx_hip_s
     a.keep = (double *)ctx->d_tgt;
     a.flag = (int32_t *)(a.keep + (size_t)TGT_KEEP_ROWS * (size_t)ctx->tgt_cap);
     a.active = a.flag + ctx->tgt_cap;
-    a.n_chain = q->n_chain;
-    for (int k = 0; k < q->n_chain; ++k) { a.sign[k] = (double)q->chain_sign[k]; a.seg[k] = ctx->host_cfg.seg[q->chain_segment[k]]; }
+    a.chain = resolve_chain(chain_view(*q), ctx->host_cfg.seg);
     a.records = ctx->d_records;
     a.o_status = res->status; a.o_iterations = res->iterations; a.o_correction = res->correction; a.o_errors = res->achieved_errors;
     a.corrected = tgt_rows(res->corrected, nullptr);

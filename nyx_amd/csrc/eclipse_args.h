@@ -1,10 +1,11 @@
 // eclipse_args.h — launch arguments of the eclipse kernels (eclipse_kernel.hip), shared with abi.cpp, and what the host works out
-// once per call: which intermediates the requested parameters need, and the DISTINCT ephemeris segments of the chains of the
-// light source and the shadow bodies (host and device; no HIP).
+// once per call: which intermediates the requested parameters need, and the chains of the light source and the shadow bodies reduced
+// to their distinct segments (chain_args.h) (host and device; no HIP).
 #pragma once
 #include <stdint.h>
 
 #include "../../include/nyx_hip_eclipse.h"
+#include "chain_args.h"
 #include "devcfg.h"
 
 // shared intermediates of one sample: each is computed only when a requested parameter needs it
@@ -18,13 +19,11 @@ enum {
 #define ECL_MAX_USEG DEV_MAX_SEG
 static_assert(ECL_MAX_USEG <= NYX_HIP_MAX_SEGMENTS, "the distinct segments of a query are segments of the configuration");
 
-// A chain as the kernel walks it: position = sum_k sign[k] * (vector of distinct segment useg[k]), in chain order
-struct EclChain {
-    int32_t n_chain;
-    int32_t useg[NYX_HIP_MAX_CHAIN];  // indices into EclArgs.seg
-    double sign[NYX_HIP_MAX_CHAIN];
+// The chain of a body with a disk (useg: indices into EclArgs.seg / LnkArgs.seg)
+struct EclChain : ReducedChain {
     double radius_km;
 };
+static_assert(sizeof(EclChain) == sizeof(ReducedChain) + sizeof(double), "the radius follows the signs without padding");
 
 struct EclArgs {
     nyx_hip_traj_t src;   // device pointers, step-major [k * n + i]
@@ -71,30 +70,15 @@ static inline void ecl_needs(EclArgs &a) {
     }
 }
 
-// The chains of a.q (the light source first, then the bodies in order) reduced to their distinct segments: a.n_useg, a.seg_index,
-// a.seg (rows of `ctx_seg`, the context's DevCfg.seg), a.light, a.body.  Earth -> EMB is on the chain of the Sun AND of the Moon of
-// an Earth-centred context: it is evaluated once per sample.  The chain order is kept, so the sums are those of the oracle's
-// body_position.  Returns false (nothing usable in `a`) when the chains name more than ECL_MAX_USEG distinct segments, which a query
-// check_ecl_series has accepted cannot.
-// (ecl_reduce_chain is the step of ONE body, over the distinct segments found so far: the link report, link_args.h, shares it)
+// The chains of a.q (the light source first, then the bodies in order) reduced to their distinct segments (reduce_chain of
+// chain_args.h, body after body): a.n_useg, a.seg_index, a.seg, a.light, a.body.  Earth -> EMB is on the chain of the Sun AND of the
+// Moon of an Earth-centred context: it is evaluated once per sample.  Returns false (nothing usable in `a`) when the chains name more
+// than ECL_MAX_USEG distinct segments, which a query check_ecl_series has accepted cannot.
+// (ecl_reduce_chain is the step of ONE body: the link report, link_args.h, shares it)
 static inline bool ecl_reduce_chain(const nyx_hip_ecl_body_t &src, EclChain &dst, int32_t &n_useg, int32_t *seg_index, DevSeg *seg,
                                     const DevSeg *ctx_seg) {
-    dst.n_chain = src.n_chain;
     dst.radius_km = src.mean_radius_km;
-    for (int k = 0; k < NYX_HIP_MAX_CHAIN; ++k) { dst.useg[k] = 0; dst.sign[k] = 0.0; }
-    for (int k = 0; k < src.n_chain; ++k) {
-        int u = 0;
-        while (u < n_useg && seg_index[u] != src.chain_segment[k]) ++u;
-        if (u == n_useg) {
-            if (n_useg == ECL_MAX_USEG) return false;
-            seg_index[u] = src.chain_segment[k];
-            seg[u] = ctx_seg[src.chain_segment[k]];
-            ++n_useg;
-        }
-        dst.useg[k] = u;
-        dst.sign[k] = (double)src.chain_sign[k];
-    }
-    return true;
+    return reduce_chain(chain_view(src), dst, n_useg, seg_index, seg, ECL_MAX_USEG, ctx_seg);
 }
 static inline bool ecl_reduce_chains(EclArgs &a, const DevSeg *ctx_seg) {
     a.n_useg = 0;

@@ -13,7 +13,7 @@
 // alive across `traj_at` in AGPRs through copies under an empty exec mask).  Pass 1 interpolates the tile and parks the inertial
 // POSITION in LDS - three components, not six, so the tile is sixteen samples at the station views' 24 KiB.  Pass 2 walks the parked
 // positions: every DISTINCT segment of the chains in use is evaluated once per sample, per lane, at the lane's own sample epoch
-// (eclipse_dev.h: the Clenshaw recurrence; the segment rows are kernel arguments, scalar loads) and its vector parked in LDS too
+// (chain_dev.h: the Clenshaw recurrence; the segment rows are kernel arguments, scalar loads) and its vector parked in LDS too
 // - a column per lane, written and read by that lane alone, no barrier - because the chains index the segments with a scalar that
 // is not a compile-time constant; then the chains are summed in chain order (the additions of the oracle's body_position), then
 // the overlap formula per body, then the parameters.  No loop encloses both passes: nothing of the asin / acos constants or the
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(LANES) void nyxecl_values_kernel(EclArgs a) {
 #pragma unroll 1
         for (int u = 0; u < a.n_useg; ++u) {
             double p[3];
-            const int s1 = ecl_cheby(a.seg[u], a.records, et, p);
+            const int s1 = frm_cheby_pv(a.seg[u], a.records, et, false, p, nullptr);
             if (s1) st = s1;
             segpos[u][0][lane] = p[0];
             segpos[u][1][lane] = p[1];
@@ -145,16 +145,9 @@ __global__ __launch_bounds__(LANES) void nyxecl_values_kernel(EclArgs a) {
         EclModel m;
         double r_ls[3];
         {
-            double b0 = 0.0, b1 = 0.0, b2 = 0.0;
-#pragma unroll 1
-            for (int k = 0; k < a.light.n_chain; ++k) {
-                const double sg = a.light.sign[k];
-                const int u = a.light.useg[k];
-                b0 = b0 + sg * segpos[u][0][lane];
-                b1 = b1 + sg * segpos[u][1][lane];
-                b2 = b2 + sg * segpos[u][2][lane];
-            }
-            r_ls[0] = b0 - r[0]; r_ls[1] = b1 - r[1]; r_ls[2] = b2 - r[2];
+            double b[3];
+            chain_sum<3>(a.light, &segpos[0][0][lane], 3 * LANES, LANES, b);
+            r_ls[0] = b[0] - r[0]; r_ls[1] = b[1] - r[1]; r_ls[2] = b[2] - r[2];
         }
         m.n_ls = ecl_norm3(r_ls);
         m.ls_p = qnan;
@@ -166,16 +159,9 @@ __global__ __launch_bounds__(LANES) void nyxecl_values_kernel(EclArgs a) {
             for (int b = 0; b < a.q.n_bodies; ++b) {
                 if (!(a.need & ECL_NEED_MODEL) && !((a.body_mask >> b) & 1)) continue;
                 const EclChain &ch = a.body[b];
-                double b0 = 0.0, b1 = 0.0, b2 = 0.0;
-#pragma unroll 1
-                for (int k = 0; k < ch.n_chain; ++k) {
-                    const double sg = ch.sign[k];
-                    const int u = ch.useg[k];
-                    b0 = b0 + sg * segpos[u][0][lane];
-                    b1 = b1 + sg * segpos[u][1][lane];
-                    b2 = b2 + sg * segpos[u][2][lane];
-                }
-                const double r_eb[3] = {r[0] - b0, r[1] - b1, r[2] - b2};
+                double pb[3];
+                chain_sum<3>(ch, &segpos[0][0][lane], 3 * LANES, LANES, pb);
+                const double r_eb[3] = {r[0] - pb[0], r[1] - pb[1], r[2] - pb[2]};
                 const EclDisk d = ecl_occultation(m.ls_p, m.n_ls, ch.radius_km, r_eb, r_ls);
                 if (d.pct > m.best) { m.best = d.pct; m.winner = b; }
                 if ((a.body_mask >> b) & 1) {

@@ -1,10 +1,11 @@
 // frame_args.h — launch arguments of the encounter kernels (frame_kernel.hip), shared with abi.cpp, and what the host works out once
 // per call: which intermediates the requested parameters need, and the DISTINCT ephemeris segments of the target's chain (host and
-// device; no HIP).  The idea of eclipse_args.h (ecl_reduce_chains, EclChain) for the ONE chain of this report.
+// device; no HIP).  The reduction is reduce_chain of chain_args.h, for the ONE chain of this report.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/nyx_hip_frame.h"
+#include "chain_args.h"
 #include "devcfg.h"
 #include "report_args.h"   // REP_NEED_*, report_param_needs: codes 0 .. 18 are enum nyx_hip_state_param
 
@@ -20,13 +21,6 @@ static_assert((REP_NEED_R | REP_NEED_V | REP_NEED_H | REP_NEED_ENERGY | REP_NEED
 // There is one chain here: its distinct segments are no more than its links
 #define FRM_MAX_USEG NYX_HIP_MAX_CHAIN
 
-// The chain as the kernel walks it: state = sum_k sign[k] * (position and velocity of distinct segment useg[k]), in chain order
-struct FrmChain {
-    int32_t n_chain;
-    int32_t useg[NYX_HIP_MAX_CHAIN];  // indices into FrmArgs.seg
-    double sign[NYX_HIP_MAX_CHAIN];
-};
-
 struct FrmArgs {
     nyx_hip_traj_t src;   // device pointers, step-major [k * n + i]
     int64_t n;            // trajectories
@@ -38,7 +32,7 @@ struct FrmArgs {
     int32_t n_useg;                   // distinct segments of the chain, filled by frm_reduce_chain
     int32_t seg_index[FRM_MAX_USEG];  // which segment of the context each is (first use first)
     DevSeg seg[FRM_MAX_USEG];         // its row of DevCfg.seg: kernel arguments, scalar loads
-    FrmChain chain;
+    ReducedChain chain;               // (useg: indices into seg)
     int32_t need;                     // FRM_NEED_* | REP_NEED_* of q.param[0 .. n_params), filled by the launcher
     int64_t sample0;                  // the first sample of this launch of the evaluation kernel, filled by the launcher
 };
@@ -71,21 +65,8 @@ static inline void frm_needs(FrmArgs &a) {
     for (int p = 0; p < a.q.n_params; ++p) a.need |= frm_param_needs(a.q.param[p]);
 }
 
-// The chain of a.q reduced to its distinct segments: a.n_useg, a.seg_index, a.seg (rows of `ctx_seg`, the context's DevCfg.seg),
-// a.chain.  The chain order is kept, so the sums are those of the oracle's frame_shift.
+// The chain of a.q reduced to its distinct segments: a.n_useg, a.seg_index, a.seg, a.chain (n_chain <= FRM_MAX_USEG: always room)
 static inline void frm_reduce_chain(FrmArgs &a, const DevSeg *ctx_seg) {
     a.n_useg = 0;
-    a.chain.n_chain = a.q.n_chain;
-    for (int k = 0; k < NYX_HIP_MAX_CHAIN; ++k) { a.chain.useg[k] = 0; a.chain.sign[k] = 0.0; }
-    for (int k = 0; k < a.q.n_chain; ++k) {
-        int u = 0;
-        while (u < a.n_useg && a.seg_index[u] != a.q.chain_segment[k]) ++u;
-        if (u == a.n_useg) {   // (n_chain <= FRM_MAX_USEG: always room)
-            a.seg_index[u] = a.q.chain_segment[k];
-            a.seg[u] = ctx_seg[a.q.chain_segment[k]];
-            ++a.n_useg;
-        }
-        a.chain.useg[k] = u;
-        a.chain.sign[k] = (double)a.q.chain_sign[k];
-    }
+    reduce_chain(chain_view(a.q), a.chain, a.n_useg, a.seg_index, a.seg, FRM_MAX_USEG, ctx_seg);
 }

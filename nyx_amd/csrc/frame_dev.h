@@ -1,10 +1,7 @@
-// frame_dev.h — what the encounter kernel (frame_kernel.hip) evaluates per sample, written so that the SAME TEXT compiles for the
-// device and for the host (FRM_FN): tests/cxx/frame_host_check.cpp runs the very code of the kernel on the CPU.  A stand-alone
-// restatement, on purpose, of pieces that stay untouched - their code objects and budgets do not move with this report:
-//   frm_cheby_pv   SPK type 2 with the derivative, as oracle/nyx_oracle.c restates CHBINT (`cheby_eval_pv`): the rolled Clenshaw
-//                  recurrence w0 = cf[j] + (two_t * w1 - w2) with its companion d0 = (2 * w1 + two_t * d1) - d2,
-//                  r = cf[0] + (t * w0 - w1), v = ((w0 + t * d0) - d1) / radius; honours DevSeg.stride (the host may have laid the
-//                  records out sixteen coefficients wide, zero-padded) and the range rule of ecl_cheby (eclipse_dev.h)
+// frame_dev.h — what the encounter kernel (frame_kernel.hip) evaluates per sample beside the chain (chain_dev.h), written so that the
+// SAME TEXT compiles for the device and for the host (FRM_FN): tests/cxx/frame_host_check.cpp runs the very code of the kernel on the
+// CPU.  A stand-alone restatement, on purpose, of pieces that stay untouched - their code objects and budgets do not move with this
+// report:
 //   frm_shared / frm_param   the nineteen parameters of enum nyx_hip_state_param as report_kernel.hip evaluates them (that kernel's
 //                  rep_shared / rep_value live in its translation unit; the needs come from report_args.h, which is included)
 //   frm_bplane     BdotT / BdotR after cosmic/bplane.rs, as include/nyx_hip_frame.h writes them out
@@ -14,53 +11,10 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "chain_dev.h"
 #include "frame_args.h"
 
-#if defined(__HIPCC__)
-#define FRM_FN static __host__ __device__ __forceinline__
-#else
-#define FRM_FN static inline
-#endif
-
-// Position and (with_v) velocity of one segment at et_s -> r3, v3; NYX_HIP_OK, or NYX_HIP_ERR_EPHEM_RANGE when et_s lies outside
-// the segment (r3 / v3 are then the clamped record's: never used).  `records` is the context's table in its DEVICE layout.
-// `with_v` is the same for every lane; without it v3 is left alone and the companion recurrence is not run.
-FRM_FN int frm_cheby_pv(const DevSeg &sg, const double *records, double et_s, bool with_v, double *r3, double *v3) {
-    const double rel = (et_s - sg.init_et) / sg.interval;
-    const double fl = floor(rel);
-    int st = NYX_HIP_OK;
-    // (compared as doubles: an epoch far outside the segment must not overflow the conversion)
-    if (!(fl >= 0.0) || fl > (double)sg.n_rec || (fl == (double)sg.n_rec && et_s > sg.end_et)) st = NYX_HIP_ERR_EPHEM_RANGE;
-    int idx = !(fl >= 0.0) ? 0 : (fl >= (double)sg.n_rec ? sg.n_rec - 1 : (int)fl);
-    const int nc = sg.n_coef;
-    const int cs = (sg.stride - 2) / 3;  // doubles per component: n_coef, or sixteen when the host padded the record with zeros
-    const double *rec = records + sg.offset + (int64_t)idx * sg.stride;
-    const double t = (et_s - rec[0]) / rec[1];
-    const double two_t = 2.0 * t;
-    for (int c = 0; c < 3; ++c) {
-        const double *cf = rec + 2 + c * cs;
-        double w0 = 0.0, w1 = 0.0, w2, d0 = 0.0, d1 = 0.0, d2;
-        if (with_v) {
-            for (int j = nc - 1; j >= 1; --j) {
-                w2 = w1;
-                w1 = w0;
-                w0 = cf[j] + (two_t * w1 - w2);
-                d2 = d1;
-                d1 = d0;
-                d0 = (2.0 * w1 + two_t * d1) - d2;
-            }
-            v3[c] = ((w0 + t * d0) - d1) / rec[1];
-        } else {
-            for (int j = nc - 1; j >= 1; --j) {
-                w2 = w1;
-                w1 = w0;
-                w0 = cf[j] + (two_t * w1 - w2);
-            }
-        }
-        r3[c] = cf[0] + (t * w0 - w1);
-    }
-    return st;
-}
+#define FRM_FN CHAIN_FN
 
 constexpr double FRM_DEG = 180.0 / 3.14159265358979323846;  // np.degrees: x * (180 / pi)
 

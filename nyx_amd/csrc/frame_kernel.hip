@@ -116,14 +116,8 @@ __global__ __launch_bounds__(LANES) void nyxfrm_values_kernel(FrmArgs a) {
         // the target: its chain in chain order, then rv' = rv - body
         double y[6];
         {
-            double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-            for (int k = 0; k < a.chain.n_chain; ++k) {
-                const double sg = a.chain.sign[k];
-                const int u = a.chain.useg[k];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) b[c] = b[c] + sg * segpv[u][c][lane];
-            }
+            double b[6];
+            chain_sum<6>(a.chain, &segpv[0][0][lane], 6 * LANES, LANES, b);
             // (an empty chain subtracts +0: the identity, bit for bit - a signed zero of the state included)
 #pragma unroll
             for (int c = 0; c < 6; ++c) y[c] = parked[t][c][lane] - b[c];

@@ -1,22 +1,15 @@
 // lambert_args.h — launch arguments of the Lambert kernels (lambert_kernel.hip), shared with abi.cpp, and what the two entries of
 // include/nyx_hip_lambert.h refuse before anything is launched (host and device text; no HIP).  The refusals are data (Refusal,
-// series_host.h) and are tested on the CPU (tests/test_lambert_abi.py through the C entries).
+// refusal.h) and are tested on the CPU (tests/test_lambert_abi.py through the C entries).  The three chains of a grid are
+// ResolvedChains (chain_args.h).
 #pragma once
 #include <stdint.h>
 
 #include <cmath>
 
 #include "../../include/nyx_hip_lambert.h"
+#include "chain_args.h"   // Refusal, bad_arg, ResolvedChain
 #include "devcfg.h"
-#include "series_host.h"   // Refusal, bad_arg
-
-// One chain as the kernel walks it: state = sum_k sign[k] * (position and velocity of seg[k]), in chain order, from zero.  The
-// segment rows travel as kernel arguments (scalar loads, the same for every lane).
-struct LmbChain {
-    int32_t n_chain, _pad;
-    double sign[NYX_HIP_MAX_CHAIN];
-    DevSeg seg[NYX_HIP_MAX_CHAIN];
-};
 
 struct LmbBatchArgs {
     const double *rv1, *rv2, *tof_s;  // device pointers, component-major [c * n + i]
@@ -30,21 +23,11 @@ struct LmbBatchArgs {
 struct LmbGridArgs {
     nyx_hip_lambert_grid_query_t q;
     const double *records;   // the context's ephemeris records on the device (DevSeg.offset points into it)
-    LmbChain dep, arr, centre;
+    ResolvedChain dep, arr, centre;   // filled by the launcher (resolve_chain)
     double *values;    // [n_params][n_dep][n_arr]
     int32_t *status;   // [n_dep][n_arr]
 };
 static_assert(sizeof(LmbGridArgs) <= 4096, "LmbGridArgs must fit the kernel-argument segment");
-
-static inline LmbChain lmb_chain(const nyx_hip_lambert_chain_t &c, const DevSeg *ctx_seg) {
-    LmbChain out = {};
-    out.n_chain = c.n_chain;
-    for (int k = 0; k < c.n_chain; ++k) {
-        out.sign[k] = (double)c.chain_sign[k];
-        out.seg[k] = ctx_seg[c.chain_segment[k]];
-    }
-    return out;
-}
 
 // ---- refusals.  The solver's settings first, in the order of the header's list
 inline Refusal check_lambert_query(const char *name, const nyx_hip_ctx *ctx, const nyx_hip_lambert_query_t *q, double mu_km3_s2) {
@@ -80,15 +63,6 @@ inline bool lmb_same_chain(const nyx_hip_lambert_chain_t &a, const nyx_hip_lambe
     return true;
 }
 
-inline Refusal check_lambert_chain(const char *name, const char *who, const nyx_hip_lambert_chain_t &c) {
-    if (c.n_chain < 0 || c.n_chain > NYX_HIP_MAX_CHAIN) return bad_arg("%s: %s.n_chain = %d, 0 .. %d segments", name, who, c.n_chain, NYX_HIP_MAX_CHAIN);
-    for (int k = 0; k < c.n_chain; ++k) {
-        if (c.chain_segment[k] < 0) return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context", name, who, k, c.chain_segment[k]);
-        if (c.chain_sign[k] != 1 && c.chain_sign[k] != -1) return bad_arg("%s: %s.chain_sign[%d] = %d, +1 or -1", name, who, k, c.chain_sign[k]);
-    }
-    return {};
-}
-
 // check_lambert_grid never dereferences the context; check_lambert_context is what the query asks of it (of a query the first accepted)
 inline Refusal check_lambert_grid(const nyx_hip_ctx *ctx, const nyx_hip_lambert_grid_query_t *q, const double *values, const int32_t *status) {
     const char *name = "lambert_grid";
@@ -101,26 +75,18 @@ inline Refusal check_lambert_grid(const nyx_hip_ctx *ctx, const nyx_hip_lambert_
     if (q->dep_step_ns <= 0) return bad_arg("%s: dep_step_ns must be > 0", name);
     if (q->has_tof ? q->tof_step_ns <= 0 : q->arr_step_ns <= 0) return bad_arg("%s: %s must be > 0", name, q->has_tof ? "tof_step_ns" : "arr_step_ns");
     if (!values || !status) return bad_arg("%s: values and status arrays required", name);
-    if (Refusal r = check_lambert_chain(name, "dep", q->dep)) return r;
-    if (Refusal r = check_lambert_chain(name, "arr", q->arr)) return r;
-    if (Refusal r = check_lambert_chain(name, "centre", q->centre)) return r;
+    if (Refusal r = check_chain(name, "dep", chain_view(q->dep), 0)) return r;
+    if (Refusal r = check_chain(name, "arr", chain_view(q->arr), 0)) return r;
+    if (Refusal r = check_chain(name, "centre", chain_view(q->centre), 0)) return r;
     if (lmb_same_chain(q->dep, q->centre)) return bad_arg("%s: the departure body's chain is the centre's: its radius is zero by construction", name);
     if (lmb_same_chain(q->arr, q->centre)) return bad_arg("%s: the arrival body's chain is the centre's: its radius is zero by construction", name);
     return {};
 }
 inline Refusal check_lambert_context(const nyx_hip_lambert_grid_query_t &q, int n_seg, bool frame_swapped) {
     const char *name = "lambert_grid";
-    const nyx_hip_lambert_chain_t *chains[3] = {&q.dep, &q.arr, &q.centre};
-    const char *who[3] = {"dep", "arr", "centre"};
-    for (int b = 0; b < 3; ++b)
-        for (int k = 0; k < chains[b]->n_chain; ++k)
-            if (chains[b]->chain_segment[k] >= n_seg)
-                return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, who[b], k, chains[b]->chain_segment[k], n_seg - 1);
-    if (frame_swapped) {
-        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): its chains are not those of "
-                            "the states it integrates", name);
-        r.rc = NYX_HIP_RC_UNSUPPORTED;
-        return r;
-    }
+    if (Refusal r = check_chain_context(name, "dep", chain_view(q.dep), n_seg)) return r;
+    if (Refusal r = check_chain_context(name, "arr", chain_view(q.arr), n_seg)) return r;
+    if (Refusal r = check_chain_context(name, "centre", chain_view(q.centre), n_seg)) return r;
+    if (frame_swapped) return frame_swap_refusal(name, "its chains are not those of the states it integrates");   // NYX_HIP_RC_UNSUPPORTED
     return {};
 }

@@ -2,21 +2,20 @@
 // device and for the host (LMB_FN, as FRM_FN of frame_dev.h).  It restates nyx_amd/lambert.py - the definition, which carries the
 // method, its source and the four departures from the reference's izzo.rs (the natural normal, the series window x > 0, the way on
 // multi-revolution requests, the closed form of T without its cancellations) - OPERATION FOR OPERATION: one rounding per operation, sums of three as ((a0 + a1) + a2), powers written
-// out as products.  Compile with -ffp-contract=off.  The chains go through frm_cheby_pv (frame_dev.h), which is included, not copied.
+// out as products.  Compile with -ffp-contract=off.  The chains go through chain_pv (chain_dev.h), which is included, not copied.
 //
 // Every loop is bounded on both sides: Halley and Householder by max_iter (<= 1000), the series by NYX_HIP_LMB_SERIES_MAX terms.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
-#include "frame_dev.h"
+#include "frame_dev.h"   // FRM_DEG; chain_dev.h
 #include "lambert_args.h"
 
+#define LMB_FN CHAIN_FN
 #if defined(__HIPCC__)
-#define LMB_FN static __host__ __device__ __forceinline__
 #define LMB_OOL static __host__ __device__ __noinline__
 #else
-#define LMB_FN static inline
 #define LMB_OOL static inline
 #endif
 
@@ -262,29 +261,11 @@ LMB_FN double lmb_param(int32_t param, const LmbSol &s) {
     }
 }
 
-// The signed sum of a chain at et_s, in chain order, from zero -> rv6; NYX_HIP_OK, or NYX_HIP_ERR_EPHEM_RANGE of one of its segments
-LMB_FN int lmb_chain_pv(const LmbChain &ch, const double *records, double et_s, double rv6[6]) {
-    int st = NYX_HIP_OK;
-    for (int c = 0; c < 6; ++c) rv6[c] = 0.0;
-#if defined(__HIPCC__)
-#pragma unroll 1   // (n_chain is a scalar: one copy of the recurrence)
-#endif
-    for (int k = 0; k < ch.n_chain; ++k) {
-        double p[3], pv[3];
-        if (const int s1 = frm_cheby_pv(ch.seg[k], records, et_s, true, p, pv)) st = s1;
-        for (int c = 0; c < 3; ++c) {
-            rv6[c] = rv6[c] + ch.sign[k] * p[c];
-            rv6[3 + c] = rv6[3 + c] + ch.sign[k] * pv[c];
-        }
-    }
-    return st;
-}
-
 // A body's state about the centre at et_s: chain(body) - chain(centre), component by component
-LMB_FN int lmb_body_state(const LmbChain &body, const LmbChain &centre, const double *records, double et_s, double rv6[6]) {
+LMB_FN int lmb_body_state(const ResolvedChain &body, const ResolvedChain &centre, const double *records, double et_s, double rv6[6]) {
     double b[6], c[6];
-    const int st_b = lmb_chain_pv(body, records, et_s, b);
-    const int st_c = lmb_chain_pv(centre, records, et_s, c);
+    const int st_b = chain_pv(body, records, et_s, b);
+    const int st_c = chain_pv(centre, records, et_s, c);
     for (int k = 0; k < 6; ++k) rv6[k] = b[k] - c[k];
     return st_b ? st_b : st_c;
 }

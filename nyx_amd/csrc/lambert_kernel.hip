@@ -8,7 +8,7 @@
 // GRID: one launch, no global scratch, no atomics.  A workgroup of eight waves owns a tile of LMB_TD = 8 departures x LMB_TA = 64
 // arrivals, the arrival index on the lanes, so that values[(p * n_dep + i) * n_arr + j] is written in coalesced rows.  The tile's
 // departure states are evaluated once each by the first eight lanes of wave 0 and, where the arrivals are given by epoch, the tile's
-// arrival states once each by the lanes of wave 1 at the same time (Clenshaw with the companion derivative, frm_cheby_pv, the body's
+// arrival states once each by the lanes of wave 1 at the same time (Clenshaw with the companion derivative, chain_pv of chain_dev.h, the body's
 // chain minus the centre's), and parked in LDS: (8 + 64) x 6 doubles and the status words, under 4 KiB.  After ONE barrier wave w
 // solves the cells of departure w of the tile: the lane reads its arrival state from LDS and the departure state as an LDS
 // broadcast.  Lanes past the edge of the grid take part in the barrier and store nothing.
@@ -128,9 +128,9 @@ extern "C" hipError_t nyx_launch_lambert_batch(const LmbBatchArgs *args, hipStre
 extern "C" hipError_t nyx_launch_lambert_grid(const LmbGridArgs *args, const DevSeg *ctx_seg, hipStream_t stream) {
     LmbGridArgs a = *args;
     if (a.q.n_dep <= 0 || a.q.n_arr <= 0) return hipSuccess;
-    a.dep = lmb_chain(a.q.dep, ctx_seg);
-    a.arr = lmb_chain(a.q.arr, ctx_seg);
-    a.centre = lmb_chain(a.q.centre, ctx_seg);
+    a.dep = resolve_chain(chain_view(a.q.dep), ctx_seg);
+    a.arr = resolve_chain(chain_view(a.q.arr), ctx_seg);
+    a.centre = resolve_chain(chain_view(a.q.centre), ctx_seg);
     const int64_t tiles_d = (a.q.n_dep + LMB_TD - 1) / LMB_TD, tiles_a = (a.q.n_arr + LMB_TA - 1) / LMB_TA;
     if (tiles_d * tiles_a > INT32_MAX) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nyxlmb_grid_kernel, dim3((unsigned)(tiles_d * tiles_a)), dim3(LMB_TILE), 0, stream, a, tiles_a);

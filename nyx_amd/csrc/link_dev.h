@@ -1,11 +1,11 @@
 // link_dev.h — what the link kernel (link_kernel.hip) evaluates per sample, written so that the SAME TEXT compiles for the device and
 // for the host (LNK_FN): tests/cxx/link_host_check.cpp runs the very code of the kernel's second pass on the CPU.  No HIP includes,
 // nothing read from the process.
-//   lnk_segments   every DISTINCT segment of the chains in use once, at one epoch (ecl_cheby of eclipse_dev.h, position only), parked
+//   lnk_segments   every DISTINCT segment of the chains in use once, at one epoch (frm_cheby_pv of chain_dev.h, position only), parked
 //                  where the caller says: base[u * su + c * sc] is component c of distinct segment u (the kernel: a column of LDS per
 //                  lane, written and read by that lane alone; the host check: a plain array)
 //   lnk_sight      Vallado's SIGHT test of one body, as include/nyx_hip_link.h states it
-//   lnk_sample     the second pass of one sample: the shared intermediates `need` names, the chains summed in chain order, the SIGHT
+//   lnk_sample     the second pass of one sample: the shared intermediates `need` names, the chains summed in chain order (chain_sum), the SIGHT
 //                  test per body, every requested parameter handed to `put(p, value)`
 // nyx_amd/links.py restates this operation for operation (sums of three as ((a0 + a1) + a2)); only + - x /, sqrt and comparisons:
 // compile with -ffp-contract=off and the two agree to the last bit.
@@ -13,15 +13,11 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "eclipse_dev.h"   // ECL_FN, ecl_cheby
+#include "chain_dev.h"
 #include "link_args.h"
 
-#define LNK_FN ECL_FN
-#if defined(__HIPCC__)
-#define LNK_ROLLED _Pragma("unroll 1")   // one copy of the body: the trip count and what the body branches on are scalars
-#else
-#define LNK_ROLLED
-#endif
+#define LNK_FN CHAIN_FN
+#define LNK_ROLLED CHAIN_ROLLED
 
 // NYX_HIP_OK, or NYX_HIP_ERR_EPHEM_RANGE when et_s lies outside one of the segments (what was parked is then never used).  Nothing is
 // evaluated when no body has a chain (n_useg == 0).
@@ -30,7 +26,7 @@ LNK_FN int lnk_segments(const LnkArgs &a, double et_s, double *base, int su, int
     LNK_ROLLED
     for (int u = 0; u < a.n_useg; ++u) {
         double p[3];
-        const int s1 = ecl_cheby(a.seg[u], a.records, et_s, p);
+        const int s1 = frm_cheby_pv(a.seg[u], a.records, et_s, false, p, nullptr);
         if (s1) st = s1;
         base[u * su] = p[0];
         base[u * su + sc] = p[1];
@@ -78,15 +74,8 @@ LNK_FN void lnk_sample(const LnkArgs &a, const double *rx6, const double *tx6, c
         for (int b = 0; b < a.q.n_bodies; ++b) {
             if (!(a.need & LNK_NEED_SIGHT) && !((a.body_mask >> b) & 1)) continue;
             const EclChain &ch = a.body[b];
-            double pos[3] = {0.0, 0.0, 0.0};   // (an empty chain: the centre itself)
-            LNK_ROLLED
-            for (int k = 0; k < ch.n_chain; ++k) {
-                const double sg = ch.sign[k];
-                const int u = ch.useg[k];
-                pos[0] = pos[0] + sg * base[u * su];
-                pos[1] = pos[1] + sg * base[u * su + sc];
-                pos[2] = pos[2] + sg * base[u * su + 2 * sc];
-            }
+            double pos[3];   // (an empty chain: the centre itself)
+            chain_sum<3>(ch, base, su, sc, pos);
             const LnkSight s = lnk_sight(rx6, tx6, pos, ch.radius_km);
             if (s.obstructs && first < 0.0) first = (double)b;
             if (s.clearance < clearance) clearance = s.clearance;

@@ -4,12 +4,12 @@
 #pragma once
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
 #include "aer_args.h"
+#include "chain_args.h"   // Refusal, bad_arg (refusal.h), check_chain, check_chain_context, frame_swap_refusal
 #include "eclipse_args.h"
 #include "frame_args.h"
 #include "groundtrack_args.h"
@@ -17,22 +17,6 @@
 #include "report_args.h"
 #include "ric_args.h"
 #include "traj_args.h"
-
-// A refusal as data: the return code and the message the caller hands to nyx_set_error.  rc == NYX_HIP_RC_OK: accepted.
-struct Refusal {
-    int rc = NYX_HIP_RC_OK;
-    char msg[256] = "";
-    explicit operator bool() const { return rc != NYX_HIP_RC_OK; }
-};
-__attribute__((format(printf, 1, 2))) inline Refusal bad_arg(const char *fmt, ...) {
-    Refusal r;
-    r.rc = NYX_HIP_RC_BAD_ARG;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(r.msg, sizeof r.msg, fmt, ap);
-    va_end(ap);
-    return r;
-}
 
 inline Refusal check_traj(const nyx_hip_traj_t *t, const char *what, bool need_epochs) {
     if (!t || t->capacity < 0 || !t->len || !t->x_km || !t->y_km || !t->z_km || !t->vx_km_s || !t->vy_km_s || !t->vz_km_s ||
@@ -145,7 +129,8 @@ inline Refusal check_aer_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *tr
 // The eclipses are checked in two steps.  check_ecl_series is what its siblings are - it never dereferences the context - and
 // refuses everything that can be told from the query alone.  check_ecl_context is what the query asks OF the context, checked once the
 // query itself is sound: every chain segment is one of the context's `n_seg` (DevCfg.n_seg), and the context was not built with an
-// integration-frame swap (`frame_swapped`: state_frame_body != 0) - the one refusal that is not a bad argument.
+// integration-frame swap (`frame_swapped`: state_frame_body != 0) - the one refusal that is not a bad argument.  The chain rules
+// themselves are chain_args.h's.
 inline const char *ecl_body_name(char (&who)[32], const char *which, int index) {
     if (index < 0) std::snprintf(who, sizeof who, "%s", which);
     else std::snprintf(who, sizeof who, "%s[%d]", which, index);
@@ -154,12 +139,7 @@ inline const char *ecl_body_name(char (&who)[32], const char *which, int index) 
 inline Refusal check_ecl_body(const char *name, const char *which, int index, const nyx_hip_ecl_body_t &b, int min_chain) {
     char who[32];
     ecl_body_name(who, which, index);
-    if (b.n_chain < min_chain || b.n_chain > NYX_HIP_MAX_CHAIN)
-        return bad_arg("%s: %s.n_chain = %d, %d .. %d segments", name, who, b.n_chain, min_chain, NYX_HIP_MAX_CHAIN);
-    for (int k = 0; k < b.n_chain; ++k) {
-        if (b.chain_segment[k] < 0) return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context", name, who, k, b.chain_segment[k]);
-        if (b.chain_sign[k] != 1 && b.chain_sign[k] != -1) return bad_arg("%s: %s.chain_sign[%d] = %d, +1 or -1", name, who, k, b.chain_sign[k]);
-    }
+    if (Refusal r = check_chain(name, who, chain_view(b), min_chain)) return r;
     if (!(std::isfinite(b.mean_radius_km) && b.mean_radius_km > 0.0)) return bad_arg("%s: %s.mean_radius_km must be finite and > 0", name, who);
     return {};
 }
@@ -184,19 +164,12 @@ inline Refusal check_ecl_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *tr
 inline Refusal check_ecl_context(const nyx_hip_ecl_query_t &q, int n_seg, bool frame_swapped) {
     const char *name = "traj_eclipse";
     for (int b = -1; b < q.n_bodies; ++b) {
-        const nyx_hip_ecl_body_t &body = b < 0 ? q.light : q.bodies[b];
         char who[32];
         ecl_body_name(who, b < 0 ? "light" : "bodies", b);
-        for (int k = 0; k < body.n_chain; ++k)
-            if (body.chain_segment[k] >= n_seg)
-                return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, who, k, body.chain_segment[k], n_seg - 1);
+        if (Refusal r = check_chain_context(name, who, chain_view(b < 0 ? q.light : q.bodies[b]), n_seg)) return r;
     }
-    if (frame_swapped) {
-        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
-                            "trajectories is in another frame than the rest, an eclipse series of them is not defined", name);
-        r.rc = NYX_HIP_RC_UNSUPPORTED;
-        return r;
-    }
+    if (frame_swapped)   // NYX_HIP_RC_UNSUPPORTED
+        return frame_swap_refusal(name, "the first stored state of its trajectories is in another frame than the rest, an eclipse series of them is not defined");
     return {};
 }
 
@@ -209,26 +182,16 @@ inline Refusal check_frame_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *
     if (Refusal r = series_open(name, ctx, traj, false, nullptr, q, n)) return r;
     if (Refusal r = series_params(name, *q, NYX_HIP_MAX_FRAME_PARAMS, frm_param_needs, "nyx_hip_frame_param", &need)) return r;
     if (Refusal r = series_span(name, q->step_ns, capacity)) return r;
-    if (q->n_chain < 0 || q->n_chain > NYX_HIP_MAX_CHAIN) return bad_arg("%s: n_chain = %d, 0 .. %d segments", name, q->n_chain, NYX_HIP_MAX_CHAIN);
-    for (int k = 0; k < q->n_chain; ++k) {
-        if (q->chain_segment[k] < 0) return bad_arg("%s: chain_segment[%d] = %d is not a segment of the context", name, k, q->chain_segment[k]);
-        if (q->chain_sign[k] != 1 && q->chain_sign[k] != -1) return bad_arg("%s: chain_sign[%d] = %d, +1 or -1", name, k, q->chain_sign[k]);
-    }
+    if (Refusal r = check_chain(name, "", chain_view(*q), 0)) return r;
     if (!(std::isfinite(q->mu_km3_s2) && q->mu_km3_s2 > 0.0)) return bad_arg("%s: mu_km3_s2 must be finite and > 0", name);
     return series_outputs(name, values, len);
 }
 // (of a query check_frame_series has accepted)
 inline Refusal check_frame_context(const nyx_hip_frame_query_t &q, int n_seg, bool frame_swapped) {
     const char *name = "traj_frame_values";
-    for (int k = 0; k < q.n_chain; ++k)
-        if (q.chain_segment[k] >= n_seg)
-            return bad_arg("%s: chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, k, q.chain_segment[k], n_seg - 1);
-    if (frame_swapped) {
-        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
-                            "trajectories is in another frame than the rest, a series of them about another centre is not defined", name);
-        r.rc = NYX_HIP_RC_UNSUPPORTED;
-        return r;
-    }
+    if (Refusal r = check_chain_context(name, "", chain_view(q), n_seg)) return r;
+    if (frame_swapped)   // NYX_HIP_RC_UNSUPPORTED
+        return frame_swap_refusal(name, "the first stored state of its trajectories is in another frame than the rest, a series of them about another centre is not defined");
     return {};
 }
 
@@ -275,19 +238,12 @@ inline Refusal check_link_series(const nyx_hip_ctx *ctx, const nyx_hip_traj_t *t
 inline Refusal check_link_context(const nyx_hip_link_query_t &q, int n_seg, bool frame_swapped) {
     const char *name = "traj_link";
     for (int b = 0; b < q.n_bodies; ++b) {
-        const nyx_hip_ecl_body_t &body = q.bodies[b];
         char who[32];
         ecl_body_name(who, "bodies", b);
-        for (int k = 0; k < body.n_chain; ++k)
-            if (body.chain_segment[k] >= n_seg)
-                return bad_arg("%s: %s.chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, who, k, body.chain_segment[k], n_seg - 1);
+        if (Refusal r = check_chain_context(name, who, chain_view(q.bodies[b]), n_seg)) return r;
     }
-    if (frame_swapped) {
-        Refusal r = bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): the first stored state of its "
-                            "trajectories is in another frame than the rest, a link series of them is not defined", name);
-        r.rc = NYX_HIP_RC_UNSUPPORTED;
-        return r;
-    }
+    if (frame_swapped)   // NYX_HIP_RC_UNSUPPORTED
+        return frame_swap_refusal(name, "the first stored state of its trajectories is in another frame than the rest, a link series of them is not defined");
     return {};
 }
 

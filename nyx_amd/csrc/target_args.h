@@ -1,15 +1,15 @@
 // target_args.h — launch arguments of the targeter kernels (target_kernel.hip), shared with abi.cpp, and what the two entries of
 // include/nyx_hip_target.h refuse before anything is launched (host and device text; no HIP).  The refusals are data (Refusal,
-// series_host.h) and are tested on the CPU (tests/test_target_abi.py through the C entries, tests/cxx/target_host_check.cpp directly).
+// refusal.h) and are tested on the CPU (tests/test_target_abi.py through the C entries, tests/cxx/target_host_check.cpp directly).
 #pragma once
 #include <stdint.h>
 
 #include <cmath>
 
 #include "../../include/nyx_hip_target.h"
+#include "chain_args.h"    // Refusal, bad_arg, ResolvedChain
 #include "devcfg.h"
 #include "frame_args.h"    // frm_param_needs
-#include "series_host.h"   // Refusal, bad_arg
 
 // What a run keeps between the iterations, one row of `cap` doubles each (TgtArgs.keep + row * cap + i)
 enum { TGT_XI_START = 0, TGT_XI = 6, TGT_TOTAL = 12, TGT_PREV = 18, TGT_PARK = 19 /* the Jacobian of the round, 36 rows */, TGT_KEEP_ROWS = 55 };
@@ -35,10 +35,7 @@ struct TgtArgs {
     int32_t *active;    // [iterations + 2] runs still active after round `it`
     int32_t it;         // the round of this launch of the step kernel
     int32_t need;       // tgt_needs(q): FRM_NEED_* | REP_NEED_* of the objectives, filled by the launcher
-    int32_t _pad;
-    int32_t n_chain;    // the objective target's chain, resolved against the context's segment rows by the launcher
-    double sign[NYX_HIP_MAX_CHAIN];
-    DevSeg seg[NYX_HIP_MAX_CHAIN];
+    ResolvedChain chain;   // the objective target's chain, resolved against the context's segment rows by the launcher
     const double *records;   // the context's ephemeris records on the device (DevSeg.offset points into it)
     // outputs
     int32_t *o_status, *o_iterations;
@@ -91,11 +88,7 @@ inline Refusal check_target(const nyx_hip_ctx *ctx, const nyx_hip_states_t *in, 
         if (!std::isfinite(q->obj_desired[o]) || !std::isfinite(q->obj_mult[o]) || !std::isfinite(q->obj_add[o]))
             return bad_arg("%s: obj_desired[%d], obj_mult[%d] and obj_add[%d] must be finite", name, o, o, o);
     }
-    if (q->n_chain < 0 || q->n_chain > NYX_HIP_MAX_CHAIN) return bad_arg("%s: n_chain = %d, 0 .. %d segments", name, q->n_chain, NYX_HIP_MAX_CHAIN);
-    for (int k = 0; k < q->n_chain; ++k) {
-        if (q->chain_segment[k] < 0) return bad_arg("%s: chain_segment[%d] = %d is not a segment of the context", name, k, q->chain_segment[k]);
-        if (q->chain_sign[k] != 1 && q->chain_sign[k] != -1) return bad_arg("%s: chain_sign[%d] = %d, +1 or -1", name, k, q->chain_sign[k]);
-    }
+    if (Refusal r = check_chain(name, "", chain_view(*q), 0)) return r;
     if (!(std::isfinite(q->mu_km3_s2) && q->mu_km3_s2 > 0.0)) return bad_arg("%s: mu_km3_s2 must be finite and > 0", name);
     if (!in || in->n < 0 || !tgt_has_rows(*in)) return bad_arg("%s: in: epoch and the six Cartesian arrays are mandatory", name);
     if (!res->status || !res->iterations || !res->correction || !res->achieved_errors)
@@ -112,15 +105,12 @@ inline Refusal check_target(const nyx_hip_ctx *ctx, const nyx_hip_states_t *in, 
 
 inline Refusal check_target_context(const nyx_hip_target_query_t &q, int n_seg, bool carries_stm, bool frame_swapped) {
     const char *name = "target_batch";
-    for (int k = 0; k < q.n_chain; ++k)
-        if (q.chain_segment[k] >= n_seg)
-            return bad_arg("%s: chain_segment[%d] = %d is not a segment of the context (0 .. %d)", name, k, q.chain_segment[k], n_seg - 1);
-    if (carries_stm || frame_swapped) {
-        Refusal r = carries_stm ? bad_arg("%s: the context carries STMs: the hyperdual targeter is not on the device path", name)
-                                : bad_arg("%s: the context was built with an integration-frame swap (state_frame_body != 0): its chains are not "
-                                          "those of the states it integrates", name);
+    if (Refusal r = check_chain_context(name, "", chain_view(q), n_seg)) return r;
+    if (carries_stm) {
+        Refusal r = bad_arg("%s: the context carries STMs: the hyperdual targeter is not on the device path", name);
         r.rc = NYX_HIP_RC_UNSUPPORTED;
         return r;
     }
+    if (frame_swapped) return frame_swap_refusal(name, "its chains are not those of the states it integrates");
     return {};
 }

@@ -79,9 +79,9 @@ __global__ __launch_bounds__(TGT_BLOCK) void nyxtgt_step_kernel(TgtArgs a) {
     __shared__ int seg_st[NYX_HIP_MAX_CHAIN];
     const int tid = threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * TGT_BLOCK + tid;
-    if (tid < a.n_chain) {
+    if (tid < a.chain.n_chain) {
         double r[3], v[3];
-        seg_st[tid] = frm_cheby_pv(a.seg[tid], a.records, ns_to_seconds(a.q.achievement_epoch_ns), true, r, v);
+        seg_st[tid] = frm_cheby_pv(a.chain.seg[tid], a.records, ns_to_seconds(a.q.achievement_epoch_ns), true, r, v);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             seg_rv[tid][c] = r[c];
@@ -97,10 +97,10 @@ __global__ __launch_bounds__(TGT_BLOCK) void nyxtgt_step_kernel(TgtArgs a) {
         bool ephem_bad = false;
 #pragma unroll
         for (int k = 0; k < NYX_HIP_MAX_CHAIN; ++k)
-            if (k < a.n_chain) {
+            if (k < a.chain.n_chain) {
                 ephem_bad = ephem_bad || seg_st[k] != NYX_HIP_OK;
 #pragma unroll
-                for (int c = 0; c < 6; ++c) body[c] = body[c] + a.sign[k] * seg_rv[k][c];
+                for (int c = 0; c < 6; ++c) body[c] = body[c] + a.chain.sign[k] * seg_rv[k][c];
             }
         TgtRun run;
 #pragma unroll
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(TGT_BLOCK) void nyxtgt_step_kernel(TgtArgs a) {
             run.total[c] = a.keep[(int64_t)(TGT_TOTAL + c) * a.cap + i];
         }
         run.prev = a.keep[(int64_t)TGT_PREV * a.cap + i];
-        const bool translate = a.n_chain > 0;
+        const bool translate = a.chain.n_chain > 0;
         const int leg = flag == TGT_RUN_LEG_FAILED ? 1 : 0;
         double err[TGT_MO];
         const int st = tgt_step(a.q, a.need, a.it, ephem_bad, [&](int k, double y[6]) -> int {

@@ -3,8 +3,8 @@
 Host-side definition of what `ShadowModel::compute` (cosmic/eclipse.rs:69-83) computes through anise's
 `Almanac::solar_eclipsing`: the apparent disk of the light source, the apparent disk of every shadow body, the share of the first
 that the second hides, the body with the largest share (strict >, first wins).  The device kernel (csrc/eclipse_kernel.hip) is
-tested against this module, which restates the oracle's `occultation_pct` / `body_position` / `cheby_eval`
-(oracle/nyx_oracle.c) OPERATION FOR OPERATION - sums of three left to right, `norm3` as sqrt(x x + y y + z z), one rounding per
+tested against this module, which restates the oracle's `occultation_pct` (oracle/nyx_oracle.c; `body_position` / `cheby_eval` are
+chains.py's) OPERATION FOR OPERATION - sums of three left to right, `norm3` as sqrt(x x + y y + z z), one rounding per
 operation, asin / acos of the C library element by element - so that it agrees with the oracle bit for bit
 (tests/test_eclipse_host.py).
 
@@ -13,8 +13,8 @@ operation, asin / acos of the C library element by element - so that it agrees w
     d_p  = acos(-(r_ls . r_eb) / (|r_eb| |r_ls|))        is kept, and the degree-valued parameters report what the formula used
     lit (d_p - ls_p > fo_p) 0;  umbra (fo_p > d_p + ls_p) 100;  penumbra: the lens of two disks;  else annular 100 fo_p^2 / ls_p^2
 
-Positions are signed sums of the almanac's Chebyshev segments along a body's chain, in chain order.  An epoch outside a segment
-gives NaN for that sample (the device series ends there).
+Positions are signed sums of the almanac's Chebyshev segments along a body's chain, in chain order (chains.py).  An epoch outside
+a segment gives NaN for that sample (the device series ends there).
 """
 from __future__ import annotations
 
@@ -25,6 +25,7 @@ from typing import List
 
 import numpy as np
 
+from .chains import MAX_CHAIN, body_chain, chain_state, checked_chain, cheby_position  # noqa: F401  (re-exported)
 from .groundtrack import _TO_DEG, _libm, _ns_to_seconds
 
 
@@ -49,7 +50,6 @@ class EclipseParameter(enum.IntEnum):
 PER_BODY = frozenset(p for p in EclipseParameter if p >= EclipseParameter.BodyOccultation)
 DEFAULT_PARAMS = (EclipseParameter.Occultation, EclipseParameter.State)
 MAX_BODIES = 8
-MAX_CHAIN = 4
 
 
 @dataclass
@@ -77,15 +77,6 @@ class ShadowModel:
         return ids.index(int(body.naif_id))
 
 
-def body_chain(naif_id: int, almanac, central):
-    """[(segment, sign), ...] of a body w.r.t. `central` in `almanac`; [] for the central body itself."""
-    if int(naif_id) == int(central.naif_id):
-        return []
-    if naif_id not in almanac.bodies:
-        raise KeyError(f"planetary data of body {naif_id} not loaded")
-    return [(int(s), int(g)) for s, g in almanac.bodies[naif_id]["chain"]]
-
-
 def check_shadow_model(model: ShadowModel, almanac, central) -> None:
     """What `check_ecl_series` (csrc/series_host.h) refuses, on the host: ValueError."""
     if not isinstance(model, ShadowModel):
@@ -93,15 +84,8 @@ def check_shadow_model(model: ShadowModel, almanac, central) -> None:
     if not 1 <= len(model.shadow_bodies) <= MAX_BODIES:
         raise ValueError(f"shadow model: {len(model.shadow_bodies)} shadow bodies, 1 .. {MAX_BODIES} per call")
     for which, frame, least in [("light source", model.light_source, 1)] + [(f"shadow_bodies[{k}]", b, 0) for k, b in enumerate(model.shadow_bodies)]:
-        chain = body_chain(frame.naif_id, almanac, central)
-        if not least <= len(chain) <= MAX_CHAIN:
-            raise ValueError(f"shadow model: the {which} has a chain of {len(chain)} segments, {least} .. {MAX_CHAIN}"
-                             + (" (the light source cannot be the central body)" if least else ""))
-        for seg, sign in chain:
-            if not 0 <= seg < len(almanac.segments):
-                raise ValueError(f"shadow model: the {which} names segment {seg}, not a segment of the almanac")
-            if sign not in (1, -1):
-                raise ValueError(f"shadow model: the {which} has a chain sign {sign}, +1 or -1")
+        checked_chain(body_chain(frame.naif_id, almanac, central), almanac, f"shadow model: the {which}", least,
+                      " (the light source cannot be the central body)" if least else "")
         radius = float(frame.mean_equatorial_radius_km)
         if not (math.isfinite(radius) and radius > 0.0):
             raise ValueError(f"shadow model: the {which} needs a finite mean radius > 0")
@@ -118,39 +102,9 @@ def _acos_c(x: float) -> float:
 _asin, _acos = _libm(_asin_c), _libm(_acos_c)
 
 
-def cheby_position(seg, et_s) -> np.ndarray:
-    """`cheby_eval` of oracle/nyx_oracle.c for an array of epochs: [..., 3]; NaN where et lies outside the segment."""
-    et = np.asarray(et_s, dtype=np.float64)
-    rec_all = np.asarray(seg.records, dtype=np.float64)
-    n_rec, nc = rec_all.shape[0], seg.n_coeffs
-    with np.errstate(invalid="ignore"):
-        idx = np.floor((et - float(seg.init_et_s)) / float(seg.interval_s))
-        end = float(seg.init_et_s) + float(seg.interval_s) * float(n_rec)
-        bad = ~(idx >= 0) | (idx > n_rec) | ((idx == n_rec) & (et > end))
-    idx = np.where(bad, 0, np.minimum(np.where(bad, 0, idx), n_rec - 1)).astype(np.int64)
-    rec = rec_all[idx]
-    t = (et - rec[..., 0]) / rec[..., 1]
-    two_t = 2.0 * t
-    out = np.empty(et.shape + (3,))
-    for c in range(3):
-        cf = rec[..., 2 + c * nc:2 + (c + 1) * nc]
-        w0, w1 = np.zeros(et.shape), np.zeros(et.shape)
-        for j in range(nc - 1, 0, -1):
-            w2 = w1
-            w1 = w0
-            w0 = cf[..., j] + (two_t * w1 - w2)
-        out[..., c] = cf[..., 0] + (t * w0 - w1)
-    out[bad] = np.nan
-    return out
-
-
 def body_position(naif_id: int, epoch_ns, almanac, central) -> np.ndarray:
     """`body_position` of the oracle: the signed sum over the chain, in chain order, from zero."""
-    et = _ns_to_seconds(epoch_ns)
-    p = np.zeros(et.shape + (3,))
-    for seg, sign in body_chain(naif_id, almanac, central):
-        p = p + float(sign) * cheby_position(almanac.segments[seg], et)
-    return p
+    return chain_state(body_chain(naif_id, almanac, central), _ns_to_seconds(epoch_ns), almanac, with_v=False)[0]
 
 
 def _norm3(v):

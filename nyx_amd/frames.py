@@ -4,8 +4,8 @@ Host-side definition of what `Traj::to_frame` (md/trajectory/sc_traj.rs:88-129: 
 for every state) computes between two frames of ONE orientation - a translation by the state of one centre relative to the other -
 followed by a parameter evaluation about the new centre: the orbit-derived `StateParameter`s with the target's mu, and the B-plane of
 the approach (cosmic/bplane.rs:55-136, 195-219).  The device kernel (csrc/frame_kernel.hip) is tested against this module, which
-restates the oracle's `cheby_eval_pv` / `frame_shift` (oracle/nyx_oracle.c:117-161) OPERATION FOR OPERATION - one rounding per
-operation, sums along the chain in chain order - so that positions agree with the oracle bit for bit (tests/test_frame_host.py).
+restates the oracle's `frame_shift` (oracle/nyx_oracle.c:143-161; the chain and `cheby_eval_pv` are chains.py's) OPERATION FOR
+OPERATION - one rounding per operation - so that positions agree with the oracle bit for bit (tests/test_frame_host.py).
 
     body   = sum_k sign_k * (p_k, pv_k)                  the target's chain, in chain order, from zero
     rv'    = rv - body                                   no aberration, no light time (the reference passes None too)
@@ -24,7 +24,7 @@ import math
 
 import numpy as np
 
-from .eclipse import body_chain
+from .chains import MAX_CHAIN, body_chain, chain_state, checked_chain, cheby_state  # noqa: F401  (re-exported)
 from .groundtrack import _TO_DEG, _libm, _ns_to_seconds
 from .params import StateParameter, bplane_of_state, state_value
 
@@ -60,7 +60,6 @@ class FrameParameter(enum.IntEnum):
 
 
 HYPERBOLA_ONLY = frozenset({FrameParameter.BdotT, FrameParameter.BdotR, FrameParameter.BAngle, FrameParameter.BMagnitude, FrameParameter.VInfinity})
-MAX_CHAIN = 4
 _atan2 = _libm(math.atan2, 2)
 
 
@@ -80,62 +79,17 @@ def frame_param(param) -> FrameParameter:
 def check_target(target, almanac, central):
     """The chain of `target` w.r.t. `central` in `almanac`, refusing what `check_frame_series` (csrc/series_host.h) refuses: KeyError
     from `eclipse.body_chain` for a body the almanac cannot reach, ValueError for the rest."""
-    chain = body_chain(target.naif_id, almanac, central)
-    if len(chain) > MAX_CHAIN:
-        raise ValueError(f"encounter target: a chain of {len(chain)} segments, 0 .. {MAX_CHAIN}")
-    for seg, sign in chain:
-        if not 0 <= seg < len(almanac.segments):
-            raise ValueError(f"encounter target: segment {seg} is not a segment of the almanac")
-        if sign not in (1, -1):
-            raise ValueError(f"encounter target: chain sign {sign}, +1 or -1")
+    chain = checked_chain(body_chain(target.naif_id, almanac, central), almanac, "encounter target: the frame")
     mu = float(target.mu_km3_s2)
     if not (math.isfinite(mu) and mu > 0.0):
         raise ValueError("encounter target: the frame needs a finite mu > 0")
     return chain
 
 
-def cheby_state(seg, et_s):
-    """`cheby_eval_pv` of oracle/nyx_oracle.c for an array of epochs: (r[..., 3], v[..., 3]); NaN where et lies outside the segment.
-    The value exactly as `eclipse.cheby_position`, the derivative by the companion recurrence, scaled by 1 / radius."""
-    et = np.asarray(et_s, dtype=np.float64)
-    rec_all = np.asarray(seg.records, dtype=np.float64)
-    n_rec, nc = rec_all.shape[0], seg.n_coeffs
-    with np.errstate(invalid="ignore"):
-        idx = np.floor((et - float(seg.init_et_s)) / float(seg.interval_s))
-        end = float(seg.init_et_s) + float(seg.interval_s) * float(n_rec)
-        bad = ~(idx >= 0) | (idx > n_rec) | ((idx == n_rec) & (et > end))
-    idx = np.where(bad, 0, np.minimum(np.where(bad, 0, idx), n_rec - 1)).astype(np.int64)   # (idx == n_rec: exactly the end of coverage)
-    rec = rec_all[idx]
-    t = (et - rec[..., 0]) / rec[..., 1]
-    two_t = 2.0 * t
-    r, v = np.empty(et.shape + (3,)), np.empty(et.shape + (3,))
-    for c in range(3):
-        cf = rec[..., 2 + c * nc:2 + (c + 1) * nc]
-        w0, w1, d0, d1 = np.zeros(et.shape), np.zeros(et.shape), np.zeros(et.shape), np.zeros(et.shape)
-        for j in range(nc - 1, 0, -1):
-            w2 = w1
-            w1 = w0
-            w0 = cf[..., j] + (two_t * w1 - w2)
-            d2 = d1
-            d1 = d0
-            d0 = (2.0 * w1 + two_t * d1) - d2
-        r[..., c] = cf[..., 0] + (t * w0 - w1)
-        v[..., c] = ((w0 + t * d0) - d1) / rec[..., 1]
-    r[bad] = np.nan
-    v[bad] = np.nan
-    return r, v
-
-
 def body_state(naif_id: int, epoch_ns, almanac, central):
     """`frame_shift` of the oracle without the state: (r[..., 3], v[..., 3]) of a body w.r.t. `central`, the signed sum over its
     chain, in chain order, from zero."""
-    et = _ns_to_seconds(epoch_ns)
-    r, v = np.zeros(et.shape + (3,)), np.zeros(et.shape + (3,))
-    for seg, sign in body_chain(naif_id, almanac, central):
-        p, pv = cheby_state(almanac.segments[seg], et)
-        r = r + float(sign) * p
-        v = v + float(sign) * pv
-    return r, v
+    return chain_state(body_chain(naif_id, almanac, central), _ns_to_seconds(epoch_ns), almanac)[:2]
 
 
 def to_frame(rv, epoch_ns, target, almanac, central) -> np.ndarray:

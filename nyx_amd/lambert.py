@@ -42,8 +42,8 @@ from typing import Optional
 
 import numpy as np
 
-from .eclipse import body_chain
-from .frames import MAX_CHAIN, cheby_state
+from . import chains
+from .chains import MAX_CHAIN, body_chain, cheby_state  # noqa: F401  (re-exported)
 from .groundtrack import _TO_DEG, _ns_to_seconds
 
 
@@ -492,27 +492,13 @@ def batch_definition(rv1, rv2, tof_s, mu: float, way=TransferKind.Auto, n_revs: 
 
 
 def check_chain(what: str, naif_id: int, almanac, central):
-    chain = body_chain(naif_id, almanac, central)
-    if len(chain) > MAX_CHAIN:
-        raise ValueError(f"lambert_grid: the {what} has a chain of {len(chain)} segments, 0 .. {MAX_CHAIN}")
-    for seg, sign in chain:
-        if not 0 <= seg < len(almanac.segments):
-            raise ValueError(f"lambert_grid: the {what} names segment {seg}, not a segment of the almanac")
-        if sign not in (1, -1):
-            raise ValueError(f"lambert_grid: the {what} has a chain sign {sign}, +1 or -1")
-    return chain
+    return chains.checked_chain(body_chain(naif_id, almanac, central), almanac, f"lambert_grid: the {what}")
 
 
 def chain_state(chain, et_s, almanac):
     """The signed sum of a chain at the epochs `et_s` (seconds), in chain order, from zero: (rv[..., 6], inside[...])."""
-    et = np.asarray(et_s, dtype=np.float64)
-    rv = np.zeros(et.shape + (6,))
-    inside = np.ones(et.shape, dtype=bool)
-    for seg, sign in chain:
-        p, pv = cheby_state(almanac.segments[seg], et)
-        inside &= ~np.isnan(p[..., 0])
-        rv = rv + float(sign) * np.concatenate([p, pv], axis=-1)
-    return rv, inside
+    r, v, inside = chains.chain_state(chain, et_s, almanac)
+    return np.concatenate([r, v], axis=-1), inside
 
 
 def grid_epochs(n_dep, n_arr, dep0_ns, dep_step_ns, arr0_ns=None, arr_step_ns=None, tof0_ns=None, tof_step_ns=None):

@@ -30,7 +30,8 @@ import math
 
 import numpy as np
 
-from .eclipse import body_chain, body_position
+from .chains import MAX_CHAIN, body_chain, checked_chain  # noqa: F401  (re-exported)
+from .eclipse import body_position
 
 
 class LinkParameter(enum.IntEnum):
@@ -54,7 +55,6 @@ class LinkParameter(enum.IntEnum):
 PER_BODY = frozenset((LinkParameter.BodyClearance, LinkParameter.BodyObstructs))
 DEFAULT_PARAMS = (LinkParameter.Range, LinkParameter.RangeRate, LinkParameter.Visible)
 MAX_BODIES = 8
-MAX_CHAIN = 4
 
 
 def default_bodies(central) -> list:
@@ -90,14 +90,7 @@ def check_link_bodies(bodies, almanac, central) -> None:
     if len(bodies) > MAX_BODIES:
         raise ValueError(f"link: {len(bodies)} bodies, 0 .. {MAX_BODIES} per call")
     for k, frame in enumerate(bodies):
-        chain = link_chain(frame, almanac, central)
-        if len(chain) > MAX_CHAIN:
-            raise ValueError(f"link: bodies[{k}] has a chain of {len(chain)} segments, 0 .. {MAX_CHAIN}")
-        for seg, sign in chain:
-            if not 0 <= seg < len(almanac.segments):
-                raise ValueError(f"link: bodies[{k}] names segment {seg}, not a segment of the almanac")
-            if sign not in (1, -1):
-                raise ValueError(f"link: bodies[{k}] has a chain sign {sign}, +1 or -1")
+        checked_chain(link_chain(frame, almanac, central), almanac, f"link: bodies[{k}]")
         radius = float(frame.mean_equatorial_radius_km)
         if not (math.isfinite(radius) and radius > 0.0):
             raise ValueError(f"link: bodies[{k}] needs a finite mean radius > 0")

@@ -35,7 +35,8 @@ from .stations import DEFAULT_PARAMS as AER_DEFAULT, AerParameter, check_station
 from . import frames
 from . import lambert
 from . import targeter
-from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, body_chain, check_shadow_model
+from .chains import body_chain, fill_chain
+from .eclipse import DEFAULT_PARAMS as ECLIPSE_DEFAULT, PER_BODY as ECLIPSE_PER_BODY, EclipseParameter, check_shadow_model
 from . import links
 from . import stats as series_statistics
 
@@ -927,10 +928,8 @@ class GpuContext:
             raise ValueError("traj_eclipse: at least one parameter")
 
         def fill_body(dst, frame):
-            chain = body_chain(frame.naif_id, almanac, central)
-            dst.n_chain, dst.mean_radius_km = len(chain), float(frame.mean_equatorial_radius_km)
-            for k, (seg, sign) in enumerate(chain):
-                dst.chain_segment[k], dst.chain_sign[k] = seg, sign
+            fill_chain(dst, body_chain(frame.naif_id, almanac, central))
+            dst.mean_radius_km = float(frame.mean_equatorial_radius_km)
 
         def fill(q):
             fill_body(q.light, model.light_source)
@@ -966,9 +965,8 @@ class GpuContext:
             raise ValueError("traj_frame_values: at least one parameter")
 
         def fill(q):
-            q.n_chain, q.mu_km3_s2 = len(chain), float(target.mu_km3_s2)
-            for k, (seg, sign) in enumerate(chain):
-                q.chain_segment[k], q.chain_sign[k] = seg, sign
+            fill_chain(q, chain)
+            q.mu_km3_s2 = float(target.mu_km3_s2)
 
         return _param_series("traj_frame_values", fn, self._h, _abi.FrameQuery, _abi.MAX_FRAME_PARAMS, fill, traj, codes, step_ns, start_ns, end_ns,
                              capacity, stats=stats)
@@ -1037,9 +1035,7 @@ class GpuContext:
             q = _abi.LambertGridQuery()
             self._lambert_query(q.solve, [int(p) for p in group], way, n_revs, high_path, tol, max_iter)
             for dst, chain in zip((q.dep, q.arr, q.centre), chains):
-                dst.n_chain = len(chain)
-                for k, (seg, sign) in enumerate(chain):
-                    dst.chain_segment[k], dst.chain_sign[k] = seg, sign
+                fill_chain(dst, chain)
             q.has_tof, q.n_dep, q.n_arr, q.dep0_ns, q.dep_step_ns = int(tof0_ns is not None), n_dep, n_arr, int(dep0_ns), int(dep_step_ns)
             if tof0_ns is not None:
                 q.tof0_ns, q.tof_step_ns = int(tof0_ns), int(tof_step_ns)
@@ -1072,10 +1068,8 @@ class GpuContext:
             almanac, central = self.compiled.almanac, self.compiled.central
             if almanac is None:
                 raise ValueError("target: the context was not compiled from an almanac (CompiledConfig.almanac)")
-            chain = frames.check_target(objective_frame, almanac, central)
-            q.n_chain, q.mu_km3_s2 = len(chain), float(objective_frame.mu_km3_s2)
-            for k, (seg, sign) in enumerate(chain):
-                q.chain_segment[k], q.chain_sign[k] = seg, sign
+            fill_chain(q, frames.check_target(objective_frame, almanac, central))
+            q.mu_km3_s2 = float(objective_frame.mu_km3_s2)
         q.correction_epoch_ns, q.achievement_epoch_ns = int(correction_epoch_ns), int(achievement_epoch_ns)
         return q
 
@@ -1139,9 +1133,8 @@ class GpuContext:
         def fill(q):
             q.n_bodies = len(bodies)
             for b, (frame, chain) in enumerate(zip(bodies, chains)):
-                q.bodies[b].n_chain, q.bodies[b].mean_radius_km = len(chain), float(frame.mean_equatorial_radius_km)
-                for k, (seg, sign) in enumerate(chain):
-                    q.bodies[b].chain_segment[k], q.bodies[b].chain_sign[k] = seg, sign
+                fill_chain(q.bodies[b], chain)
+                q.bodies[b].mean_radius_km = float(frame.mean_equatorial_radius_km)
             for k in range(q.n_params):   # (_param_series stored the pairs' codes; the bodies ride in a list of their own)
                 q.param_body[k] = of_body.pop(0)
 

@@ -1,6 +1,6 @@
 // Stand-alone check of the host side of the eclipse report (nyx_amd/csrc/series_host.h: check_ecl_series; nyx_amd/csrc/eclipse_args.h:
 // ecl_param_needs, ecl_needs, ecl_reduce_chains) and of the kernel's own per-sample code compiled FOR THE HOST
-// (nyx_amd/csrc/eclipse_dev.h: ecl_cheby, ecl_occultation) - g++ only, no HIP, no GPU (tests/test_eclipse_host_cxx.py, which builds
+// (nyx_amd/csrc/chain_dev.h: frm_cheby_pv; nyx_amd/csrc/eclipse_dev.h: ecl_occultation) - g++ only, no HIP, no GPU (tests/test_eclipse_host_cxx.py, which builds
 // it with the address and undefined-behaviour sanitizers).
 //   eclipse_host_check INPUT
 // runs check_ecl_series over a table of cases and the chain reduction over hand-made chains, then reads INPUT (text, numbers as
@@ -279,7 +279,7 @@ static void evaluate(const char *path) {
             // the kernel's second pass, step by step: every distinct segment once, then the chains in chain order
             double segpos[ECL_MAX_USEG][3];
             int seg_st[ECL_MAX_USEG];
-            for (int u = 0; u < a.n_useg; ++u) seg_st[u] = ecl_cheby(a.seg[u], records.data(), et, segpos[u]);
+            for (int u = 0; u < a.n_useg; ++u) seg_st[u] = frm_cheby_pv(a.seg[u], records.data(), et, false, segpos[u], nullptr);
             double p_body[1 + NYX_HIP_MAX_ECL_BODIES][3];
             for (int b = 0; b < n_bodies; ++b) {
                 const EclChain &ch = b == 0 ? a.light : a.body[b - 1];

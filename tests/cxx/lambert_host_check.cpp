@@ -169,9 +169,9 @@ static void refusals() {
     DevSeg ctx_seg[kSeg];
     std::memset(ctx_seg, 0, sizeof ctx_seg);
     for (int i = 0; i < kSeg; ++i) ctx_seg[i].offset = 100 * i;
-    const LmbChain ch = lmb_chain(g.arr, ctx_seg);
+    const ResolvedChain ch = resolve_chain(chain_view(g.arr), ctx_seg);
     CHECK(ch.n_chain == 3 && ch.seg[0].offset == 400 && ch.seg[1].offset == 100 && ch.seg[2].offset == 0 && ch.sign[0] == 1.0 && ch.sign[1] == -1.0 && ch.sign[3] == 0.0,
-          "lmb_chain");
+          "resolve_chain");
 }
 
 struct Seg { double init, interval; int n_rec, n_coef; std::vector<double> rec; };
@@ -265,7 +265,8 @@ static void evaluate(const char *path) {
                 records.insert(records.end(), s.rec.begin(), s.rec.end());
             }
         }
-        const LmbChain dep = lmb_chain(chains[0], ctx_seg), arr = lmb_chain(chains[1], ctx_seg), centre = lmb_chain(chains[2], ctx_seg);
+        const ResolvedChain dep = resolve_chain(chain_view(chains[0]), ctx_seg), arr = resolve_chain(chain_view(chains[1]), ctx_seg),
+                            centre = resolve_chain(chain_view(chains[2]), ctx_seg);
         const nyx_hip_lambert_query_t q = good_solver();
         for (int c = 0; c < n_cell; ++c) {
             // a cell of the grid kernel, step by step: the two body states about the centre, then the solve
