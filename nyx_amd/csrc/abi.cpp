@@ -1,5 +1,7 @@
 // abi.cpp — host side of the C-ABI (include/nyx_hip.h): context creation (what it builds: ctx_build.h; the launch policy:
-// launch_plan.h; a batch's arrays in a launch: batch_bind.h; refusals and device blocks: run_host.h, series_host.h; here the device, the uploads), batch staging and kernel launch.
+// launch_plan.h; a batch's arrays in a launch: batch_bind.h; refusals and device blocks: run_host.h, series_host.h, stats_host.h,
+// lambert_args.h, target_args.h on dev_block.h; here the device, the uploads), batch staging, the two host brackets (host_run for the
+// runs, host_block for the flavours whose device arrays are one block) and kernel launch.
 // Compiled with hipcc.
 
 #include <hip/hip_runtime.h>
@@ -923,6 +925,39 @@ struct DevTraj {
     }
 };
 
+// The one or two trajectory batches of a report staged on the device (`ref`: the second batch - RIC's nominal, a link's
+// transmitter - or null: `second` stays empty).
+static int stage_trajs(DevTraj &src, DevTraj &second, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref) {
+    if (int rc = src.alloc(traj->capacity, n)) return rc;
+    if (int rc = src.upload(traj)) return rc;
+    if (!ref) return NYX_HIP_RC_OK;
+    if (int rc = second.alloc(ref->capacity, n_ref)) return rc;
+    return second.upload(ref);
+}
+
+// The host bracket of a host flavour whose device arrays are one block (dev_block.h): under the context's lock the block `b`
+// allocated, the parts `up` copied from their host arrays, `entry(base)` - the device flavour on the block at `base` -, awaited
+// (a failure: "`what` failed") and, `timed`, its kernel time read, the parts `down` copied to their host arrays.  A part of size 0 or
+// with a null host array is skipped.  `timed` false: the targeter, whose timed launches are the propagator's.
+struct HostPart { Part part; const void *host; };
+template <typename T> static T *part_at(char *base, const Part &p) { return (T *)(base + p.at); }
+template <int N, typename Entry>
+static int host_block(nyx_hip_ctx *ctx, const Block<N> &b, const std::vector<HostPart> &up, const std::vector<HostPart> &down, const char *what, bool timed, Entry entry) {
+    CTX_LOCK(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf blk;
+    if (int rc = blk.alloc(b.total)) return rc;
+    char *base = blk.as<char>();
+    for (const HostPart &h : up)
+        if (h.part.bytes && h.host) HIP_TRY(hipMemcpy(base + h.part.at, h.host, h.part.bytes, hipMemcpyHostToDevice));
+    if (int rc = entry(base)) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("%s failed", what); return NYX_HIP_RC_HIP_ERROR; }
+    if (timed) read_kernel_ms(ctx);
+    for (const HostPart &h : down)
+        if (h.part.bytes && h.host) HIP_TRY(hipMemcpy(const_cast<void *>(h.host), base + h.part.at, h.part.bytes, hipMemcpyDeviceToHost));
+    return NYX_HIP_RC_OK;
+}
+
 // The host bracket of a run: what every such entry checks (check_run, run_host.h; an empty batch is done), the batch staged in the
 // context's blocks, `enqueue(sg)` - the entry's launches on the staged views -, awaited and timed, the states and stats fetched, then
 // `collect()` - the entry's own copies back.  `upload_stm` false: predict_until.  `traced`: host_propagate (debug_flags 0x400: stderr).
@@ -1157,7 +1192,7 @@ extern "C" int32_t nyx_hip_reports_sizeof(int32_t which) {
 }
 
 // The host flavour of a report: the trajectories (`ref`: RIC's, or null) staged on the device, the outputs one block laid out by
-// series_block, `entry(src, ref, outputs)` - the device flavour on those - awaited and timed, every non-empty part copied back.
+// series_block, `entry(src, ref, outputs)` - the device flavour on those - through host_block, every non-empty part copied back.
 // `host.epoch0` / `host.moments` may be null: not asked for.  `what` names the kernel in the message of a failed launch.
 struct SeriesOut { double *values; int32_t *len; int64_t *epoch0; double *moments; };
 template <typename Entry>
@@ -1166,26 +1201,22 @@ static int series_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, 
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     DevTraj src, nominal;
-    if (int rc = src.alloc(traj->capacity, n)) return rc;
-    if (int rc = src.upload(traj)) return rc;
-    if (ref) {
-        if (int rc = nominal.alloc(ref->capacity, n_ref)) return rc;
-        if (int rc = nominal.upload(ref)) return rc;
-    }
-    const SeriesBlock b = series_block(n_params, capacity, n, host.moments != nullptr, host.epoch0 != nullptr);
-    DevBuf out;
-    if (int rc = out.alloc(b.total)) return rc;
-    char *base = out.as<char>();
-    const SeriesOut dev = {(double *)(base + b.values_at), (int32_t *)(base + b.len_at), host.epoch0 ? (int64_t *)(base + b.epoch0_at) : nullptr,
-                           host.moments ? (double *)(base + b.moments_at) : nullptr};
-    if (int rc = entry(&src.t, ref ? &nominal.t : nullptr, dev)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("%s kernel failed", what); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    if (b.values) HIP_TRY(hipMemcpy(host.values, dev.values, b.values, hipMemcpyDeviceToHost));
-    if (b.moments) HIP_TRY(hipMemcpy(host.moments, dev.moments, b.moments, hipMemcpyDeviceToHost));
-    if (b.epoch0) HIP_TRY(hipMemcpy(host.epoch0, dev.epoch0, b.epoch0, hipMemcpyDeviceToHost));
-    if (b.len) HIP_TRY(hipMemcpy(host.len, dev.len, b.len, hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    if (int rc = stage_trajs(src, nominal, traj, n, ref, n_ref)) return rc;
+    const auto b = series_block(n_params, capacity, n, host.moments != nullptr, host.epoch0 != nullptr);
+    return host_block(ctx, b, {}, {{b[SB_VALUES], host.values}, {b[SB_MOMENTS], host.moments}, {b[SB_EPOCH0], host.epoch0}, {b[SB_LEN], host.len}}, what, true,
+                      [&](char *base) {
+                          return entry(&src.t, ref ? &nominal.t : nullptr, SeriesOut{part_at<double>(base, b[SB_VALUES]), part_at<int32_t>(base, b[SB_LEN]),
+                                                                                      host.epoch0 ? part_at<int64_t>(base, b[SB_EPOCH0]) : nullptr,
+                                                                                      host.moments ? part_at<double>(base, b[SB_MOMENTS]) : nullptr});
+                      });
+}
+
+// What the launch arguments of every report begin with: all zero, then the members the seven have in common (the family's own are
+// set behind it).
+template <typename Args, typename Query>
+static void series_fill(Args &a, const nyx_hip_traj_t *traj, int64_t n, int64_t capacity, double *values, int32_t *len, const Query *q) {
+    std::memset(&a, 0, sizeof a);
+    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
 }
 
 extern "C" int32_t nyx_hip_traj_values_device(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_values_query_t *q,
@@ -1195,8 +1226,7 @@ extern "C" int32_t nyx_hip_traj_values_device(nyx_hip_ctx *ctx, const nyx_hip_tr
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     ValuesArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    series_fill(a, traj, n, capacity, values, len, q);
     if (!(a.q.mu_km3_s2 > 0.0)) a.q.mu_km3_s2 = ctx->host_cfg.mu_central;
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_values(&a, stream); });
 }
@@ -1205,7 +1235,7 @@ extern "C" int32_t nyx_hip_traj_values(nyx_hip_ctx *ctx, const nyx_hip_traj_t *t
                                        int64_t capacity, double *values, int32_t *len) {
     if (Refusal r = check_values_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "report",
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "report kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_values_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
@@ -1231,8 +1261,7 @@ extern "C" int32_t nyx_hip_traj_ground_track_device(nyx_hip_ctx *ctx, const nyx_
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     GroundTrackArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    series_fill(a, traj, n, capacity, values, len, q);
     return timed_launch(ctx, stream, [&] { return nyx_launch_ground_track(&a, stream); });
 }
 
@@ -1240,7 +1269,7 @@ extern "C" int32_t nyx_hip_traj_ground_track(nyx_hip_ctx *ctx, const nyx_hip_tra
                                              int64_t capacity, double *values, int32_t *len) {
     if (Refusal r = check_gt_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "ground-track",
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "ground-track kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_ground_track_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
@@ -1267,8 +1296,7 @@ extern "C" int32_t nyx_hip_traj_aer_device(nyx_hip_ctx *ctx, const nyx_hip_traj_
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     AerArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    series_fill(a, traj, n, capacity, values, len, q);
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_aer(&a, stream); });
 }
 
@@ -1276,7 +1304,7 @@ extern "C" int32_t nyx_hip_traj_aer(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj
                                     double *values, int32_t *len) {
     if (Refusal r = check_aer_series(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    return series_host(ctx, traj, n, nullptr, 0, (int64_t)q->n_stations * q->n_params, capacity, {values, len, nullptr, nullptr}, "station-view",
+    return series_host(ctx, traj, n, nullptr, 0, (int64_t)q->n_stations * q->n_params, capacity, {values, len, nullptr, nullptr}, "station-view kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_aer_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
@@ -1312,8 +1340,7 @@ extern "C" int32_t nyx_hip_traj_eclipse_device(nyx_hip_ctx *ctx, const nyx_hip_t
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     EclArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    series_fill(a, traj, n, capacity, values, len, q);
     a.records = ctx->d_records;
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_eclipse(&a, ctx->host_cfg.seg, stream); });
 }
@@ -1322,7 +1349,7 @@ extern "C" int32_t nyx_hip_traj_eclipse(nyx_hip_ctx *ctx, const nyx_hip_traj_t *
                                         double *values, int32_t *len) {
     if (Refusal r = check_ecl(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "eclipse",
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "eclipse kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_eclipse_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
@@ -1356,8 +1383,7 @@ extern "C" int32_t nyx_hip_traj_frame_values_device(nyx_hip_ctx *ctx, const nyx_
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     FrmArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.n = n; a.capacity = capacity; a.values = values; a.len = len; a.q = *q;
+    series_fill(a, traj, n, capacity, values, len, q);
     a.records = ctx->d_records;
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_frame_values(&a, ctx->host_cfg.seg, stream); });
 }
@@ -1366,7 +1392,7 @@ extern "C" int32_t nyx_hip_traj_frame_values(nyx_hip_ctx *ctx, const nyx_hip_tra
                                              int64_t capacity, double *values, int32_t *len) {
     if (Refusal r = check_frame(ctx, traj, n, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "encounter",
+    return series_host(ctx, traj, n, nullptr, 0, q->n_params, capacity, {values, len, nullptr, nullptr}, "encounter kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *, const SeriesOut &d) {
                            return nyx_hip_traj_frame_values_device(ctx, src, n, q, capacity, d.values, d.len, nullptr);
                        });
@@ -1403,24 +1429,12 @@ extern "C" int32_t nyx_hip_lambert_batch(nyx_hip_ctx *ctx, const double *rv1, co
                                          const nyx_hip_lambert_query_t *q, double *values, int32_t *status) {
     if (Refusal r = check_lambert_batch(ctx, rv1, rv2, tof_s, n, mu_km3_s2, q, values, status)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    // one device block: rv1 [6][n], rv2 [6][n], tof_s [n], values [n_params][n], status [n]
-    const size_t row = (size_t)n * sizeof(double), in = 13 * row, vals = (size_t)q->n_params * row;
-    DevBuf blk;
-    if (int rc = blk.alloc(in + vals + (size_t)n * sizeof(int32_t))) return rc;
-    char *base = blk.as<char>();
-    HIP_TRY(hipMemcpy(base, rv1, 6 * row, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(base + 6 * row, rv2, 6 * row, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(base + 12 * row, tof_s, row, hipMemcpyHostToDevice));
-    if (int rc = nyx_hip_lambert_batch_device(ctx, (const double *)base, (const double *)(base + 6 * row), (const double *)(base + 12 * row), n, mu_km3_s2, q,
-                                              (double *)(base + in), (int32_t *)(base + in + vals), nullptr))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("lambert batch kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    HIP_TRY(hipMemcpy(values, base + in, vals, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(status, base + in + vals, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    const auto b = lambert_batch_block(n, q->n_params);
+    return host_block(ctx, b, {{b[LBB_RV1], rv1}, {b[LBB_RV2], rv2}, {b[LBB_TOF], tof_s}}, {{b[LBB_VALUES], values}, {b[LBB_STATUS], status}}, "lambert batch kernel", true,
+                      [&](char *base) {
+                          return nyx_hip_lambert_batch_device(ctx, part_at<double>(base, b[LBB_RV1]), part_at<double>(base, b[LBB_RV2]), part_at<double>(base, b[LBB_TOF]), n,
+                                                              mu_km3_s2, q, part_at<double>(base, b[LBB_VALUES]), part_at<int32_t>(base, b[LBB_STATUS]), nullptr);
+                      });
 }
 
 // check_lambert_grid never reads the context; what the query asks of the context - its segments, no integration-frame swap - is
@@ -1444,18 +1458,10 @@ extern "C" int32_t nyx_hip_lambert_grid_device(nyx_hip_ctx *ctx, const nyx_hip_l
 extern "C" int32_t nyx_hip_lambert_grid(nyx_hip_ctx *ctx, const nyx_hip_lambert_grid_query_t *q, double *values, int32_t *status) {
     if (Refusal r = check_lambert(ctx, q, values, status)) return refused(r);
     if (q->n_dep == 0 || q->n_arr == 0) return NYX_HIP_RC_OK;
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t cells = (size_t)q->n_dep * (size_t)q->n_arr, vals = (size_t)q->solve.n_params * cells * sizeof(double);
-    DevBuf blk;
-    if (int rc = blk.alloc(vals + cells * sizeof(int32_t))) return rc;
-    char *base = blk.as<char>();
-    if (int rc = nyx_hip_lambert_grid_device(ctx, q, (double *)base, (int32_t *)(base + vals), nullptr)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("lambert grid kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    HIP_TRY(hipMemcpy(values, base, vals, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(status, base + vals, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    const auto b = lambert_grid_block(q->n_dep, q->n_arr, q->solve.n_params);
+    return host_block(ctx, b, {}, {{b[LGB_VALUES], values}, {b[LGB_STATUS], status}}, "lambert grid kernel", true, [&](char *base) {
+        return nyx_hip_lambert_grid_device(ctx, q, part_at<double>(base, b[LGB_VALUES]), part_at<int32_t>(base, b[LGB_STATUS]), nullptr);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1558,36 +1564,21 @@ extern "C" int32_t nyx_hip_target_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t
     HIP_TRY(hipSetDevice(ctx->device));
     Staged sg;
     if (int rc = stage_batch(ctx, in, sg, false)) return rc;
-    // one device block for the outputs: correction [V][n], errors [O][n], corrected and achieved (epoch and 13 rows of n each), status [n], iterations [n]
-    const size_t row = (size_t)n * sizeof(double), corr = (size_t)q->n_vars * row, errs = (size_t)q->n_objs * row;
-    DevBuf blk;
-    if (int rc = blk.alloc(corr + errs + 28 * row + 2 * (size_t)n * sizeof(int32_t))) return rc;
-    char *base = blk.as<char>();
-    nyx_hip_target_result_t d;
-    std::memset(&d, 0, sizeof d);
-    d.correction = (double *)base;
-    d.achieved_errors = (double *)(base + corr);
-    nyx_hip_states_t *views[2] = {&d.corrected, &d.achieved};
-    for (int s = 0; s < 2; ++s) {
-        char *at = base + corr + errs + (size_t)s * 14 * row;
-        views[s]->n = n;
-        views[s]->epoch_ns = (int64_t *)at;
-        for (int k = 0; k < kStateRows; ++k) views[s]->*kStateRow[k].s = (double *)(at + (size_t)(1 + k) * row);
-    }
-    d.status = (int32_t *)(base + corr + errs + 28 * row);
-    d.iterations = d.status + n;
-    if (int rc = nyx_hip_target_batch_device(ctx, &sg.din, q, &d, nullptr)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("targeter kernels failed"); return NYX_HIP_RC_HIP_ERROR; }
-    HIP_TRY(hipMemcpy(res->correction, d.correction, corr, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(res->achieved_errors, d.achieved_errors, errs, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(res->status, d.status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(res->iterations, d.iterations, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // the outputs: one device block (target_block), every row of it the caller gave an array for copied back
+    const auto b = target_block(n, q->n_vars, q->n_objs);
+    std::vector<HostPart> down = {{b[TGB_CORRECTION], res->correction}, {b[TGB_ERRORS], res->achieved_errors}, {b[TGB_STATUS], res->status}, {b[TGB_ITERATIONS], res->iterations}};
     const nyx_hip_states_t *host[2] = {&res->corrected, &res->achieved};
     for (int s = 0; s < 2; ++s) {
-        HIP_TRY(hipMemcpy(host[s]->epoch_ns, views[s]->epoch_ns, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-        for (int k = 0; k < kStateRows; ++k)
-            if (double *h = host[s]->*kStateRow[k].s) HIP_TRY(hipMemcpy(h, views[s]->*kStateRow[k].s, row, hipMemcpyDeviceToHost));
+        down.push_back({target_row(b, TGB_CORRECTED + s, 0), host[s]->epoch_ns});
+        for (int k = 0; k < kStateRows; ++k) down.push_back({target_row(b, TGB_CORRECTED + s, 1 + k), host[s]->*kStateRow[k].s});
     }
+    nyx_hip_target_result_t d;
+    std::memset(&d, 0, sizeof d);
+    if (int rc = host_block(ctx, b, {}, down, "targeter kernels", false, [&](char *base) {
+            bind_target_result(d, base, b);
+            return nyx_hip_target_batch_device(ctx, &sg.din, q, &d, nullptr);
+        }))
+        return rc;
     res->iterations_run = d.iterations_run;
     return NYX_HIP_RC_OK;
 }
@@ -1613,9 +1604,8 @@ extern "C" int32_t nyx_hip_traj_ric_diff_device(nyx_hip_ctx *ctx, const nyx_hip_
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     RicArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.ref = *ref; a.n = n; a.n_ref = n_ref; a.capacity = capacity;
-    a.values = values; a.len = len; a.epoch0 = epoch0_ns; a.moments = moments; a.q = *q;
+    series_fill(a, traj, n, capacity, values, len, q);
+    a.ref = *ref; a.n_ref = n_ref; a.epoch0 = epoch0_ns; a.moments = moments;
     return timed_launch(ctx, stream, [&] {
         if (n > 0) return nyx_launch_ric_diff(&a, stream);
         // no run: every sample has count 0
@@ -1627,7 +1617,7 @@ extern "C" int32_t nyx_hip_traj_ric_diff(nyx_hip_ctx *ctx, const nyx_hip_traj_t 
                                          const nyx_hip_ric_query_t *q, int64_t capacity, double *values, int32_t *len, int64_t *epoch0_ns,
                                          double *moments) {
     if (Refusal r = check_ric_series(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return refused(r);
-    return series_host(ctx, traj, n, ref, n_ref, 6, capacity, {values, len, epoch0_ns, moments}, "RIC",
+    return series_host(ctx, traj, n, ref, n_ref, 6, capacity, {values, len, epoch0_ns, moments}, "RIC kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *nominal, const SeriesOut &d) {
                            return nyx_hip_traj_ric_diff_device(ctx, src, n, nominal, n_ref, q, capacity, d.values, d.len, d.epoch0, d.moments, nullptr);
                        });
@@ -1663,10 +1653,8 @@ extern "C" int32_t nyx_hip_traj_link_device(nyx_hip_ctx *ctx, const nyx_hip_traj
     hipStream_t stream = (hipStream_t)hip_stream;
     CTX_LOCK(ctx);
     LnkArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.src = *traj; a.ref = *ref; a.n = n; a.n_ref = n_ref; a.capacity = capacity;
-    a.values = values; a.len = len; a.epoch0 = epoch0_ns; a.q = *q;
-    a.records = ctx->d_records;
+    series_fill(a, traj, n, capacity, values, len, q);
+    a.ref = *ref; a.n_ref = n_ref; a.epoch0 = epoch0_ns; a.records = ctx->d_records;
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_link(&a, ctx->host_cfg.seg, stream); });
 }
 
@@ -1674,7 +1662,7 @@ extern "C" int32_t nyx_hip_traj_link(nyx_hip_ctx *ctx, const nyx_hip_traj_t *tra
                                      const nyx_hip_link_query_t *q, int64_t capacity, double *values, int32_t *len, int64_t *epoch0_ns) {
     if (Refusal r = check_link(ctx, traj, n, ref, n_ref, q, capacity, values, len)) return refused(r);
     if (n == 0) return NYX_HIP_RC_OK;
-    return series_host(ctx, traj, n, ref, n_ref, q->n_params, capacity, {values, len, epoch0_ns, nullptr}, "link",
+    return series_host(ctx, traj, n, ref, n_ref, q->n_params, capacity, {values, len, epoch0_ns, nullptr}, "link kernel",
                        [&](const nyx_hip_traj_t *src, const nyx_hip_traj_t *tx, const SeriesOut &d) {
                            return nyx_hip_traj_link_device(ctx, src, n, tx, n_ref, q, capacity, d.values, d.len, d.epoch0, nullptr);
                        });
@@ -1709,90 +1697,66 @@ extern "C" int32_t nyx_hip_series_stats_device(nyx_hip_ctx *ctx, const double *v
 extern "C" int32_t nyx_hip_series_stats(nyx_hip_ctx *ctx, const double *values, const int32_t *len, const int32_t *status, int64_t n_rows,
                                         int64_t capacity, int64_t n, const nyx_hip_stats_query_t *q, double *stats) {
     if (Refusal r = check_series_stats(ctx, values, len, n_rows, capacity, n, q, stats)) return refused(r);
-    CTX_LOCK(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const StatsBlock b = stats_block(n_rows, capacity, n, q->n_probs, status != nullptr);
-    DevBuf blk;
-    if (int rc = blk.alloc(b.total)) return rc;
-    char *base = blk.as<char>();
-    if (b.values) HIP_TRY(hipMemcpy(base + b.values_at, values, b.values, hipMemcpyHostToDevice));
-    if (b.len) HIP_TRY(hipMemcpy(base + b.len_at, len, b.len, hipMemcpyHostToDevice));
-    if (b.status) HIP_TRY(hipMemcpy(base + b.status_at, status, b.status, hipMemcpyHostToDevice));
-    if (int rc = nyx_hip_series_stats_device(ctx, (const double *)(base + b.values_at), (const int32_t *)(base + b.len_at),
-                                             b.status ? (const int32_t *)(base + b.status_at) : nullptr, n_rows, capacity, n, q,
-                                             (double *)(base + b.stats_at), nullptr))
-        return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("statistics kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    HIP_TRY(hipMemcpy(stats, base + b.stats_at, b.stats, hipMemcpyDeviceToHost));
-    return NYX_HIP_RC_OK;
+    const auto b = stats_block(n_rows, capacity, n, q->n_probs, status != nullptr);
+    return host_block(ctx, b, {{b[STB_VALUES], values}, {b[STB_LEN], len}, {b[STB_STATUS], status}}, {{b[STB_STATS], stats}}, "statistics kernel", true, [&](char *base) {
+        return nyx_hip_series_stats_device(ctx, part_at<double>(base, b[STB_VALUES]), part_at<int32_t>(base, b[STB_LEN]),
+                                           status ? part_at<int32_t>(base, b[STB_STATUS]) : nullptr, n_rows, capacity, n, q, part_at<double>(base, b[STB_STATS]), nullptr);
+    });
 }
 
-// the refusals of the report itself, by its own check function (`values` / `len`: any non-null pointers, none is read)
-static Refusal check_kind(const nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
-                          const void *query, int64_t capacity, const double *values, const int32_t *len) {
+// The seven reports by their kind (nyx_hip_series_kind), stated once for the fused entry below.  `launch` false: the refusals of the
+// report itself, by its own check function, and nothing else (`values` / `len`: any non-null pointers, none is read); true: its
+// *_device entry - which begins with that check - on the default stream.
+static int series_by_kind(bool launch, nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
+                          const void *query, int64_t capacity, double *values, int32_t *len, int64_t *epoch0) {
+    auto checked = [](const Refusal &r) { return r ? refused(r) : NYX_HIP_RC_OK; };
+    auto one = [&](auto *q, auto check, auto entry) -> int {   // a report of one batch
+        return launch ? entry(ctx, traj, n, q, capacity, values, len, nullptr) : checked(check(ctx, traj, n, q, capacity, values, len));
+    };
     switch (kind) {
-    case NYX_HIP_SERIES_VALUES: return check_values_series(ctx, traj, n, (const nyx_hip_values_query_t *)query, capacity, values, len);
-    case NYX_HIP_SERIES_GROUND_TRACK: return check_gt_series(ctx, traj, n, (const nyx_hip_gt_query_t *)query, capacity, values, len);
-    case NYX_HIP_SERIES_AER: return check_aer_series(ctx, traj, n, (const nyx_hip_aer_query_t *)query, capacity, values, len);
-    case NYX_HIP_SERIES_ECLIPSE: return check_ecl(ctx, traj, n, (const nyx_hip_ecl_query_t *)query, capacity, values, len);
-    case NYX_HIP_SERIES_FRAME: return check_frame(ctx, traj, n, (const nyx_hip_frame_query_t *)query, capacity, values, len);
-    case NYX_HIP_SERIES_LINK: return check_link(ctx, traj, n, ref, n_ref, (const nyx_hip_link_query_t *)query, capacity, values, len);
-    default: return check_ric_series(ctx, traj, n, ref, n_ref, (const nyx_hip_ric_query_t *)query, capacity, values, len);
+    case NYX_HIP_SERIES_VALUES: return one((const nyx_hip_values_query_t *)query, check_values_series, nyx_hip_traj_values_device);
+    case NYX_HIP_SERIES_GROUND_TRACK: return one((const nyx_hip_gt_query_t *)query, check_gt_series, nyx_hip_traj_ground_track_device);
+    case NYX_HIP_SERIES_AER: return one((const nyx_hip_aer_query_t *)query, check_aer_series, nyx_hip_traj_aer_device);
+    case NYX_HIP_SERIES_ECLIPSE: return one((const nyx_hip_ecl_query_t *)query, check_ecl, nyx_hip_traj_eclipse_device);
+    case NYX_HIP_SERIES_FRAME: return one((const nyx_hip_frame_query_t *)query, check_frame, nyx_hip_traj_frame_values_device);
+    case NYX_HIP_SERIES_LINK:
+        return launch ? nyx_hip_traj_link_device(ctx, traj, n, ref, n_ref, (const nyx_hip_link_query_t *)query, capacity, values, len, epoch0, nullptr)
+                      : checked(check_link(ctx, traj, n, ref, n_ref, (const nyx_hip_link_query_t *)query, capacity, values, len));
+    default:   // NYX_HIP_SERIES_RIC
+        return launch ? nyx_hip_traj_ric_diff_device(ctx, traj, n, ref, n_ref, (const nyx_hip_ric_query_t *)query, capacity, values, len, epoch0, nullptr, nullptr)
+                      : checked(check_ric_series(ctx, traj, n, ref, n_ref, (const nyx_hip_ric_query_t *)query, capacity, values, len));
     }
 }
 
-// the *_device entry of the report, on the default stream
-static int kind_device(nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref, int64_t n_ref,
-                       const void *query, int64_t capacity, double *values, int32_t *len, int64_t *epoch0) {
-    switch (kind) {
-    case NYX_HIP_SERIES_VALUES: return nyx_hip_traj_values_device(ctx, traj, n, (const nyx_hip_values_query_t *)query, capacity, values, len, nullptr);
-    case NYX_HIP_SERIES_GROUND_TRACK: return nyx_hip_traj_ground_track_device(ctx, traj, n, (const nyx_hip_gt_query_t *)query, capacity, values, len, nullptr);
-    case NYX_HIP_SERIES_AER: return nyx_hip_traj_aer_device(ctx, traj, n, (const nyx_hip_aer_query_t *)query, capacity, values, len, nullptr);
-    case NYX_HIP_SERIES_ECLIPSE: return nyx_hip_traj_eclipse_device(ctx, traj, n, (const nyx_hip_ecl_query_t *)query, capacity, values, len, nullptr);
-    case NYX_HIP_SERIES_FRAME: return nyx_hip_traj_frame_values_device(ctx, traj, n, (const nyx_hip_frame_query_t *)query, capacity, values, len, nullptr);
-    case NYX_HIP_SERIES_LINK: return nyx_hip_traj_link_device(ctx, traj, n, ref, n_ref, (const nyx_hip_link_query_t *)query, capacity, values, len, epoch0, nullptr);
-    default: return nyx_hip_traj_ric_diff_device(ctx, traj, n, ref, n_ref, (const nyx_hip_ric_query_t *)query, capacity, values, len, epoch0, nullptr, nullptr);
-    }
-}
-
-// The fused host entry: the trajectories staged as series_host stages them, the report's device entry into a device block, the reducer
-// behind it on the same stream; only the statistics, the lengths and the first epochs come back.
+// The fused host entry: the trajectories staged as series_host stages them (none where there is no run), the report's device entry
+// into the values of a stats_block, the reducer behind it on the same stream; only the statistics, the lengths and - of a report with a
+// second batch - the first epochs come back (those from a device array of their own: the block has no part for them).
 extern "C" int32_t nyx_hip_traj_series_stats(nyx_hip_ctx *ctx, int32_t kind, const nyx_hip_traj_t *traj, int64_t n, const nyx_hip_traj_t *ref,
                                              int64_t n_ref, const void *query, int64_t query_size, int64_t capacity, const int32_t *status,
                                              const nyx_hip_stats_query_t *sq, double *stats, int32_t *len, int64_t *epoch0_ns) {
     if (Refusal r = check_traj_series_stats(ctx, kind, traj, ref, query, query_size, sq, stats, len)) return refused(r);
-    if (Refusal r = check_kind(ctx, kind, traj, n, ref, n_ref, query, capacity, stats, len)) return refused(r);
+    if (int rc = series_by_kind(false, ctx, kind, traj, n, ref, n_ref, query, capacity, stats, len, nullptr)) return rc;
     if (n > INT32_MAX) return refused(bad_arg("traj_series_stats: n must be 0 .. 2^31 - 1"));
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    const int64_t rows = series_kind_rows(kind, query);
-    const StatsBlock b = stats_block(rows, capacity, n, sq->n_probs, status != nullptr);
     DevTraj src, second;
-    DevBuf blk, first;
-    if (n > 0) {
-        if (int rc = src.alloc(traj->capacity, n)) return rc;
-        if (int rc = src.upload(traj)) return rc;
-        if (ref) {
-            if (int rc = second.alloc(ref->capacity, n_ref)) return rc;
-            if (int rc = second.upload(ref)) return rc;
-        }
-    }
-    if (int rc = blk.alloc(b.total)) return rc;
-    char *base = blk.as<char>();
-    double *d_values = (double *)(base + b.values_at), *d_stats = (double *)(base + b.stats_at);
-    int32_t *d_len = (int32_t *)(base + b.len_at), *d_status = b.status ? (int32_t *)(base + b.status_at) : nullptr;
+    if (n > 0)
+        if (int rc = stage_trajs(src, second, traj, n, ref, n_ref)) return rc;
+    const int64_t rows = series_kind_rows(kind, query);
+    const auto b = stats_block(rows, capacity, n, sq->n_probs, status != nullptr);
+    DevBuf first;
     const size_t first_bytes = (ref && epoch0_ns) ? (size_t)n * sizeof(int64_t) : 0;
     if (first_bytes)
         if (int rc = first.alloc(first_bytes)) return rc;
-    if (b.status) HIP_TRY(hipMemcpy(d_status, status, b.status, hipMemcpyHostToDevice));
-    if (n > 0)
-        if (int rc = kind_device(ctx, kind, &src.t, n, ref ? &second.t : nullptr, n_ref, query, capacity, d_values, d_len, first.as<int64_t>())) return rc;
-    if (int rc = nyx_hip_series_stats_device(ctx, d_values, d_len, d_status, rows, capacity, n, sq, d_stats, nullptr)) return rc;
-    if (hipDeviceSynchronize() != hipSuccess) { nyx_set_error("report or statistics kernel failed"); return NYX_HIP_RC_HIP_ERROR; }
-    read_kernel_ms(ctx);
-    HIP_TRY(hipMemcpy(stats, d_stats, b.stats, hipMemcpyDeviceToHost));
-    if (b.len) HIP_TRY(hipMemcpy(len, d_len, b.len, hipMemcpyDeviceToHost));
+    if (int rc = host_block(ctx, b, {{b[STB_STATUS], status}}, {{b[STB_STATS], stats}, {b[STB_LEN], len}}, "report or statistics kernel", true, [&](char *base) -> int {
+            double *d_values = part_at<double>(base, b[STB_VALUES]);
+            int32_t *d_len = part_at<int32_t>(base, b[STB_LEN]);
+            if (n > 0)
+                if (int rc = series_by_kind(true, ctx, kind, &src.t, n, ref ? &second.t : nullptr, n_ref, query, capacity, d_values, d_len, first.as<int64_t>())) return rc;
+            return nyx_hip_series_stats_device(ctx, d_values, d_len, status ? part_at<int32_t>(base, b[STB_STATUS]) : nullptr, rows, capacity, n, sq,
+                                               part_at<double>(base, b[STB_STATS]), nullptr);
+        }))
+        return rc;
     if (first_bytes) HIP_TRY(hipMemcpy(epoch0_ns, first.p, first_bytes, hipMemcpyDeviceToHost));
     return NYX_HIP_RC_OK;
 }

@@ -1,7 +1,7 @@
 // lambert_args.h — launch arguments of the Lambert kernels (lambert_kernel.hip), shared with abi.cpp, and what the two entries of
 // include/nyx_hip_lambert.h refuse before anything is launched (host and device text; no HIP).  The refusals are data (Refusal,
 // refusal.h) and are tested on the CPU (tests/test_lambert_abi.py through the C entries).  The three chains of a grid are
-// ResolvedChains (chain_args.h).
+// ResolvedChains (chain_args.h).  Last, the device blocks of the two host flavours (tests/cxx/lambert_host_check.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -9,6 +9,7 @@
 
 #include "../../include/nyx_hip_lambert.h"
 #include "chain_args.h"   // Refusal, bad_arg, ResolvedChain
+#include "dev_block.h"
 #include "devcfg.h"
 
 struct LmbBatchArgs {
@@ -89,4 +90,17 @@ inline Refusal check_lambert_context(const nyx_hip_lambert_grid_query_t &q, int 
     if (Refusal r = check_chain_context(name, "centre", chain_view(q.centre), n_seg)) return r;
     if (frame_swapped) return frame_swap_refusal(name, "its chains are not those of the states it integrates");   // NYX_HIP_RC_UNSUPPORTED
     return {};
+}
+
+// ---- the device blocks of the two host flavours (Block<N>, dev_block.h).  A batch: rv1 [6][n], rv2 [6][n], tof_s [n], values
+// [n_params][n], status [n]; a grid: values [n_params][n_dep][n_arr], status [n_dep][n_arr]
+enum { LBB_RV1, LBB_RV2, LBB_TOF, LBB_VALUES, LBB_STATUS, LBB_PARTS };
+inline Block<LBB_PARTS> lambert_batch_block(int64_t n, int n_params) {
+    const size_t row = (size_t)n * sizeof(double);
+    return Block<LBB_PARTS>({6 * row, 6 * row, row, (size_t)n_params * row, (size_t)n * sizeof(int32_t)});
+}
+enum { LGB_VALUES, LGB_STATUS, LGB_PARTS };
+inline Block<LGB_PARTS> lambert_grid_block(int64_t n_dep, int64_t n_arr, int n_params) {
+    const size_t cells = (size_t)n_dep * (size_t)n_arr;
+    return Block<LGB_PARTS>({(size_t)n_params * cells * sizeof(double), cells * sizeof(int32_t)});
 }

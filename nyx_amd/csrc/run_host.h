@@ -1,9 +1,10 @@
 // run_host.h - the host side of the entries that run the propagator and of the two older host flavours (host only, no HIP; abi.cpp,
 // tests/cxx/run_host_check.cpp): what they refuse, in the order the checks fire; the device blocks of predict_until, until_event and
-// ensemble_moments; the segments of a covariance-mapping loop.  (Their launch predicates: launch_plan.h, beside pick_quad.)
+// ensemble_moments (Block<N>, dev_block.h); the segments of a covariance-mapping loop.  (Their launch predicates: launch_plan.h, beside pick_quad.)
 #pragma once
 #include <algorithm>
 
+#include "dev_block.h"
 #include "predict_args.h"
 #include "series_host.h"  // Refusal, bad_arg, check_traj, check_traj_eval
 
@@ -71,16 +72,7 @@ inline Refusal check_traj_eval_host(const nyx_hip_ctx *ctx, const nyx_hip_traj_t
     return check_traj_eval(ctx, traj, n, query, n ? m : 0, n ? step_ns : 1, out, status, mode);
 }
 
-// ---- the device blocks: byte offsets and sizes of the parts of ONE allocation, in the order of the block's enum; an absent part
-// has size 0.  Doubles and int64 first (every such part is a multiple of 8 bytes long), the int32 rows last.
-struct Part { size_t at = 0, bytes = 0; };
-template <int N> struct Block {
-    Part part[N];
-    size_t total = 0;
-    explicit Block(const size_t (&bytes)[N]) { for (int k = 0; k < N; ++k) { part[k] = {total, bytes[k]}; total += bytes[k]; } }
-    const Part &operator[](int k) const { return part[k]; }
-};
-
+// ---- the device blocks (Block<N>, dev_block.h)
 // predict_until: the covariances [n][81], the six int64 work rows [n], the deviations [n][9], the history arrays the caller asks for
 // (widths 1, 9, 81, 81, 9 per slot, capacity * n slots; contiguous, behind the deviations: cleared in one piece), status, n_updates [n]
 enum { P_COVAR, P_PREV_EPOCH, P_DUR, P_ACC_N_ACC, P_ACC_N_REJ, P_ACC_N_EVALS, P_INIT_EPOCH, P_SDEV, P_H_EPOCH, P_H_STATE, P_H_STM, P_H_COVAR, P_H_SDEV, P_STATUS, P_N_UPDATES, P_COUNT };

@@ -1,6 +1,6 @@
 // series_host.h - the host side of the sampled-series entries (host only, no HIP; abi.cpp, the launchers of the eight series kernels,
 // tests/cxx/series_host_check.cpp): what traj_at / traj_every and the seven fused reports (values, ground track, station views, eclipses, encounters, RIC, links) refuse, the
-// one output block of a report's host flavour, and the chunks of consecutive samples a launch cuts a span into.
+// one output block of a report's host flavour (a Block<N>, dev_block.h), and the chunks of consecutive samples a launch cuts a span into.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -10,6 +10,7 @@
 
 #include "aer_args.h"
 #include "chain_args.h"   // Refusal, bad_arg (refusal.h), check_chain, check_chain_context, frame_swap_refusal
+#include "dev_block.h"
 #include "eclipse_args.h"
 #include "frame_args.h"
 #include "groundtrack_args.h"
@@ -248,21 +249,11 @@ inline Refusal check_link_context(const nyx_hip_link_query_t &q, int n_seg, bool
 }
 
 // ---- the one output block of a report's host flavour: values[n_params][capacity][n] (station views: one row per station and
-// parameter), then the optional moments
-// [capacity][NYX_HIP_RIC_MOMENTS] and first epochs [n], then len[n].  Offsets and sizes in bytes; an absent part has size 0.
-struct SeriesBlock { size_t values_at, values, moments_at, moments, epoch0_at, epoch0, len_at, len, total; };
-inline SeriesBlock series_block(int64_t n_params, int64_t capacity, int64_t n, bool moments, bool epoch0) {
-    SeriesBlock b;
-    b.values_at = 0;
-    b.values = (size_t)n_params * (size_t)capacity * (size_t)n * sizeof(double);
-    b.moments_at = b.values_at + b.values;
-    b.moments = moments ? (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double) : 0;
-    b.epoch0_at = b.moments_at + b.moments;
-    b.epoch0 = epoch0 ? (size_t)n * sizeof(int64_t) : 0;
-    b.len_at = b.epoch0_at + b.epoch0;
-    b.len = (size_t)n * sizeof(int32_t);
-    b.total = b.len_at + b.len;
-    return b;
+// parameter), then the optional moments [capacity][NYX_HIP_RIC_MOMENTS] and first epochs [n], then len[n] (Block<N>, dev_block.h)
+enum { SB_VALUES, SB_MOMENTS, SB_EPOCH0, SB_LEN, SB_PARTS };
+inline Block<SB_PARTS> series_block(int64_t n_params, int64_t capacity, int64_t n, bool moments, bool epoch0) {
+    return Block<SB_PARTS>({(size_t)n_params * (size_t)capacity * (size_t)n * sizeof(double), moments ? (size_t)capacity * NYX_HIP_RIC_MOMENTS * sizeof(double) : 0,
+                            epoch0 ? (size_t)n * sizeof(int64_t) : 0, (size_t)n * sizeof(int32_t)});
 }
 
 // ---- a span of samples in chunks of consecutive samples, one per grid.y: sixteen a chunk, more where that would take more than

@@ -1,7 +1,8 @@
 // stats_host.h - the host side of the statistics entries (include/nyx_hip_stats.h; host only, no HIP; abi.cpp,
 // tests/cxx/stats_host_check.cpp): what they refuse before anything is launched, as data in the style of series_host.h, the rows and
-// the query size of every kind of report, and the one device block of the host flavours.
+// the query size of every kind of report, and the one device block of the host flavours (a Block<N>, dev_block.h).
 #pragma once
+#include "dev_block.h"
 #include "series_host.h"
 #include "stats_args.h"
 
@@ -75,17 +76,8 @@ inline Refusal check_traj_series_stats(const nyx_hip_ctx *ctx, int32_t kind, con
 }
 
 // ---- the device block of the host flavour: values [n_rows][capacity][n], stats [n_rows][capacity][S], len [n], status [n] (absent: size 0)
-struct StatsBlock { size_t values_at, values, stats_at, stats, len_at, len, status_at, status, total; };
-inline StatsBlock stats_block(int64_t n_rows, int64_t capacity, int64_t n, int n_probs, bool status) {
-    StatsBlock b;
-    b.values_at = 0;
-    b.values = (size_t)n_rows * (size_t)capacity * (size_t)n * sizeof(double);
-    b.stats_at = b.values_at + b.values;
-    b.stats = (size_t)n_rows * (size_t)capacity * (size_t)(NYX_HIP_STAT_FIXED + n_probs) * sizeof(double);
-    b.len_at = b.stats_at + b.stats;
-    b.len = (size_t)n * sizeof(int32_t);
-    b.status_at = b.len_at + b.len;
-    b.status = status ? (size_t)n * sizeof(int32_t) : 0;
-    b.total = b.status_at + b.status;
-    return b;
+enum { STB_VALUES, STB_STATS, STB_LEN, STB_STATUS, STB_PARTS };
+inline Block<STB_PARTS> stats_block(int64_t n_rows, int64_t capacity, int64_t n, int n_probs, bool status) {
+    const size_t cells = (size_t)n_rows * (size_t)capacity, words = (size_t)n * sizeof(int32_t);
+    return Block<STB_PARTS>({cells * (size_t)n * sizeof(double), cells * (size_t)(NYX_HIP_STAT_FIXED + n_probs) * sizeof(double), words, status ? words : 0});
 }

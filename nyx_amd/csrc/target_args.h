@@ -1,13 +1,16 @@
 // target_args.h — launch arguments of the targeter kernels (target_kernel.hip), shared with abi.cpp, and what the two entries of
 // include/nyx_hip_target.h refuse before anything is launched (host and device text; no HIP).  The refusals are data (Refusal,
 // refusal.h) and are tested on the CPU (tests/test_target_abi.py through the C entries, tests/cxx/target_host_check.cpp directly).
+// Last, the device block of the host flavour's outputs and the result bound into it (the same program).
 #pragma once
 #include <stdint.h>
 
 #include <cmath>
 
 #include "../../include/nyx_hip_target.h"
+#include "batch_bind.h"    // kStateRow
 #include "chain_args.h"    // Refusal, bad_arg, ResolvedChain
+#include "dev_block.h"
 #include "devcfg.h"
 #include "frame_args.h"    // frm_param_needs
 
@@ -113,4 +116,30 @@ inline Refusal check_target_context(const nyx_hip_target_query_t &q, int n_seg, 
     }
     if (frame_swapped) return frame_swap_refusal(name, "its chains are not those of the states it integrates");
     return {};
+}
+
+// ---- the device block of the host flavour's outputs (Block<N>, dev_block.h): correction [V][n], errors [O][n], corrected and achieved
+// (one epoch row, then the thirteen double rows of nyx_hip_states_t in header order, of n each), status [n], iterations [n]
+enum { TGB_CORRECTION, TGB_ERRORS, TGB_CORRECTED, TGB_ACHIEVED, TGB_STATUS, TGB_ITERATIONS, TGB_PARTS };
+inline Block<TGB_PARTS> target_block(int64_t n, int n_vars, int n_objs) {
+    const size_t row = (size_t)n * sizeof(double), words = (size_t)n * sizeof(int32_t);
+    return Block<TGB_PARTS>({n_vars * row, n_objs * row, (1 + kStateRows) * row, (1 + kStateRows) * row, words, words});
+}
+// row k of the part TGB_CORRECTED or TGB_ACHIEVED: k = 0 the epochs, k = 1 + r the state row r (kStateRow, batch_bind.h)
+inline Part target_row(const Block<TGB_PARTS> &b, int part, int k) {
+    const size_t row = b[part].bytes / (1 + kStateRows);
+    return {b[part].at + k * row, row};
+}
+// The pointers of `d` into a block at `base` (every row of both states is there, whichever rows the caller wants back).
+inline void bind_target_result(nyx_hip_target_result_t &d, char *base, const Block<TGB_PARTS> &b) {
+    d.correction = (double *)(base + b[TGB_CORRECTION].at);
+    d.achieved_errors = (double *)(base + b[TGB_ERRORS].at);
+    d.status = (int32_t *)(base + b[TGB_STATUS].at);
+    d.iterations = (int32_t *)(base + b[TGB_ITERATIONS].at);
+    nyx_hip_states_t *views[2] = {&d.corrected, &d.achieved};
+    for (int s = 0; s < 2; ++s) {
+        views[s]->n = (int64_t)(b[TGB_STATUS].bytes / sizeof(int32_t));
+        views[s]->epoch_ns = (int64_t *)(base + target_row(b, TGB_CORRECTED + s, 0).at);
+        for (int k = 0; k < kStateRows; ++k) views[s]->*kStateRow[k].s = (double *)(base + target_row(b, TGB_CORRECTED + s, 1 + k).at);
+    }
 }

@@ -27,6 +27,8 @@ static int g_fail = 0;
         }                                                                             \
     } while (0)
 
+#include "block_check.h"
+
 static const int kSeg = 5;   // segments of the pretended context
 
 static nyx_hip_lambert_query_t good_solver() {
@@ -174,6 +176,24 @@ static void refusals() {
           "resolve_chain");
 }
 
+// ---- the device blocks of the two host flavours against what abi.cpp computed inline before the header had them, restated here
+// (block_check.h)
+static void check_block() {
+    for (int64_t n : {0, 1, 63, 65})
+        for (int P : {1, 8}) {
+            const size_t row = (size_t)n * sizeof(double), in = 13 * row, vals = (size_t)P * row;   // nyx_hip_lambert_batch
+            check_parts(lambert_batch_block(n, P), {0, 6 * row, 12 * row, in, in + vals}, {6 * row, 6 * row, row, vals, (size_t)n * sizeof(int32_t)},
+                        in + vals + (size_t)n * sizeof(int32_t), LBB_STATUS, "batch", (long long)n, P, 0);
+        }
+    const int64_t grids[][2] = {{0, 0}, {0, 5}, {1, 1}, {7, 9}, {13, 5}};   // 0, 0, 1, 63 and 65 cells
+    for (const auto &g : grids)
+        for (int P : {1, 8}) {
+            const size_t cells = (size_t)g[0] * (size_t)g[1], vals = (size_t)P * cells * sizeof(double);   // nyx_hip_lambert_grid
+            check_parts(lambert_grid_block(g[0], g[1], P), {0, vals}, {vals, cells * sizeof(int32_t)}, vals + cells * sizeof(int32_t), LGB_STATUS, "grid",
+                        (long long)cells, P, 0);
+        }
+}
+
 struct Seg { double init, interval; int n_rec, n_coef; std::vector<double> rec; };
 struct Prob { nyx_hip_lambert_query_t q; double mu, rv1[6], rv2[6], tof; };
 struct Cell { double et_dep, et_arr, tof, mu; };
@@ -301,6 +321,7 @@ static void evaluate(const char *path) {
 
 int main(int argc, char **argv) {
     refusals();
+    check_block();
     if (argc > 1) evaluate(argv[1]);
     if (g_fail) { std::printf("%d checks failed\n", g_fail); return 1; }
     std::printf("ok\n");

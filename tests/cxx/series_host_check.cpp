@@ -48,20 +48,20 @@ static void check_block() {
             for (int64_t P : {1, 6, 8})
                 for (int moments = 0; moments < 2; ++moments)
                     for (int epoch0 = 0; epoch0 < 2; ++epoch0) {
-                        const SeriesBlock b = series_block(P, capacity, n, moments != 0, epoch0 != 0);
+                        const Block<SB_PARTS> b = series_block(P, capacity, n, moments != 0, epoch0 != 0);
                         const size_t vbytes = (size_t)P * (size_t)capacity * (size_t)n * 8;
                         const size_t mbytes = moments ? (size_t)capacity * 28 * 8 : 0;
                         const size_t ebytes = epoch0 ? (size_t)n * 8 : 0;
                         const long long c[5] = {(long long)n, (long long)capacity, (long long)P, moments, epoch0};
 #define AT "n=%lld capacity=%lld P=%lld moments=%lld epoch0=%lld", c[0], c[1], c[2], c[3], c[4]
-                        CHECK(b.values == vbytes && b.moments == mbytes && b.epoch0 == ebytes && b.len == (size_t)n * 4, AT);
-                        CHECK(b.values_at == 0, AT);
-                        CHECK(b.moments_at == b.values_at + b.values, AT);   // order, and no part overlaps the next
-                        CHECK(b.epoch0_at == b.moments_at + b.moments, AT);
-                        CHECK(b.len_at == b.epoch0_at + b.epoch0, AT);
-                        CHECK(b.total == b.len_at + b.len, AT);
+                        CHECK(b[SB_VALUES].bytes == vbytes && b[SB_MOMENTS].bytes == mbytes && b[SB_EPOCH0].bytes == ebytes && b[SB_LEN].bytes == (size_t)n * 4, AT);
+                        CHECK(b[SB_VALUES].at == 0, AT);
+                        CHECK(b[SB_MOMENTS].at == b[SB_VALUES].at + b[SB_VALUES].bytes, AT);   // order, and no part overlaps the next
+                        CHECK(b[SB_EPOCH0].at == b[SB_MOMENTS].at + b[SB_MOMENTS].bytes, AT);
+                        CHECK(b[SB_LEN].at == b[SB_EPOCH0].at + b[SB_EPOCH0].bytes, AT);
+                        CHECK(b.total == b[SB_LEN].at + b[SB_LEN].bytes, AT);
                         CHECK(b.total == vbytes + mbytes + ebytes + (size_t)n * sizeof(int32_t), AT);
-                        CHECK(b.values_at % 8 == 0 && b.moments_at % 8 == 0 && b.epoch0_at % 8 == 0 && b.len_at % 4 == 0, AT);
+                        CHECK(b[SB_VALUES].at % 8 == 0 && b[SB_MOMENTS].at % 8 == 0 && b[SB_EPOCH0].at % 8 == 0 && b[SB_LEN].at % 4 == 0, AT);
 #undef AT
                     }
 }

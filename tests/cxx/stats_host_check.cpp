@@ -137,7 +137,9 @@ int main(int argc, char **argv) {
         if (!series_kind(kind, &kd)) return 1;
         std::printf("kind %d %lld %d %s\n", kind, (long long)kd.query_size, (int)kd.with_ref, kd.name);
     }
-    const StatsBlock sb = stats_block(8, 91, 10000, 3, true);
-    std::printf("block %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sb.values_at, sb.values, sb.stats_at, sb.stats, sb.len_at, sb.len, sb.status_at, sb.status, sb.total);
+    const Block<STB_PARTS> sb = stats_block(8, 91, 10000, 3, true);
+    std::printf("block");
+    for (int k : {STB_VALUES, STB_STATS, STB_LEN, STB_STATUS}) std::printf(" %zu %zu", sb[k].at, sb[k].bytes);
+    std::printf(" %zu\n", sb.total);
     return 0;
 }

@@ -27,6 +27,8 @@ static int g_fail = 0;
         }                                                                             \
     } while (0)
 
+#include "block_check.h"
+
 static nyx_hip_target_query_t good_query() {
     nyx_hip_target_query_t q;
     std::memset(&q, 0, sizeof q);
@@ -128,6 +130,38 @@ static void refusal_table() {
     CHECK(tgt_needs(q) == (frm_param_needs(NYX_HIP_SP_ECCENTRICITY) | frm_param_needs(NYX_HIP_SP_SEMI_MAJOR_AXIS)), "the needs of the objectives");
 }
 
+// ---- the device block of the host flavour's outputs against what nyx_hip_target_batch computed inline before the header had it,
+// restated here (block_check.h), and the result bound into it against that entry's loop over the two states
+static void check_block() {
+    const int shapes[][2] = {{1, 1}, {3, 2}, {6, 6}};
+    for (int64_t n : {0, 1, 63, 65})
+        for (const auto &vo : shapes) {
+            const int V = vo[0], O = vo[1];
+            const size_t row = (size_t)n * sizeof(double), corr = (size_t)V * row, errs = (size_t)O * row, words = (size_t)n * sizeof(int32_t);
+            const Block<TGB_PARTS> b = target_block(n, V, O);
+            check_parts(b, {0, corr, corr + errs, corr + errs + 14 * row, corr + errs + 28 * row, corr + errs + 28 * row + words}, {corr, errs, 14 * row, 14 * row, words, words},
+                        corr + errs + 28 * row + 2 * (size_t)n * sizeof(int32_t), TGB_STATUS, "target", (long long)n, V, O);
+            std::vector<char> mem(b.total + 8);
+            char *base = mem.data();
+            nyx_hip_target_result_t d;
+            std::memset(&d, 0, sizeof d);
+            bind_target_result(d, base, b);
+            CHECK(d.correction == (double *)base && d.achieved_errors == (double *)(base + corr), "target n=%lld (%d, %d): correction, errors", (long long)n, V, O);
+            CHECK(d.status == (int32_t *)(base + corr + errs + 28 * row) && d.iterations == d.status + n, "target n=%lld (%d, %d): status, iterations", (long long)n, V, O);
+            const nyx_hip_states_t *views[2] = {&d.corrected, &d.achieved};
+            for (int s = 0; s < 2; ++s) {
+                char *at = base + corr + errs + (size_t)s * 14 * row;
+                CHECK(views[s]->n == n && views[s]->epoch_ns == (int64_t *)at, "target n=%lld (%d, %d) state %d: n, epochs", (long long)n, V, O, s);
+                for (int k = 0; k < kStateRows; ++k) {
+                    CHECK(views[s]->*kStateRow[k].s == (double *)(at + (size_t)(1 + k) * row), "target n=%lld (%d, %d) state %d: row %d", (long long)n, V, O, s, k);
+                    const Part p = target_row(b, TGB_CORRECTED + s, 1 + k);
+                    CHECK(p.at == (size_t)(at - base) + (size_t)(1 + k) * row && p.bytes == row, "target n=%lld (%d, %d) state %d: part of row %d", (long long)n, V, O, s, k);
+                }
+                CHECK(views[s]->step_ns == nullptr && views[s]->stm == nullptr, "target n=%lld (%d, %d) state %d: nothing else is bound", (long long)n, V, O, s);
+            }
+        }
+}
+
 static double rd(FILE *f) {
     char tok[64];
     if (std::fscanf(f, "%63s", tok) != 1) { std::printf("FAIL short input\n"); std::exit(2); }
@@ -215,7 +249,7 @@ static void run_cases(const char *path) {
 
 int main(int argc, char **argv) {
     if (argc > 1) run_cases(argv[1]);
-    else refusal_table();
+    else { refusal_table(); check_block(); }
     if (g_fail) { std::printf("%d checks failed\n", g_fail); return 1; }
     std::printf("ok\n");
     return 0;
