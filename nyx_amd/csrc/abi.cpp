@@ -1,7 +1,7 @@
 // abi.cpp — host side of the C-ABI (include/nyx_hip.h): context creation (what it builds: ctx_build.h; the launch policy:
 // launch_plan.h; a batch's arrays in a launch: batch_bind.h; refusals and device blocks: run_host.h, series_host.h, stats_host.h,
-// lambert_args.h, target_args.h on dev_block.h; here the device, the uploads), batch staging, the two host brackets (host_run for the
-// runs, host_block for the flavours whose device arrays are one block) and kernel launch.
+// lambert_args.h, target_args.h on dev_block.h; the context's memory: ctx_mem.h; here the device, the uploads), batch staging, the two
+// host brackets (host_run for the runs, host_block for the flavours whose device arrays are one block) and kernel launch.
 // Compiled with hipcc.
 
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "../../include/nyx_hip.h"
 #include "batch_bind.h"
 #include "ctx_build.h"
+#include "ctx_mem.h"
 #include "devcfg.h"
 #include "launch_plan.h"
 #include "predict_args.h"
@@ -98,56 +99,66 @@ static int refused(const Refusal &r) {
         }                                                                                  \
     } while (0)
 
-struct DevBuf {  // RAII device allocation
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) == hipSuccess) return NYX_HIP_RC_OK;
-        p = nullptr;
-        nyx_set_error("hipMalloc of %zu bytes failed", bytes);
-        return NYX_HIP_RC_HIP_ERROR;
-    }
-    template <typename T> T *as() const { return (T *)p; }
+// Where the owners of ctx_mem.h get their memory: the device, and pinned host memory (a batch's mirror).  The codes are hipError_t.
+struct DeviceMem {
+    static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void release(void *p) { (void)hipFree(p); }
+    static int zero(void *p, size_t bytes) { return (int)hipMemset(p, 0, bytes); }
 };
+struct PinnedMem {
+    static int alloc(void **p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void release(void *p) { (void)hipHostFree(p); }
+    static int zero(void *p, size_t bytes) { std::memset(p, 0, bytes); return 0; }
+};
+typedef Owned<DeviceMem> DevBuf;
+static int nothing_in_flight() { return 0; }
+
+// A device allocation of an entry's own, freed when the entry returns.
+static int dev_alloc(DevBuf &b, size_t bytes) {
+    if (b.ensure((int64_t)std::max<size_t>(bytes, 8), nothing_in_flight, cap_exact, PerElement{1}) == 0) return NYX_HIP_RC_OK;
+    nyx_set_error("hipMalloc of %zu bytes failed", bytes);
+    return NYX_HIP_RC_HIP_ERROR;
+}
 
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
 
-struct DevArrays {  // one SoA batch resident on the device: ONE device block, ONE pinned host mirror => one copy each way
-    int64_t cap = 0;
-    char *dblock = nullptr, *hblock = nullptr;
-    size_t bytes = 0;
+struct DevArrays {  // one SoA batch resident on the device: ONE device block (arrays_block), ONE pinned host mirror => one copy each way
+    DevBuf dev;
+    Owned<PinnedMem> mirror;
+    DevBuf stm_buf;  // [stm_buf.cap][81], allocated on first STM use
+    size_t bytes = 0, state_bytes = 0;  // of the block; of its part a staged batch uploads
+    // views into `dev`
     int64_t *epoch = nullptr, *step = nullptr;
     double *f[13] = {nullptr};
-    double *stm = nullptr;  // [cap][81], allocated on first STM use
-    int64_t stm_cap = 0;
     int64_t *last_step = nullptr, *n_acc = nullptr, *n_rej = nullptr, *n_evals = nullptr;
     double *last_error = nullptr;
     int32_t *status = nullptr, *last_attempts = nullptr;
-    template <typename T> T *host(T *dev) const { return (T *)(hblock + ((char *)dev - dblock)); }
+    double *stm() const { return stm_buf.as<double>(); }
+    template <typename T> T *host(T *d) const { return (T *)(mirror.as<char>() + ((char *)d - dev.as<char>())); }
 };
 
+// Every block of device memory a context holds is an owner (ctx_mem.h) and goes with the context; the blocks that follow a batch grow
+// by the owner's one rule (grow(), below).  The one exception is the mailbox block, borrowed from a pool.
 struct nyx_hip_ctx {
     int device = 0;
     nyx_hip_tuning_t tune = NYX_HIP_TUNING_DEFAULT;  // config.tuning, resolved (see resolve_tuning)
     DevCfg host_cfg;
-    DevCfg *d_cfg = nullptr;
+    DevBuf d_cfg;
     // opts.integration_frame: the states of a batch are centred on another body (its chain w.r.t. the integration centre)
     int swap_n_chain = 0;
     int32_t swap_seg[4] = {0, 0, 0, 0};
     double swap_sign[4] = {0.0, 0.0, 0.0, 0.0};
-    double *d_mom = nullptr;   // scratch of the ensemble-moments reduction: [MOM_BLOCKS][MOM_N] block sums, then MOM_N results (host flavour)
-    double *d_stm_hist = nullptr;  // NYX_HIP_FLAG_STM_TEXTBOOK: [16][12][stm_hist_cap] stage matrices of the attempt in flight (DevBatch.stm_hist)
-    int64_t stm_hist_cap = 0;
-    double *d_swap = nullptr;  // six rows of swap_cap doubles: the translated copy of a batch's Cartesian state
-    int64_t swap_cap = 0;
+    DevBuf d_mom;       // scratch of the ensemble-moments reduction: [MOM_BLOCKS][MOM_N] block sums, then MOM_N results (host flavour)
+    DevBuf d_stm_hist;  // NYX_HIP_FLAG_STM_TEXTBOOK: [16][12][cap] stage matrices of the attempt in flight (DevBatch.stm_hist)
+    DevBuf d_swap;      // seven rows of `cap` doubles: the translated copy of a batch's Cartesian state, the forward shift's status words
     int ed_reuse_fit = 0;  // fields of stage-0 epoch data an unchained pipelined loop may carry between attempts (LDS room)
-    HarmEntry *d_htab = nullptr;
-    HarmEntry *d_htab2 = nullptr;  // second gravity field
-    int terms2 = 0;                // its table rows
-    ColHdr *d_cols2 = nullptr;
-    double *d_hyb = nullptr;  // the same table in the hybrid-feed layout (devcfg.h HYB_*)
+    DevBuf d_htab;
+    DevBuf d_htab2;  // second gravity field
+    int terms2 = 0;  // its table rows
+    DevBuf d_cols2;
+    DevBuf d_hyb;  // the same table in the hybrid-feed layout (devcfg.h HYB_*)
     // Run streams (DevCfg.rs_*): the table once more per column schedule - [0] SOLO, [1] PRIMARY, [2] the helpers' - with every RANGE of
     // a wave starting a sixteen-row group of its own.  Rebuilt when a schedule changes (launch() sets rs_dirty), uploaded by
     // launch() before a launch that streams the table.
@@ -155,12 +166,10 @@ struct nyx_hip_ctx {
     std::vector<ColHdr> h_cols;
     std::vector<double> h_rs[3];   // (kept: the asynchronous upload reads them)
     std::vector<ColHdr> h_rs_cols[3];
-    double *d_rs[3] = {nullptr, nullptr, nullptr};
-    size_t rs_cap[3] = {0, 0, 0};
-    ColHdr *d_rs_cols[3] = {nullptr, nullptr, nullptr};
+    DevBuf d_rs[3], d_rs_cols[3];
     bool rs_dirty = true;
-    ColHdr *d_cols = nullptr;
-    double *d_records = nullptr;
+    DevBuf d_cols;
+    DevBuf d_records;
     std::vector<int32_t> col_len;  // rows per column (index = c)
     int n_waves = 1;
     int forced_waves = 0;
@@ -175,10 +184,9 @@ struct nyx_hip_ctx {
     double role_handicap[3] = {0.0, 0.0, 0.0};  // integrator, almanac, perturbations (harmonics-term units)
     DevArrays in, out;
     DevArrays work;            // the targeter's work block: (1 + V) n rows propagated in place (nyx_hip_target_batch), grown on demand
-    char *d_tgt = nullptr;     // what its runs keep between the rounds: [TGT_KEEP_ROWS][tgt_cap] doubles, flag[tgt_cap], active[NYX_HIP_TARGET_MAX_ITERATIONS + 2]
-    int64_t tgt_cap = 0;
-    int64_t *d_prof = nullptr;
-    CoopBox *d_coop = nullptr;  // cooperative-mode mailboxes, one per trajectory-owning workgroup, then the packed scan words
+    DevBuf d_tgt;              // what its runs keep between the rounds (target_keep_block)
+    DevBuf d_prof;             // tuning.profile, calibration: [36][8] cycle counters - rows 0-15 owner workgroup 0, 16 mailbox counts, 17-32 the first helper workgroup
+    char *d_coop = nullptr;    // cooperative-mode mailboxes (mailbox_block of coop_cap): the pool's, not an owner's - see mailbox_acquire
     int64_t coop_cap = 0;
     int n_cu = 0;
     int last_coop_helpers = 0;  // helpers of the last launch (0 = solo)
@@ -216,10 +224,9 @@ static void *mailbox_acquire(int device, int64_t want_cap, int64_t *cap_out, boo
                 return p;
             }
     }
-    const int64_t cap = (want_cap + 255) / 256 * 256;
-    const size_t bytes = (size_t)cap * (sizeof(CoopBox) + sizeof(CoopOut)) + 3 * (size_t)(cap + 64) * sizeof(uint32_t);  // sets of 16: <= cap + 16 words; the part-1 answers last
+    const int64_t cap = cap_mailbox(want_cap);
     void *p = nullptr;
-    if (hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (hipExtMallocWithFlags(&p, mailbox_block(cap).total, hipDeviceMallocUncached) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     *cap_out = cap;
     return p;
 }
@@ -230,46 +237,48 @@ static void mailbox_release(int device, void *ptr, int64_t cap, bool pooled = tr
     g_mailbox_free.push_back(MailboxBlock{device, ptr, cap});
 }
 
-static int ensure_stm(DevArrays &a, int64_t n) {  // (the STMs of the first n trajectories)
-    if (a.stm_cap >= n) return NYX_HIP_RC_OK;
-    (void)hipFree(a.stm);
-    a.stm = nullptr;
-    HIP_TRY(hipMalloc(&a.stm, (size_t)std::max<int64_t>(n, 1024) * 81 * sizeof(double)));
-    a.stm_cap = std::max<int64_t>(n, 1024);
+// The grow rule (Owned::ensure, ctx_mem.h) on a block of a context: what may still use the block is a launch of this context, the
+// last of which ev_done marks - awaited on the host before the block is freed, at every site.  (It costs nothing: a block grows once
+// per size, and hipFree waits for the device anyway.)
+template <typename Mem, typename Bytes>
+static hipError_t grow(nyx_hip_ctx *ctx, Owned<Mem> &b, int64_t count, int64_t (*round)(int64_t), Bytes bytes_of, bool zero = false) {
+    return (hipError_t)b.ensure(count, [ctx] { return (int)(ctx->launched ? hipEventSynchronize(ctx->ev_done) : hipSuccess); }, round, bytes_of, zero);
+}
+
+// `v` on the device, in a block of its own.
+template <typename T> static hipError_t upload(nyx_hip_ctx *ctx, DevBuf &b, const std::vector<T> &v) {
+    if (hipError_t e = grow(ctx, b, (int64_t)v.size(), cap_exact, PerElement{sizeof(T)})) return e;
+    return hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+template <typename T> static T *part_at(char *base, const Part &p) { return (T *)(base + p.at); }
+
+static int ensure_stm(nyx_hip_ctx *ctx, DevArrays &a, int64_t n) {  // (the STMs of the first n trajectories)
+    HIP_TRY(grow(ctx, a.stm_buf, n, cap_stm, PerElement{81 * sizeof(double)}));
     return NYX_HIP_RC_OK;
 }
 
-static void free_arrays(DevArrays &a) {
-    (void)hipFree(a.dblock);
-    (void)hipHostFree(a.hblock);
-    (void)hipFree(a.stm);
-    a = DevArrays();
-}
-
-static int ensure_arrays(DevArrays &a, int64_t n, bool stats) {
-    if (n <= a.cap) return NYX_HIP_RC_OK;
-    free_arrays(a);
-    const int64_t cap = (std::max<int64_t>(n, 1024) + 63) / 64 * 64;
-    const size_t slot = (size_t)cap * 8;
-    const size_t n64 = 15 + (stats ? 5 : 0);  // epoch, step, 13 f64 (+ last_step, n_acc, n_rej, n_evals, last_error)
-    a.bytes = n64 * slot + (stats ? 2 * (size_t)cap * 4 : 0);
-    HIP_TRY(hipMalloc((void **)&a.dblock, a.bytes));
-    HIP_TRY(hipMemset(a.dblock, 0, a.bytes));  // (never hand the kernel recycled device memory it might read before writing)
-    HIP_TRY(hipHostMalloc((void **)&a.hblock, a.bytes, hipHostMallocDefault));
-    char *p = a.dblock;
-    a.epoch = (int64_t *)p; p += slot;
-    a.step = (int64_t *)p; p += slot;
-    for (auto &q : a.f) { q = (double *)p; p += slot; }
+static int ensure_arrays(nyx_hip_ctx *ctx, DevArrays &a, int64_t n, bool stats) {
+    if (n <= a.dev.cap) return NYX_HIP_RC_OK;
+    const auto bytes_of = [stats](int64_t cap) { return arrays_block(cap, stats).total; };
+    HIP_TRY(grow(ctx, a.mirror, n, cap_batch, bytes_of));
+    HIP_TRY(grow(ctx, a.dev, n, cap_batch, bytes_of, /*zero=*/true));  // (never hand the kernel recycled device memory it might read before writing)
+    const auto b = arrays_block(a.dev.cap, stats);
+    char *base = a.dev.as<char>();
+    a.bytes = b.total;
+    a.state_bytes = arrays_state_bytes(b);
+    a.epoch = part_at<int64_t>(base, b[AB_EPOCH]);
+    a.step = part_at<int64_t>(base, b[AB_STEP]);
+    for (int k = 0; k < kStateRows; ++k) a.f[k] = part_at<double>(base, arrays_state_row(b, k));
     if (stats) {
-        a.last_step = (int64_t *)p; p += slot;
-        a.n_acc = (int64_t *)p; p += slot;
-        a.n_rej = (int64_t *)p; p += slot;
-        a.n_evals = (int64_t *)p; p += slot;
-        a.last_error = (double *)p; p += slot;
-        a.status = (int32_t *)p; p += (size_t)cap * 4;
-        a.last_attempts = (int32_t *)p; p += (size_t)cap * 4;
+        a.last_step = part_at<int64_t>(base, b[AB_LAST_STEP]);
+        a.n_acc = part_at<int64_t>(base, b[AB_N_ACC]);
+        a.n_rej = part_at<int64_t>(base, b[AB_N_REJ]);
+        a.n_evals = part_at<int64_t>(base, b[AB_N_EVALS]);
+        a.last_error = part_at<double>(base, b[AB_LAST_ERROR]);
+        a.status = part_at<int32_t>(base, b[AB_STATUS]);
+        a.last_attempts = part_at<int32_t>(base, b[AB_LAST_ATTEMPTS]);
     }
-    a.cap = cap;
     return NYX_HIP_RC_OK;
 }
 
@@ -338,33 +347,6 @@ static nyx_hip_tuning_t resolve_tuning(const nyx_hip_tuning_t *t) {
         r.schedule = NYX_HIP_SCHED_EXPLICIT;
     }
     return r;
-}
-
-// A run stream (DevCfg.rs_*): the rows of the schedules `ids`, every range of every wave laid out as one contiguous piece that
-// starts a sixteen-row group of its own - a wave's walk then begins on its range's first row (in the common stream it begins at the
-// batch that holds it, with up to seven rows of the previous column in front, through the recursion with a zero state: at 70x70
-// 3 % of an owner's rows, and most of a short range).  `cols_x` = the column headers with `start` pointing into this stream.
-// Same rows, same operations: bit-identical sums.
-static void build_run_stream(const nyx_hip_ctx *ctx, std::initializer_list<int> ids, std::vector<double> &hyb, int64_t &vec_off, std::vector<ColHdr> &cols_x) {
-    cols_x = ctx->h_cols;
-    std::vector<HarmEntry> t;
-    const HarmEntry z = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    std::vector<char> seen(cols_x.size(), 0);
-    for (int k : ids) {
-        const DevSched &sd = ctx->host_cfg.sched[k];
-        for (int w = 0; w < DEV_MAX_WAVES; ++w)
-            for (int r = 0; r < sd.n_ranges[w]; ++r) {
-                t.resize((t.size() + 15) / 16 * 16, z);
-                for (int c = sd.range_c0[w][r]; c < sd.range_c0[w][r] + sd.range_cnt[w][r]; ++c) {
-                    if (c < 1 || c >= (int)cols_x.size() || seen[c]) continue;
-                    seen[c] = 1;
-                    const int32_t src = ctx->h_cols[c].start;
-                    cols_x[c].start = (int32_t)t.size();
-                    for (int q = 0; q < ctx->h_cols[c].rows; ++q) t.push_back(ctx->h_tab[(size_t)src + q]);
-                }
-            }
-    }
-    build_hybrid(t, hyb, vec_off);
 }
 
 // What the launch planner (launch_plan.h) reads of a context.
@@ -492,27 +474,20 @@ extern "C" double nyx_hip_last_kernel_ms(nyx_hip_ctx *ctx) {
 
 // Cycle accounting of workgroup 0 of the last launch (NYX_HIP_PROFILE=1): out[17][8], see the kernel (row 16: mailbox counters).
 extern "C" int32_t nyx_hip_debug_profile_helper(nyx_hip_ctx *ctx, int64_t *out /* [19][8] */) {
-    if (!ctx || !ctx->d_prof) return NYX_HIP_RC_BAD_ARG;
-    if (hipMemcpy(out, ctx->d_prof + 17 * 8, 19 * 8 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return NYX_HIP_RC_HIP_ERROR;  // (row 16 of `out` = row 33: the owner's latency loop; rows 17-18 = the integrator's stage in pieces)
+    if (!ctx || !ctx->d_prof.p) return NYX_HIP_RC_BAD_ARG;
+    if (hipMemcpy(out, ctx->d_prof.as<int64_t>() + 17 * 8, 19 * 8 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return NYX_HIP_RC_HIP_ERROR;  // (row 16 of `out` = row 33: the owner's latency loop; rows 17-18 = the integrator's stage in pieces)
     return NYX_HIP_RC_OK;
 }
 extern "C" int32_t nyx_hip_debug_profile(nyx_hip_ctx *ctx, int64_t *out) {
-    if (!ctx || !ctx->d_prof) return NYX_HIP_RC_BAD_ARG;
-    if (hipMemcpy(out, ctx->d_prof, 17 * 8 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return NYX_HIP_RC_HIP_ERROR;
+    if (!ctx || !ctx->d_prof.p) return NYX_HIP_RC_BAD_ARG;
+    if (hipMemcpy(out, ctx->d_prof.p, 17 * 8 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return NYX_HIP_RC_HIP_ERROR;
     return NYX_HIP_RC_OK;
 }
 
+// (the context's blocks are owners: `delete` frees them, on the context's device)
 extern "C" void nyx_hip_ctx_destroy(nyx_hip_ctx *ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
-    hipFree(ctx->d_cfg); hipFree(ctx->d_htab); hipFree(ctx->d_htab2); hipFree(ctx->d_cols2); hipFree(ctx->d_stm_hist); hipFree(ctx->d_hyb); for (int k = 0; k < 3; ++k) { hipFree(ctx->d_rs[k]); hipFree(ctx->d_rs_cols[k]); } hipFree(ctx->d_cols); hipFree(ctx->d_records);
-    free_arrays(ctx->in);
-    free_arrays(ctx->out);
-    free_arrays(ctx->cal);
-    free_arrays(ctx->work);
-    (void)hipFree(ctx->d_tgt);
-    (void)hipFree(ctx->d_swap);
-    (void)hipFree(ctx->d_mom);
     mailbox_release(ctx->device, ctx->d_coop, ctx->coop_cap, !(ctx->tune.debug_flags & 0x100000));
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -557,31 +532,24 @@ extern "C" int32_t nyx_hip_ctx_create(const nyx_hip_config_t *cfg, int32_t devic
         std::vector<double> hyb;
         int64_t vec_off = 0;
         build_hybrid(tab, hyb, vec_off);
-        HIP_TRY(hipMalloc(&ctx->d_hyb, hyb.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(ctx->d_hyb, hyb.data(), hyb.size() * sizeof(double), hipMemcpyHostToDevice));
-        dc.hyb = (uint64_t)ctx->d_hyb;
-        dc.hyb_v = (uint64_t)(ctx->d_hyb + vec_off);
+        HIP_TRY(upload(ctx.get(), ctx->d_hyb, hyb));
+        dc.hyb = (uint64_t)ctx->d_hyb.p;
+        dc.hyb_v = (uint64_t)(ctx->d_hyb.as<double>() + vec_off);
     }
     if (!tab2.empty()) {
         tab2.resize(tab2.size() + 4 * HARM_BATCH, HarmEntry{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
-        HIP_TRY(hipMalloc(&ctx->d_htab2, tab2.size() * sizeof(HarmEntry)));
-        HIP_TRY(hipMemcpy(ctx->d_htab2, tab2.data(), tab2.size() * sizeof(HarmEntry), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&ctx->d_cols2, b.cols2.size() * sizeof(ColHdr)));
-        HIP_TRY(hipMemcpy(ctx->d_cols2, b.cols2.data(), b.cols2.size() * sizeof(ColHdr), hipMemcpyHostToDevice));
-        dc.htab2 = (uint64_t)ctx->d_htab2;
-        dc.cols2 = (uint64_t)ctx->d_cols2;
+        HIP_TRY(upload(ctx.get(), ctx->d_htab2, tab2));
+        HIP_TRY(upload(ctx.get(), ctx->d_cols2, b.cols2));
+        dc.htab2 = (uint64_t)ctx->d_htab2.p;
+        dc.cols2 = (uint64_t)ctx->d_cols2.p;
     }
-    HIP_TRY(hipMalloc(&ctx->d_cfg, sizeof(DevCfg)));
-    HIP_TRY(hipMemcpy(ctx->d_cfg, &dc, sizeof(DevCfg), hipMemcpyHostToDevice));
+    HIP_TRY(upload(ctx.get(), ctx->d_cfg, std::vector<DevCfg>(1, dc)));  // (the descriptor: a table of one)
     if (!tab.empty()) {
         tab.resize(tab.size() + 4 * HARM_BATCH, HarmEntry{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0});  // the kernel touches a few batches ahead
-        HIP_TRY(hipMalloc(&ctx->d_htab, tab.size() * sizeof(HarmEntry)));
-        HIP_TRY(hipMemcpy(ctx->d_htab, tab.data(), tab.size() * sizeof(HarmEntry), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&ctx->d_cols, b.cols.size() * sizeof(ColHdr)));
-        HIP_TRY(hipMemcpy(ctx->d_cols, b.cols.data(), b.cols.size() * sizeof(ColHdr), hipMemcpyHostToDevice));
+        HIP_TRY(upload(ctx.get(), ctx->d_htab, tab));
+        HIP_TRY(upload(ctx.get(), ctx->d_cols, b.cols));
     }
-    HIP_TRY(hipMalloc(&ctx->d_records, b.records.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(ctx->d_records, b.records.data(), b.records.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(upload(ctx.get(), ctx->d_records, b.records));
     HIP_TRY(hipEventCreate(&ctx->ev0));
     HIP_TRY(hipEventCreate(&ctx->ev1));
     HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
@@ -601,7 +569,7 @@ static void views_of(DevArrays &d, int64_t n, bool stm, nyx_hip_states_t &so, ny
     so.n = n; so.epoch_ns = d.epoch;
     for (int k = 0; k < kStateRows; ++k) so.*kStateRow[k].s = d.f[k];
     so.step_ns = d.step;
-    so.stm = stm ? d.stm : nullptr;
+    so.stm = stm ? d.stm() : nullptr;
     ss = {d.status, d.last_step, d.last_error, d.last_attempts, d.n_acc, d.n_rej, d.n_evals};
 }
 
@@ -611,8 +579,8 @@ static void views_of(DevArrays &d, int64_t n, bool stm, nyx_hip_states_t &so, ny
 static int calibrate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, hipStream_t stream, bool backward = false) {
     const bool stm = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
     const int64_t n = in->n;
-    if (int rc = ensure_arrays(ctx->cal, n, true)) return rc;
-    if (int rc = stm ? ensure_stm(ctx->cal, n) : NYX_HIP_RC_OK) return rc;
+    if (int rc = ensure_arrays(ctx, ctx->cal, n, true)) return rc;
+    if (int rc = stm ? ensure_stm(ctx, ctx->cal, n) : NYX_HIP_RC_OK) return rc;
     nyx_hip_states_t so;
     nyx_hip_step_stats_t ss;
     views_of(ctx->cal, n, stm, so, ss);
@@ -627,7 +595,7 @@ static int calibrate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, hipStream_t s
         if (fit.usable) { ctx->weights[key] = fit.w; ctx->sched_dirty = true; }
         if (int rc = launch(ctx, r)) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(prof.data(), ctx->d_prof, prof.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(prof.data(), ctx->d_prof.p, prof.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         if (ss.status) {  // lanes that died early produce garbage cycle counts: keep the model's weights then
             HIP_TRY(hipMemcpy(cal_status.data(), ss.status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
             bool bad = false;
@@ -649,134 +617,145 @@ static int calibrate(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, hipStream_t s
     return NYX_HIP_RC_OK;
 }
 
+// ---- the steps of a launch (launch_here, below), in its order
+
+// The launch-shape dependent parts of the descriptor, after the plan (waves per workgroup, column schedules and cooperative mode:
+// launch_plan.h): whether the ephemeris records fit in LDS next to this layout's buffers (the quad layout is smaller than the D3 one).
+static int refresh_descriptor(nyx_hip_ctx *ctx, const LaunchPlan &plan, hipStream_t stream) {
+    const int kind = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) ? (plan.quad ? 2 : 1) : 0;
+    const int rd = ctx->host_cfg.rec_doubles;  // (after the schedule: chained attempts give the carried epoch data's LDS back)
+    const int want_rec = records_fit_lds(nyx_kernel_lds_bytes, rd, DEV_MAX_WAVES, kind, kind == 0 ? ctx->host_cfg.ed_reuse : 0) ? 1 : 0;
+    const bool dirty = plan.rebuilt || want_rec != ctx->host_cfg.rec_in_lds;
+    ctx->host_cfg.rec_in_lds = want_rec;
+    if (plan.rebuilt) ctx->rs_dirty = true;  // (the run streams follow the schedules)
+    if (dirty) HIP_TRY(hipMemcpyAsync(ctx->d_cfg.p, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
+    return NYX_HIP_RC_OK;
+}
+
+// NYX_HIP_FLAG_STM_TEXTBOOK: the stage matrices of the attempt in flight.
+static int bind_textbook_history(nyx_hip_ctx *ctx, int64_t n, DevBatch &bt) {
+    if (!(ctx->host_cfg.flags & NYX_HIP_FLAG_STM_TEXTBOOK)) return NYX_HIP_RC_OK;
+    HIP_TRY(grow(ctx, ctx->d_stm_hist, n, cap_stm_hist, PerElement{DEV_MAX_STAGES * 12 * sizeof(double)}));
+    bt.stm_hist = ctx->d_stm_hist.as<double>();
+    bt.stm_hist_stride = ctx->d_stm_hist.cap;
+    return NYX_HIP_RC_OK;
+}
+
+// Cooperative mode (plan.coop): helper workgroups on the idle CUs take over a share of the harmonics columns
+// (propagate_kernel.hip).  Owners and helpers that talk to each other get block indices that agree modulo 8 (round-robin XCD
+// dispatch: same L2).  Their mailboxes: borrowed from the pool, grown, cleared and bound (mailbox_block).
+static int bind_mailboxes(nyx_hip_ctx *ctx, const CoopPlan &cp, DevBatch &bt, hipStream_t stream) {
+    ctx->last_coop_helpers = 0;
+    if (!cp.run) return NYX_HIP_RC_OK;
+    const bool pooled = !(ctx->tune.debug_flags & 0x100000);
+    if (ctx->coop_cap < cp.boxes || ctx->coop_cap < cp.answers) {
+        // the block goes back to the process-wide pool, where another context (another host thread) may take and clear it
+        // at once: not before every launch of THIS context that uses it has finished (the device entry points are asynchronous)
+        if (ctx->d_coop && ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
+        mailbox_release(ctx->device, ctx->d_coop, ctx->coop_cap, pooled);
+        ctx->d_coop = nullptr;
+        ctx->coop_cap = 0;
+        // uncached device memory: the mailboxes are coherent across the XCDs' L2s without any cache
+        // write-back / invalidate in the kernel (those would also flush the harmonics table out of L2)
+        int64_t got = 0;
+        ctx->d_coop = (char *)mailbox_acquire(ctx->device, std::max<int64_t>({cp.boxes, cp.answers, 256}), &got, pooled);
+        if (ctx->d_coop) ctx->coop_cap = got;  // (else: no such memory here, every workgroup works alone)
+    }
+    if (!ctx->d_coop) return NYX_HIP_RC_OK;
+    const auto mb = mailbox_block(ctx->coop_cap);
+    // (only what this launch touches: its mailboxes, the scan words, and its answer blocks)
+    HIP_TRY(hipMemsetAsync(ctx->d_coop, 0, (size_t)cp.boxes * sizeof(CoopBox), stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_coop + mb[MB_POSTED].at, 0, mb[MB_ANSWERS].at - mb[MB_POSTED].at, stream));
+    CoopOut *out2 = part_at<CoopOut>(ctx->d_coop, mb[MB_ANSWERS]);
+    if (cp.answers) HIP_TRY(hipMemsetAsync(out2, 0, (size_t)cp.answers * sizeof(CoopOut), stream));
+    bt.coop_out2 = cp.answers ? out2 : nullptr;
+    bt.coop_fan = cp.fan ? 1 : 0;
+    bt.coop_helpers = (int32_t)cp.helpers; bt.coop_base = (int32_t)cp.base; bt.coop_box = part_at<CoopBox>(ctx->d_coop, mb[MB_BOXES]);
+    bt.coop_posted = part_at<uint32_t>(ctx->d_coop, mb[MB_POSTED]);
+    bt.coop_claimed = part_at<uint32_t>(ctx->d_coop, mb[MB_CLAIMED]);
+    bt.coop_finished = part_at<uint32_t>(ctx->d_coop, mb[MB_FINISHED]);
+    bt.coop_sets = (int32_t)((cp.n_own + 15) / 16);
+    bt.coop_parts = cp.parts;
+    bt.coop_mute = ctx->tune.coop_mute ? 1 : 0;  // (bit 1, the retired speculative fetch of helper_body, stays clear)
+    ctx->last_coop_helpers = (int)cp.helpers;
+    return NYX_HIP_RC_OK;
+}
+
+// Workgroups that stream the table walk run streams: one per schedule, every range of a wave at the head of a sixteen-row group
+// (DevCfg.rs_*, build_run_stream); rebuilt and uploaded when the schedules have changed.
+static int upload_run_streams(nyx_hip_ctx *ctx, hipStream_t stream) {
+    DevCfg &dc = ctx->host_cfg;
+    if (ctx->h_tab.empty() || dc.harm_feed == 0 || (dc.flags & NYX_HIP_FLAG_STM) || !ctx->rs_dirty) return NYX_HIP_RC_OK;
+    for (int k = 0; k < 3; ++k) {
+        const bool used = k == 0 ? (dc.harm_feed & 1) != 0 : (dc.coop_ok != 0 && (k == 1 ? (dc.harm_feed & 1) != 0 : (dc.harm_feed & 2) != 0));
+        dc.rs_hyb[k] = 0;
+        if (!used) continue;
+        std::vector<double> &rs = ctx->h_rs[k];
+        std::vector<ColHdr> &rs_cols = ctx->h_rs_cols[k];
+        int64_t vec_off = 0;
+        if (k == 0) build_run_stream(ctx->h_cols, ctx->h_tab, dc.sched, {DEV_SCHED_SOLO}, rs, vec_off, rs_cols);
+        else if (k == 1) build_run_stream(ctx->h_cols, ctx->h_tab, dc.sched, {DEV_SCHED_PRIMARY}, rs, vec_off, rs_cols);
+        else build_run_stream(ctx->h_cols, ctx->h_tab, dc.sched, {DEV_SCHED_HELPER, DEV_SCHED_HELPER2}, rs, vec_off, rs_cols);
+        HIP_TRY(grow(ctx, ctx->d_rs[k], (int64_t)rs.size(), cap_exact, PerElement{sizeof(double)}));
+        HIP_TRY(grow(ctx, ctx->d_rs_cols[k], (int64_t)rs_cols.size(), cap_exact, PerElement{sizeof(ColHdr)}));
+        HIP_TRY(hipMemcpyAsync(ctx->d_rs[k].p, rs.data(), rs.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(ctx->d_rs_cols[k].p, rs_cols.data(), rs_cols.size() * sizeof(ColHdr), hipMemcpyHostToDevice, stream));
+        dc.rs_hyb[k] = (uint64_t)ctx->d_rs[k].p;
+        dc.rs_hyb_v[k] = (uint64_t)(ctx->d_rs[k].as<double>() + vec_off);
+        dc.rs_cols[k] = (uint64_t)ctx->d_rs_cols[k].p;
+    }
+    ctx->rs_dirty = false;
+    HIP_TRY(hipMemcpyAsync(ctx->d_cfg.p, &dc, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
+    return NYX_HIP_RC_OK;
+}
+
+// tuning.profile, a calibration launch: the cycle counters, cleared.
+static int bind_profile_block(nyx_hip_ctx *ctx, bool calibrating, DevBatch &bt, hipStream_t stream) {
+    if (!ctx->tune.profile && !calibrating) return NYX_HIP_RC_OK;
+    HIP_TRY(grow(ctx, ctx->d_prof, 36 * 8, cap_exact, PerElement{sizeof(int64_t)}));
+    HIP_TRY(hipMemsetAsync(ctx->d_prof.p, 0, 36 * 8 * sizeof(int64_t), stream));
+    bt.prof = ctx->d_prof.as<int64_t>();
+    return NYX_HIP_RC_OK;
+}
+
+// The kernel between its events.
+static int launch_kernel(nyx_hip_ctx *ctx, const LaunchPlan &plan, const DevBatch &bt, bool timed, hipStream_t stream) {
+    const DevCfg &dc = ctx->host_cfg;
+    if (timed) HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    // (the LDS staging of the ephemeris records was decided at ctx_create for the D3 layout; the quad layout is smaller)
+    HIP_TRY(nyx_launch_propagate(bt, ctx->d_cfg.as<DevCfg>(), ctx->d_htab.as<HarmEntry>(), ctx->d_cols.as<ColHdr>(), ctx->d_records.as<double>(), plan.n_waves,
+                                 dc.rec_in_lds ? dc.rec_doubles : 0, dc.ed_reuse, stream, plan.quad ? 1 : 0,
+                                 (!dc.has_grav && !dc.has_drag && !dc.has_tides && !dc.has_grav2) ? 1 : 0));
+    if (timed) HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
+    ctx->launched = true;
+    return NYX_HIP_RC_OK;
+}
+
 // One launch, in the frame the context integrates in.
 static int launch_here(nyx_hip_ctx *ctx, const LaunchReq &r) {
     CTX_LOCK(ctx);
     const hipStream_t stream = (hipStream_t)r.stream;
     const nyx_hip_states_t *in = r.in;
     if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // one launch of a context at a time on the device
-    // launch-shape dependent parts of the descriptor: waves per workgroup, column schedules and cooperative mode (launch_plan.h),
-    // and whether the ephemeris records fit in LDS next to this layout's buffers (the quad layout is smaller than the D3 one)
     const LaunchPlan plan = plan_launch(plan_inputs(ctx), ctx->host_cfg, ctx->shape, in->n, ctx->sched_dirty);
-    const int nw = plan.n_waves;
-    const CoopPlan &cp = plan.coop;
     ctx->sched_dirty = false;
-    {
-        const int kind = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) ? (plan.quad ? 2 : 1) : 0;
-        const int rd = ctx->host_cfg.rec_doubles;  // (after the schedule: chained attempts give the carried epoch data's LDS back)
-        const int want_rec = records_fit_lds(nyx_kernel_lds_bytes, rd, DEV_MAX_WAVES, kind, kind == 0 ? ctx->host_cfg.ed_reuse : 0) ? 1 : 0;
-        const bool dirty = plan.rebuilt || want_rec != ctx->host_cfg.rec_in_lds;
-        ctx->host_cfg.rec_in_lds = want_rec;
-        if (plan.rebuilt) ctx->rs_dirty = true;  // (the run streams follow the schedules)
-        if (dirty) HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
-    }
+    if (int rc = refresh_descriptor(ctx, plan, stream)) return rc;
     BoundBatch b = bind_batch(r, (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0, ctx->fused_pred);
     if (b.rc != NYX_HIP_RC_OK) { nyx_set_error("%s", b.error); return b.rc; }
-    DevBatch &bt = b.bt;
-    if (ctx->host_cfg.flags & NYX_HIP_FLAG_STM_TEXTBOOK) {
-        if (ctx->stm_hist_cap < in->n) {
-            if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
-            (void)hipFree(ctx->d_stm_hist);
-            ctx->d_stm_hist = nullptr; ctx->stm_hist_cap = 0;
-            const int64_t cap = (in->n + 63) / 64 * 64;
-            HIP_TRY(hipMalloc(&ctx->d_stm_hist, (size_t)DEV_MAX_STAGES * 12 * (size_t)cap * sizeof(double)));
-            ctx->stm_hist_cap = cap;
-        }
-        bt.stm_hist = ctx->d_stm_hist;
-        bt.stm_hist_stride = ctx->stm_hist_cap;
+    if (int rc = bind_textbook_history(ctx, in->n, b.bt)) return rc;
+    if (int rc = bind_mailboxes(ctx, plan.coop, b.bt, stream)) return rc;
+    if (int rc = upload_run_streams(ctx, stream)) return rc;
+    // the column weights of this launch's workgroup shape: measured once per context (see calibrate())
+    const WKey key = weight_key(ctx->host_cfg, plan.n_waves, plan.quad, b.bt.coop_helpers > 0);
+    ctx->last_key = key;
+    const int64_t span = r.use_end ? INT64_MAX : (r.duration_ns < 0 ? -r.duration_ns : r.duration_ns);
+    if (calibrates_first(plan_inputs(ctx), ctx->host_cfg, key, plan.n_waves, in->n, /*min_n=*/64, !r.calibrating && !r.traj && !r.dur_ns && !r.ev, span, /*min_steps=*/100)) {
+        if (int rc = calibrate(ctx, in, stream, !r.use_end && r.duration_ns < 0)) return rc;
+        return launch_here(ctx, r);
     }
-    // Cooperative mode (plan.coop): helper workgroups on the idle CUs take over a share of the harmonics columns
-    // (propagate_kernel.hip).  Owners and helpers that talk to each other get block indices that agree modulo 8 (round-robin XCD
-    // dispatch: same L2).
-    ctx->last_coop_helpers = 0;
-    if (cp.run) {
-        const bool pooled = !(ctx->tune.debug_flags & 0x100000);
-        if (ctx->coop_cap < cp.boxes || ctx->coop_cap < cp.answers) {
-            // the block goes back to the process-wide pool, where another context (another host thread) may take and clear it
-            // at once: not before every launch of THIS context that uses it has finished (the device entry points are asynchronous)
-            if (ctx->d_coop && ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
-            mailbox_release(ctx->device, ctx->d_coop, ctx->coop_cap, pooled);
-            ctx->d_coop = nullptr;
-            ctx->coop_cap = 0;
-            // uncached device memory: the mailboxes are coherent across the XCDs' L2s without any cache
-            // write-back / invalidate in the kernel (those would also flush the harmonics table out of L2)
-            int64_t got = 0;
-            ctx->d_coop = (CoopBox *)mailbox_acquire(ctx->device, std::max<int64_t>({cp.boxes, cp.answers, 256}), &got, pooled);
-            if (ctx->d_coop) ctx->coop_cap = got;  // (else: no such memory here, every workgroup works alone)
-        }
-        if (ctx->d_coop) {
-            // (only what this launch touches: its mailboxes, the scan words, and its answer blocks - coop_cap of them behind the scan words)
-            HIP_TRY(hipMemsetAsync(ctx->d_coop, 0, (size_t)cp.boxes * sizeof(CoopBox), stream));
-            HIP_TRY(hipMemsetAsync(ctx->d_coop + ctx->coop_cap, 0, 3 * (size_t)(ctx->coop_cap + 64) * sizeof(uint32_t), stream));
-            uint32_t *words = (uint32_t *)(ctx->d_coop + ctx->coop_cap);
-            CoopOut *out2 = (CoopOut *)(words + 3 * (ctx->coop_cap + 64));
-            if (cp.answers) HIP_TRY(hipMemsetAsync(out2, 0, (size_t)cp.answers * sizeof(CoopOut), stream));
-            bt.coop_out2 = cp.answers ? out2 : nullptr;
-            bt.coop_fan = cp.fan ? 1 : 0;
-            bt.coop_helpers = (int32_t)cp.helpers; bt.coop_base = (int32_t)cp.base; bt.coop_box = ctx->d_coop;
-            bt.coop_posted = words; bt.coop_claimed = words + (ctx->coop_cap + 64); bt.coop_finished = words + 2 * (ctx->coop_cap + 64);
-            bt.coop_sets = (int32_t)((cp.n_own + 15) / 16);
-            bt.coop_parts = cp.parts;
-            bt.coop_mute = ctx->tune.coop_mute ? 1 : 0;  // (bit 1, the retired speculative fetch of helper_body, stays clear)
-            ctx->last_coop_helpers = (int)cp.helpers;
-        }
-    }
-    if (!ctx->h_tab.empty() && ctx->host_cfg.harm_feed != 0 && !(ctx->host_cfg.flags & NYX_HIP_FLAG_STM)) {
-        // workgroups that stream the table walk run streams: one per schedule, every range of a wave at the head of a sixteen-row
-        // group (DevCfg.rs_*)
-        if (ctx->rs_dirty) {
-            for (int k = 0; k < 3; ++k) {
-                const bool used = k == 0 ? (ctx->host_cfg.harm_feed & 1) != 0
-                                  : (ctx->host_cfg.coop_ok != 0 && (k == 1 ? (ctx->host_cfg.harm_feed & 1) != 0 : (ctx->host_cfg.harm_feed & 2) != 0));
-                ctx->host_cfg.rs_hyb[k] = 0;
-                if (!used) continue;
-                int64_t vec_off = 0;
-                if (k == 0) build_run_stream(ctx, {DEV_SCHED_SOLO}, ctx->h_rs[k], vec_off, ctx->h_rs_cols[k]);
-                else if (k == 1) build_run_stream(ctx, {DEV_SCHED_PRIMARY}, ctx->h_rs[k], vec_off, ctx->h_rs_cols[k]);
-                else build_run_stream(ctx, {DEV_SCHED_HELPER, DEV_SCHED_HELPER2}, ctx->h_rs[k], vec_off, ctx->h_rs_cols[k]);
-                if (ctx->h_rs[k].size() > ctx->rs_cap[k]) {
-                    if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));
-                    (void)hipFree(ctx->d_rs[k]);
-                    ctx->d_rs[k] = nullptr; ctx->rs_cap[k] = 0;
-                    HIP_TRY(hipMalloc(&ctx->d_rs[k], ctx->h_rs[k].size() * sizeof(double)));
-                    ctx->rs_cap[k] = ctx->h_rs[k].size();
-                }
-                if (!ctx->d_rs_cols[k]) HIP_TRY(hipMalloc(&ctx->d_rs_cols[k], ctx->h_rs_cols[k].size() * sizeof(ColHdr)));
-                HIP_TRY(hipMemcpyAsync(ctx->d_rs[k], ctx->h_rs[k].data(), ctx->h_rs[k].size() * sizeof(double), hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(ctx->d_rs_cols[k], ctx->h_rs_cols[k].data(), ctx->h_rs_cols[k].size() * sizeof(ColHdr), hipMemcpyHostToDevice, stream));
-                ctx->host_cfg.rs_hyb[k] = (uint64_t)ctx->d_rs[k];
-                ctx->host_cfg.rs_hyb_v[k] = (uint64_t)(ctx->d_rs[k] + vec_off);
-                ctx->host_cfg.rs_cols[k] = (uint64_t)ctx->d_rs_cols[k];
-            }
-            ctx->rs_dirty = false;
-            HIP_TRY(hipMemcpyAsync(ctx->d_cfg, &ctx->host_cfg, sizeof(DevCfg), hipMemcpyHostToDevice, stream));
-        }
-    }
-    {
-        // the column weights of this launch's workgroup shape: measured once per context (see calibrate())
-        const WKey key = weight_key(ctx->host_cfg, nw, plan.quad, bt.coop_helpers > 0);
-        ctx->last_key = key;
-        const int64_t span = r.use_end ? INT64_MAX : (r.duration_ns < 0 ? -r.duration_ns : r.duration_ns);
-        if (calibrates_first(plan_inputs(ctx), ctx->host_cfg, key, nw, in->n, /*min_n=*/64, !r.calibrating && !r.traj && !r.dur_ns && !r.ev, span, /*min_steps=*/100)) {
-            if (int rc = calibrate(ctx, in, stream, !r.use_end && r.duration_ns < 0)) return rc;
-            return launch_here(ctx, r);
-        }
-    }
-    if (ctx->tune.profile || r.calibrating) {
-        if (!ctx->d_prof) HIP_TRY(hipMalloc(&ctx->d_prof, 36 * 8 * sizeof(int64_t)));  // rows 0-15 owner workgroup 0, 16 mailbox counts, 17-32 the first helper workgroup
-        HIP_TRY(hipMemsetAsync(ctx->d_prof, 0, 36 * 8 * sizeof(int64_t), stream));
-        bt.prof = ctx->d_prof;
-    }
-    if (r.timed) HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    const bool quad = plan.quad;
-    // (the LDS staging of the ephemeris records was decided at ctx_create for the D3 layout; the quad layout is smaller)
-    HIP_TRY(nyx_launch_propagate(bt, ctx->d_cfg, ctx->d_htab, ctx->d_cols, ctx->d_records, nw,
-                                 ctx->host_cfg.rec_in_lds ? ctx->host_cfg.rec_doubles : 0, ctx->host_cfg.ed_reuse, stream, quad ? 1 : 0,
-                                 (!ctx->host_cfg.has_grav && !ctx->host_cfg.has_drag && !ctx->host_cfg.has_tides && !ctx->host_cfg.has_grav2) ? 1 : 0));
-    if (r.timed) HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_done, stream));
-    ctx->launched = true;
-    return NYX_HIP_RC_OK;
+    if (int rc = bind_profile_block(ctx, r.calibrating, b.bt, stream)) return rc;
+    return launch_kernel(ctx, plan, b.bt, r.timed, stream);
 }
 
 static int launch(nyx_hip_ctx *ctx, const LaunchReq &r) {
@@ -796,22 +775,19 @@ static int launch(nyx_hip_ctx *ctx, const LaunchReq &r) {
     const hipStream_t stream = (hipStream_t)r.stream;
     const nyx_hip_states_t *in = r.in, *out = r.out;
     if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // (the copy below is shared by the launches of this context)
-    if (ctx->swap_cap < in->n) {
-        (void)hipFree(ctx->d_swap);
-        ctx->d_swap = nullptr; ctx->swap_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_swap, (size_t)7 * (size_t)in->n * sizeof(double)));  // (row 6: the forward shift's status words)
-        ctx->swap_cap = in->n;
-    }
+    HIP_TRY(grow(ctx, ctx->d_swap, in->n, cap_exact, PerElement{7 * sizeof(double)}));  // (row 6: the forward shift's status words)
+    double *swap = ctx->d_swap.as<double>();
+    const size_t swap_row = (size_t)ctx->d_swap.cap;
     nyx_hip_states_t in2 = *in;
     for (int q = 0; q < kCartRows; ++q) {
-        double *row = in2.*kStateRow[q].s = ctx->d_swap + (size_t)q * (size_t)ctx->swap_cap;
+        double *row = in2.*kStateRow[q].s = swap + (size_t)q * swap_row;
         HIP_TRY(hipMemcpyAsync(row, in->*kStateRow[q].s, (size_t)in->n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
     // a start epoch outside the swap body's ephemeris gives a clamped, i.e. WRONG, translation: its status is kept aside and
     // merged into the run's status by the back-translation (the propagation launch rewrites the status array in between)
-    int32_t *fwd_status = (int32_t *)(ctx->d_swap + (size_t)6 * (size_t)ctx->swap_cap);
+    int32_t *fwd_status = (int32_t *)(swap + 6 * swap_row);
     HIP_TRY(hipMemsetAsync(fwd_status, 0, (size_t)in->n * sizeof(int32_t), stream));
-    HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg, ctx->d_records, ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, in->epoch_ns,
+    HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg.as<DevCfg>(), ctx->d_records.as<double>(), ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, in->epoch_ns,
                                    in2.x_km, in2.y_km, in2.z_km, in2.vx_km_s, in2.vy_km_s, in2.vz_km_s, +1.0, fwd_status, nullptr, r.dur_ns, stream));
     LaunchReq r2 = r;
     r2.in = &in2;
@@ -819,7 +795,7 @@ static int launch(nyx_hip_ctx *ctx, const LaunchReq &r) {
     if (r.traj && r.traj->capacity > 0)  // entry 0 (step-major: the first n elements of every array) = the state in the caller's frame
         for (int q = 0; q < kCartRows; ++q)
             if (double *dst = r.traj->*kTrajRow[q]) HIP_TRY(hipMemcpyAsync(dst, in->*kStateRow[q].s, (size_t)in->n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg, ctx->d_records, ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, out->epoch_ns,
+    HIP_TRY(nyx_launch_frame_shift(ctx->d_cfg.as<DevCfg>(), ctx->d_records.as<double>(), ctx->swap_seg, ctx->swap_sign, ctx->swap_n_chain, in->n, out->epoch_ns,
                                    out->x_km, out->y_km, out->z_km, out->vx_km_s, out->vy_km_s, out->vz_km_s, -1.0, r.stats ? r.stats->status : nullptr,
                                    fwd_status, r.dur_ns, stream));
     HIP_TRY(hipEventRecord(ctx->ev_done, stream));
@@ -863,8 +839,8 @@ struct Staged {
 // `upload_stm` false leaves ctx->in.stm allocated but unwritten (covariance mapping starts from identity); true: check_run has seen in->stm.
 static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, Staged &sg, bool upload_stm) {
     const int64_t n = in->n;
-    if (int rc = ensure_arrays(ctx->in, n, false)) return rc;
-    if (int rc = ensure_arrays(ctx->out, n, true)) return rc;
+    if (int rc = ensure_arrays(ctx, ctx->in, n, false)) return rc;
+    if (int rc = ensure_arrays(ctx, ctx->out, n, true)) return rc;
     DevArrays &di = ctx->in, &dq = ctx->out;
     nyx_hip_states_t &din = sg.din;  // (rows the caller left null stay null)
     std::memset(&din, 0, sizeof din);
@@ -873,14 +849,14 @@ static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, Staged &sg,
     for (int k = 0; k < kStateRows; ++k)
         if (const double *h = in->*kStateRow[k].s) std::memcpy(di.host(din.*kStateRow[k].s = di.f[k]), h, n * sizeof(double));
     if (in->step_ns) std::memcpy(di.host(din.step_ns = di.step), in->step_ns, n * sizeof(int64_t));
-    HIP_TRY(hipMemcpy(di.dblock, di.hblock, (size_t)((char *)(di.f[kStateRows - 1] + di.cap) - di.dblock), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(di.dev.p, di.mirror.p, di.state_bytes, hipMemcpyHostToDevice));
     sg.stm = (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0;
     if (sg.stm) {
         for (DevArrays *d : {&di, &dq})
-            if (int rc = ensure_stm(*d, n)) return rc;
-        if (upload_stm) HIP_TRY(hipMemcpy(di.stm, in->stm, (size_t)n * 81 * sizeof(double), hipMemcpyHostToDevice));
+            if (int rc = ensure_stm(ctx, *d, n)) return rc;
+        if (upload_stm) HIP_TRY(hipMemcpy(di.stm(), in->stm, (size_t)n * 81 * sizeof(double), hipMemcpyHostToDevice));
     }
-    din.stm = sg.stm ? di.stm : nullptr;
+    din.stm = sg.stm ? di.stm() : nullptr;
     views_of(dq, n, sg.stm, sg.dout, sg.dst);
     return NYX_HIP_RC_OK;
 }
@@ -888,12 +864,12 @@ static int stage_batch(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, Staged &sg,
 // D2H of ctx->out (states + stats) through the pinned mirror, unpacked into the caller's arrays.
 static int fetch_batch(nyx_hip_ctx *ctx, int64_t n, bool stm, nyx_hip_states_t *out, nyx_hip_step_stats_t *stats) {
     DevArrays &dq = ctx->out;
-    HIP_TRY(hipMemcpy(dq.hblock, dq.dblock, dq.bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dq.mirror.p, dq.dev.p, dq.bytes, hipMemcpyDeviceToHost));
     auto get = [&](auto *h, auto *dev) { if (h) std::memcpy(h, dq.host(dev), n * sizeof *h); };
     get(out->epoch_ns, dq.epoch);
     for (int k = 0; k < kStateRows; ++k) get(out->*kStateRow[k].s, dq.f[k]);
     get(out->step_ns, dq.step);
-    if (stm && out->stm) HIP_TRY(hipMemcpy(out->stm, dq.stm, (size_t)n * 81 * sizeof(double), hipMemcpyDeviceToHost));
+    if (stm && out->stm) HIP_TRY(hipMemcpy(out->stm, dq.stm(), (size_t)n * 81 * sizeof(double), hipMemcpyDeviceToHost));
     if (stats) {
         get(stats->status, dq.status); get(stats->last_step_ns, dq.last_step); get(stats->last_error, dq.last_error);
         get(stats->last_attempts, dq.last_attempts); get(stats->n_accepted, dq.n_acc); get(stats->n_rejected, dq.n_rej); get(stats->n_evals, dq.n_evals);
@@ -910,7 +886,7 @@ struct DevTraj {
     int alloc(int64_t capacity, int64_t n_) {
         n = n_;
         slots = (size_t)capacity * (size_t)n;
-        if (int rc = block.alloc(traj_block_bytes(capacity, n))) return rc;
+        if (int rc = dev_alloc(block, traj_block_bytes(capacity, n))) return rc;
         t = traj_in_block(block.p, capacity, n);
         return NYX_HIP_RC_OK;
     }
@@ -940,13 +916,12 @@ static int stage_trajs(DevTraj &src, DevTraj &second, const nyx_hip_traj_t *traj
 // (a failure: "`what` failed") and, `timed`, its kernel time read, the parts `down` copied to their host arrays.  A part of size 0 or
 // with a null host array is skipped.  `timed` false: the targeter, whose timed launches are the propagator's.
 struct HostPart { Part part; const void *host; };
-template <typename T> static T *part_at(char *base, const Part &p) { return (T *)(base + p.at); }
 template <int N, typename Entry>
 static int host_block(nyx_hip_ctx *ctx, const Block<N> &b, const std::vector<HostPart> &up, const std::vector<HostPart> &down, const char *what, bool timed, Entry entry) {
     CTX_LOCK(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     DevBuf blk;
-    if (int rc = blk.alloc(b.total)) return rc;
+    if (int rc = dev_alloc(blk, b.total)) return rc;
     char *base = blk.as<char>();
     for (const HostPart &h : up)
         if (h.part.bytes && h.host) HIP_TRY(hipMemcpy(base + h.part.at, h.host, h.part.bytes, hipMemcpyHostToDevice));
@@ -1101,13 +1076,13 @@ extern "C" int32_t nyx_hip_traj_every_device(nyx_hip_ctx *ctx, const nyx_hip_tra
 static int moments_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *s, const int32_t *status, const double *x0, double *out55, hipStream_t stream) {
     if (Refusal r = check_moments(ctx, s, out55, false)) return refused(r);
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_mom) HIP_TRY(hipMalloc((void **)&ctx->d_mom, (size_t)(MOM_BLOCKS + 1) * MOM_N * sizeof(double)));
+    HIP_TRY(grow(ctx, ctx->d_mom, (MOM_BLOCKS + 1) * MOM_N, cap_exact, PerElement{sizeof(double)}));
     MomArgs a;
     std::memset(&a, 0, sizeof a);
     a.n = s->n;
     for (int k = 0; k < kMomentRows; ++k) { a.f[k] = s->*kStateRow[k].s; a.x0[k] = x0 ? x0[k] : 0.0; }
     a.status = status;
-    a.partial = ctx->d_mom;
+    a.partial = ctx->d_mom.as<double>();
     if (ctx->launched) HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_done, 0));  // (the scratch is the context's: one reduction at a time)
     HIP_TRY(nyx_launch_moments(a, out55, stream));
     HIP_TRY(hipEventRecord(ctx->ev_done, stream));
@@ -1129,7 +1104,7 @@ extern "C" int32_t nyx_hip_ensemble_moments(nyx_hip_ctx *ctx, const nyx_hip_stat
     HIP_TRY(hipSetDevice(ctx->device));
     const auto b = moments_block(states->n, status != nullptr);
     DevBuf blk;
-    if (int rc = blk.alloc(b.total)) return rc;
+    if (int rc = dev_alloc(blk, b.total)) return rc;
     nyx_hip_states_t d{}; d.n = states->n;  // (the staged rows: a device pointer where the caller gave a row)
     for (int k = 0; k < kMomentRows; ++k)
         if (const double *h = states->*kStateRow[k].s) {
@@ -1138,8 +1113,8 @@ extern "C" int32_t nyx_hip_ensemble_moments(nyx_hip_ctx *ctx, const nyx_hip_stat
         }
     int32_t *dst = status ? (int32_t *)(blk.as<char>() + b[M_STATUS].at) : nullptr;
     if (b[M_STATUS].bytes) HIP_TRY(hipMemcpy(dst, status, b[M_STATUS].bytes, hipMemcpyHostToDevice));
-    if (!ctx->d_mom) HIP_TRY(hipMalloc((void **)&ctx->d_mom, (size_t)(MOM_BLOCKS + 1) * MOM_N * sizeof(double)));
-    double *result = ctx->d_mom + (size_t)MOM_BLOCKS * MOM_N;
+    HIP_TRY(grow(ctx, ctx->d_mom, (MOM_BLOCKS + 1) * MOM_N, cap_exact, PerElement{sizeof(double)}));
+    double *result = ctx->d_mom.as<double>() + (size_t)MOM_BLOCKS * MOM_N;
     if (int rc = moments_device(ctx, &d, dst, x0, result, nullptr)) return rc;
     HIP_TRY(hipMemcpy(out55, result, MOM_N * sizeof(double), hipMemcpyDeviceToHost));
     return NYX_HIP_RC_OK;
@@ -1157,8 +1132,8 @@ static int traj_eval_host(nyx_hip_ctx *ctx, const nyx_hip_traj_t *traj, int64_t 
     DevBuf d_query, d_status;  // traj_at with m > 0 only: the query epochs [m], the statuses [m][n]
     const size_t qbytes = mode == TRAJ_MODE_AT ? (size_t)m * sizeof(int64_t) : 0, sbytes = mode == TRAJ_MODE_AT ? (size_t)m * (size_t)n * sizeof(int32_t) : 0;
     if (qbytes) {
-        if (int rc = d_query.alloc(qbytes)) return rc;
-        if (int rc = d_status.alloc(sbytes)) return rc;
+        if (int rc = dev_alloc(d_query, qbytes)) return rc;
+        if (int rc = dev_alloc(d_status, sbytes)) return rc;
         HIP_TRY(hipMemcpy(d_query.p, query, qbytes, hipMemcpyHostToDevice));
     }
     if (int rc = traj_eval_device(ctx, &src.t, n, d_query.as<int64_t>(), m, step_ns, &dst.t, d_status.as<int32_t>(), mode, nullptr)) return rc;
@@ -1341,7 +1316,7 @@ extern "C" int32_t nyx_hip_traj_eclipse_device(nyx_hip_ctx *ctx, const nyx_hip_t
     CTX_LOCK(ctx);
     EclArgs a;
     series_fill(a, traj, n, capacity, values, len, q);
-    a.records = ctx->d_records;
+    a.records = ctx->d_records.as<double>();
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_eclipse(&a, ctx->host_cfg.seg, stream); });
 }
 
@@ -1384,7 +1359,7 @@ extern "C" int32_t nyx_hip_traj_frame_values_device(nyx_hip_ctx *ctx, const nyx_
     CTX_LOCK(ctx);
     FrmArgs a;
     series_fill(a, traj, n, capacity, values, len, q);
-    a.records = ctx->d_records;
+    a.records = ctx->d_records.as<double>();
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_frame_values(&a, ctx->host_cfg.seg, stream); });
 }
 
@@ -1451,7 +1426,7 @@ extern "C" int32_t nyx_hip_lambert_grid_device(nyx_hip_ctx *ctx, const nyx_hip_l
     CTX_LOCK(ctx);
     LmbGridArgs a;
     std::memset(&a, 0, sizeof a);
-    a.q = *q; a.records = ctx->d_records; a.values = values; a.status = status;
+    a.q = *q; a.records = ctx->d_records.as<double>(); a.values = values; a.status = status;
     return timed_launch(ctx, stream, [&] { return nyx_launch_lambert_grid(&a, ctx->host_cfg.seg, stream); });
 }
 
@@ -1485,19 +1460,6 @@ static Refusal check_tgt(const nyx_hip_ctx *ctx, const nyx_hip_states_t *in, con
     return check_target_context(*q, ctx->host_cfg.n_seg, (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0, ctx->swap_n_chain != 0);
 }
 
-// what the runs keep between the rounds, their flags and the counters: one block of the context, grown on demand
-static int ensure_target_keep(nyx_hip_ctx *ctx, int64_t n) {
-    if (ctx->tgt_cap >= n) return NYX_HIP_RC_OK;
-    (void)hipFree(ctx->d_tgt);
-    ctx->d_tgt = nullptr; ctx->tgt_cap = 0;
-    const int64_t cap = (std::max<int64_t>(n, 1024) + 63) / 64 * 64;
-    const size_t bytes = (size_t)TGT_KEEP_ROWS * (size_t)cap * sizeof(double) + (size_t)cap * sizeof(int32_t) + (NYX_HIP_TARGET_MAX_ITERATIONS + 2) * sizeof(int32_t);
-    HIP_TRY(hipMalloc((void **)&ctx->d_tgt, bytes));
-    HIP_TRY(hipMemset(ctx->d_tgt, 0, bytes));
-    ctx->tgt_cap = cap;
-    return NYX_HIP_RC_OK;
-}
-
 // The loop on device arrays: one launch to the correction epoch, the seed, then per round one in-place propagation of the work block,
 // the step kernel and the 4-byte read of the runs still active.  Under the context's lock for its whole length.
 extern "C" int32_t nyx_hip_target_batch_device(nyx_hip_ctx *ctx, const nyx_hip_states_t *in, const nyx_hip_target_query_t *q, nyx_hip_target_result_t *res,
@@ -1511,9 +1473,11 @@ extern "C" int32_t nyx_hip_target_batch_device(nyx_hip_ctx *ctx, const nyx_hip_s
     HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->ev_done));  // (the blocks below may grow: nothing of this context is in flight then)
     const int64_t rows = (int64_t)(1 + q->n_vars) * n;
-    if (int rc = ensure_arrays(ctx->out, n, true)) return rc;
-    if (int rc = ensure_arrays(ctx->work, rows, true)) return rc;
-    if (int rc = ensure_target_keep(ctx, n)) return rc;
+    if (int rc = ensure_arrays(ctx, ctx->out, n, true)) return rc;
+    if (int rc = ensure_arrays(ctx, ctx->work, rows, true)) return rc;
+    // what the runs keep between the rounds, their flags and the counters: one block of the context
+    HIP_TRY(grow(ctx, ctx->d_tgt, n, cap_batch, [](int64_t cap) { return target_keep_block(cap).total; }, /*zero=*/true));
+    const auto keep = target_keep_block(ctx->d_tgt.cap);
     nyx_hip_states_t xs, ws;
     nyx_hip_step_stats_t xss, wss;
     views_of(ctx->out, n, false, xs, xss);
@@ -1524,14 +1488,14 @@ extern "C" int32_t nyx_hip_target_batch_device(nyx_hip_ctx *ctx, const nyx_hip_s
     if (int rc = launch(ctx, leg)) return rc;
     TgtArgs a;
     std::memset(&a, 0, sizeof a);
-    a.q = *q; a.n = n; a.cap = ctx->tgt_cap;
+    a.q = *q; a.n = n; a.cap = ctx->d_tgt.cap;
     a.start = tgt_rows(xs, xss.status);
     a.work = tgt_rows(ws, wss.status);
-    a.keep = (double *)ctx->d_tgt;
-    a.flag = (int32_t *)(a.keep + (size_t)TGT_KEEP_ROWS * (size_t)ctx->tgt_cap);
-    a.active = a.flag + ctx->tgt_cap;
+    a.keep = part_at<double>(ctx->d_tgt.as<char>(), keep[TK_KEEP]);
+    a.flag = part_at<int32_t>(ctx->d_tgt.as<char>(), keep[TK_FLAG]);
+    a.active = part_at<int32_t>(ctx->d_tgt.as<char>(), keep[TK_ACTIVE]);
     a.chain = resolve_chain(chain_view(*q), ctx->host_cfg.seg);
-    a.records = ctx->d_records;
+    a.records = ctx->d_records.as<double>();
     a.o_status = res->status; a.o_iterations = res->iterations; a.o_correction = res->correction; a.o_errors = res->achieved_errors;
     a.corrected = tgt_rows(res->corrected, nullptr);
     a.achieved = tgt_rows(res->achieved, nullptr);
@@ -1654,7 +1618,7 @@ extern "C" int32_t nyx_hip_traj_link_device(nyx_hip_ctx *ctx, const nyx_hip_traj
     CTX_LOCK(ctx);
     LnkArgs a;
     series_fill(a, traj, n, capacity, values, len, q);
-    a.ref = *ref; a.n_ref = n_ref; a.epoch0 = epoch0_ns; a.records = ctx->d_records;
+    a.ref = *ref; a.n_ref = n_ref; a.epoch0 = epoch0_ns; a.records = ctx->d_records.as<double>();
     return timed_launch(ctx, stream, [&] { return nyx_launch_traj_link(&a, ctx->host_cfg.seg, stream); });
 }
 
@@ -1747,7 +1711,7 @@ extern "C" int32_t nyx_hip_traj_series_stats(nyx_hip_ctx *ctx, int32_t kind, con
     DevBuf first;
     const size_t first_bytes = (ref && epoch0_ns) ? (size_t)n * sizeof(int64_t) : 0;
     if (first_bytes)
-        if (int rc = first.alloc(first_bytes)) return rc;
+        if (int rc = dev_alloc(first, first_bytes)) return rc;
     if (int rc = host_block(ctx, b, {{b[STB_STATUS], status}}, {{b[STB_STATS], stats}, {b[STB_LEN], len}}, "report or statistics kernel", true, [&](char *base) -> int {
             double *d_values = part_at<double>(base, b[STB_VALUES]);
             int32_t *d_len = part_at<int32_t>(base, b[STB_LEN]);
@@ -1775,8 +1739,8 @@ extern "C" int32_t nyx_hip_propagate_until_event(nyx_hip_ctx *ctx, const nyx_hip
         const int64_t n = in->n;
         if (int rc = dtraj.alloc(traj->capacity, n)) return rc;
         const auto b = event_block(n);
-        if (int rc = evbuf.alloc(b.total)) return rc;
-        if (int rc = evdesc.alloc(sizeof(nyx_hip_event_t))) return rc;
+        if (int rc = dev_alloc(evbuf, b.total)) return rc;
+        if (int rc = dev_alloc(evdesc, sizeof(nyx_hip_event_t))) return rc;
         HIP_TRY(hipMemcpy(evdesc.p, event, sizeof(nyx_hip_event_t), hipMemcpyHostToDevice));
         ev.ev = evdesc.as<nyx_hip_event_t>(); ev.ev_mu = ctx->host_cfg.mu_central;
         char *base = evbuf.as<char>();
@@ -1811,7 +1775,7 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
     const auto b = predict_block(in ? in->n : 0, h);  // (used behind check_run only)
     return host_run(ctx, in, out, stats, false, false, [&](Staged &sg) -> int {
         const int64_t n = in->n;
-        if (int rc = block.alloc(b.total)) return rc;
+        if (int rc = dev_alloc(block, b.total)) return rc;
         char *base = block.as<char>();
         HIP_TRY(hipMemcpy(base + b[P_COVAR].at, est->covar, b[P_COVAR].bytes, hipMemcpyHostToDevice));
         if (est->state_dev) HIP_TRY(hipMemcpy(base + b[P_SDEV].at, est->state_dev, b[P_SDEV].bytes, hipMemcpyHostToDevice));
@@ -1847,7 +1811,7 @@ extern "C" int32_t nyx_hip_predict_until(nyx_hip_ctx *ctx, const nyx_hip_states_
         LaunchReq seg;  // (per-trajectory durations; segment 0 reads the staged states, the later ones run in place)
         seg.in = &sg.din; seg.out = &sg.dout; seg.stats = &sg.dst; seg.dur_ns = a.dur; seg.stream = stream;
         if (predict_fused(plan_inputs(ctx), ctx->host_cfg, n, ctx->swap_n_chain)) {
-            if (int rc = pa_dev.alloc(sizeof(PredictArgs))) return rc;
+            if (int rc = dev_alloc(pa_dev, sizeof(PredictArgs))) return rc;
             HIP_TRY(hipMemcpyAsync(pa_dev.p, &a, sizeof(PredictArgs), hipMemcpyHostToDevice, stream));
             ctx->fused_pred = (const PredictArgs *)pa_dev.p;
             const int rc = launch(ctx, seg);

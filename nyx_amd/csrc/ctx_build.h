@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -147,6 +148,35 @@ inline void build_hybrid(const std::vector<HarmEntry> &tab, std::vector<double> 
                 const HarmEntry &e = r < n ? tab[r] : z;
                 hyb.push_back(j == 0 ? e.t3 : j == 1 ? e.t4 : j == 2 ? e.t5 : e.t6);
             }
+}
+
+// A run stream (DevCfg.rs_*): the rows of the schedules `ids` of `sched` (DevCfg.sched), every range of every wave laid out as one
+// contiguous piece that starts a sixteen-row group of its own - a wave's walk then begins on its range's first row (in the common
+// stream it begins at the batch that holds it, with up to seven rows of the previous column in front, through the recursion with a
+// zero state: at 70x70 3 % of an owner's rows, and most of a short range).  `cols` / `tab`: the column headers and the entry table
+// (without its tail padding); `cols_x` = the column headers with `start` pointing into this stream.
+// Same rows, same operations: bit-identical sums.
+inline void build_run_stream(const std::vector<ColHdr> &cols, const std::vector<HarmEntry> &tab, const DevSched *sched, std::initializer_list<int> ids,
+                             std::vector<double> &hyb, int64_t &vec_off, std::vector<ColHdr> &cols_x) {
+    cols_x = cols;
+    std::vector<HarmEntry> t;
+    const HarmEntry z = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    std::vector<char> seen(cols_x.size(), 0);
+    for (int k : ids) {
+        const DevSched &sd = sched[k];
+        for (int w = 0; w < DEV_MAX_WAVES; ++w)
+            for (int r = 0; r < sd.n_ranges[w]; ++r) {
+                t.resize((t.size() + 15) / 16 * 16, z);
+                for (int c = sd.range_c0[w][r]; c < sd.range_c0[w][r] + sd.range_cnt[w][r]; ++c) {
+                    if (c < 1 || c >= (int)cols_x.size() || seen[c]) continue;
+                    seen[c] = 1;
+                    const int32_t src = cols[c].start;
+                    cols_x[c].start = (int32_t)t.size();
+                    for (int q = 0; q < cols[c].rows; ++q) t.push_back(tab[(size_t)src + q]);
+                }
+            }
+    }
+    build_hybrid(t, hyb, vec_off);
 }
 
 // What build_context hands nyx_hip_ctx_create: rc != NYX_HIP_RC_OK and `error`, or everything below.
