@@ -255,15 +255,20 @@ typedef struct nyx_hip_tuning {
                                 * since round 5: its runs placed in a free wave order); 0x100000 no mailbox pool (allocate and free per context);
                                 * 0x4000 full-range sincos for a polynomial IAU orientation every stage (results differ by the rounding of the large
                                 * argument).  nyx_hip_ctx_create refuses any other bit with NYX_HIP_RC_BAD_ARG. */
-    double coop_fraction;      /* 0 auto: share of the harmonics terms a helper takes */
+    double coop_fraction;     /* 0 auto: share of the harmonics terms a helper takes */
     double coop_helper_ratio;  /* 0 auto: helper workgroups per trajectory-owning workgroup */
     double column_start_cost;  /* < 0 auto: rows a column's start is charged in the schedule */
     double role_duties[3];     /* all 0: model.  Integrator, almanac, perturbation duty in harmonics-term units */
     double age_weights[4];     /* NYX_HIP_SCHED_EXPLICIT, all 0: unused.  One speed weight per SIMD age class */
     double wave_weights[16];   /* NYX_HIP_SCHED_EXPLICIT: per-wave speed weights (all 0: age_weights) */
+    /* (added behind every field of the first ABI v4 layout: none of those moves) */
+    int32_t helper_resident;   /* -1 auto, 0 off, 1 on: the helper workgroups of the plain sixteen-wave kernel keep the table rows of their
+                                * columns in LDS for the whole launch where they fit (80 KB) and walk them from there; elsewhere, and
+                                * with 0, they walk with the feed `harmonics_feed` gives them.  The same bits either way. */
+    int32_t reserved_;         /* 0 */
 } nyx_hip_tuning_t;
 /* all "auto" */
-#define NYX_HIP_TUNING_DEFAULT {0, 0, -1, -1, -1, -1, -1, 0, -1, -1, 0, 0, 0, 0, 0.0, 0.0, -1.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0}}
+#define NYX_HIP_TUNING_DEFAULT {0, 0, -1, -1, -1, -1, -1, 0, -1, -1, 0, 0, 0, 0, 0.0, 0.0, -1.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0}, -1, 0}
 
 /* PropagatorConfig{dynamics, method, options}: dynamics/sequence/config.rs:96-169.
  * Model order is the reference's `Dynamics::build` order: two-body, point

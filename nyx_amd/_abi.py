@@ -154,12 +154,13 @@ class Tuning(C.Structure):
         ("profile", C.c_int32), ("debug_flags", C.c_int32),
         ("coop_fraction", C.c_double), ("coop_helper_ratio", C.c_double), ("column_start_cost", C.c_double),
         ("role_duties", C.c_double * 3), ("age_weights", C.c_double * 4), ("wave_weights", C.c_double * 16),
+        ("helper_resident", C.c_int32), ("reserved_", C.c_int32),
     ]
 
     def __init__(self, **kw):
         super().__init__()
         self.cooperative = self.pipelined = self.chained_attempts = self.epoch_data_reuse = self.role_fanout = -1
-        self.stm_quad = self.harmonics_feed = -1
+        self.stm_quad = self.harmonics_feed = self.helper_resident = -1
         self.column_start_cost = -1.0
         for k, v in kw.items():
             if k in ("role_duties", "age_weights", "wave_weights"):
@@ -692,6 +693,9 @@ def load_library():
     lib.nyx_hip_ctx_set_column_waves.restype = C.c_int32
     lib.nyx_hip_last_coop_helpers.argtypes = [C.c_void_p]
     lib.nyx_hip_last_coop_helpers.restype = C.c_int32
+    # (introspection beside it, not an entry of nyx_hip.h: which feed the helpers of the last launch walked with)
+    lib.nyx_hip_debug_helper_feed.argtypes = [C.c_void_p]
+    lib.nyx_hip_debug_helper_feed.restype = C.c_int32
     lib.nyx_hip_last_kernel_ms.argtypes = [C.c_void_p]
     lib.nyx_hip_last_kernel_ms.restype = C.c_double
     lib.nyx_hip_last_error.restype = C.c_char_p

@@ -190,6 +190,7 @@ struct nyx_hip_ctx {
     int64_t coop_cap = 0;
     int n_cu = 0;
     int last_coop_helpers = 0;  // helpers of the last launch (0 = solo)
+    int last_helper_feed = -1;  // what their column waves walked with: 0 scalar, 1 streamed, 2 resident in LDS (-1 = no helpers)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_ms = -1.0;
     // Concurrency contract (nyx_hip.h): every entry point locks `mu`, so host threads may share a context; on the DEVICE the
@@ -332,6 +333,7 @@ static nyx_hip_tuning_t resolve_tuning(const nyx_hip_tuning_t *t) {
     geti("NYX_HIP_STM_QUAD", r.stm_quad);
     geti("NYX_HIP_HARM_FEED", r.harmonics_feed);
     geti("NYX_HIP_COOP_COLS", r.coop_max_columns);
+    geti("NYX_HIP_HELPER_RESIDENT", r.helper_resident);
     if (std::getenv("NYX_HIP_COOP_MUTE")) r.coop_mute = 1;
     if (std::getenv("NYX_HIP_PROFILE")) r.profile = 1;
     geti("NYX_HIP_DEBUG", r.debug_flags);
@@ -362,6 +364,10 @@ extern "C" int32_t nyx_hip_ctx_set_column_waves(nyx_hip_ctx *ctx, int32_t waves)
 }
 
 extern "C" int32_t nyx_hip_last_coop_helpers(nyx_hip_ctx *ctx) { return ctx ? ctx->last_coop_helpers : 0; }
+
+// Introspection (tests, tools): the feed of the helpers' column walk in the last launch - 0 scalar, 1 streamed, 2 resident in LDS;
+// -1 when it had no helpers.
+extern "C" int32_t nyx_hip_debug_helper_feed(nyx_hip_ctx *ctx) { return ctx ? ctx->last_helper_feed : -1; }
 
 // The first `count` column weights of the last launch's workgroup shape (WeightMap), then the spread (max - min) / mean of the
 // per-wave windows measured when they were calibrated (-1 = structural default weights, never calibrated).
@@ -644,8 +650,9 @@ static int bind_textbook_history(nyx_hip_ctx *ctx, int64_t n, DevBatch &bt) {
 // Cooperative mode (plan.coop): helper workgroups on the idle CUs take over a share of the harmonics columns
 // (propagate_kernel.hip).  Owners and helpers that talk to each other get block indices that agree modulo 8 (round-robin XCD
 // dispatch: same L2).  Their mailboxes: borrowed from the pool, grown, cleared and bound (mailbox_block).
-static int bind_mailboxes(nyx_hip_ctx *ctx, const CoopPlan &cp, DevBatch &bt, hipStream_t stream) {
+static int bind_mailboxes(nyx_hip_ctx *ctx, const CoopPlan &cp, int32_t staged_groups, DevBatch &bt, hipStream_t stream) {
     ctx->last_coop_helpers = 0;
+    ctx->last_helper_feed = -1;
     if (!cp.run) return NYX_HIP_RC_OK;
     const bool pooled = !(ctx->tune.debug_flags & 0x100000);
     if (ctx->coop_cap < cp.boxes || ctx->coop_cap < cp.answers) {
@@ -678,6 +685,9 @@ static int bind_mailboxes(nyx_hip_ctx *ctx, const CoopPlan &cp, DevBatch &bt, hi
     bt.coop_parts = cp.parts;
     bt.coop_mute = ctx->tune.coop_mute ? 1 : 0;  // (bit 1, the retired speculative fetch of helper_body, stays clear)
     ctx->last_coop_helpers = (int)cp.helpers;
+    // the resident feed: this launch's LDS holds the staged rows behind the helper's carve (select_helper_feed said that they fit)
+    bt.coop_stage = (int32_t)helper_stage_bytes(staged_groups);
+    ctx->last_helper_feed = staged_groups > 0 ? 2 : ((ctx->host_cfg.harm_feed & 2) ? 1 : 0);
     return NYX_HIP_RC_OK;
 }
 
@@ -685,9 +695,10 @@ static int bind_mailboxes(nyx_hip_ctx *ctx, const CoopPlan &cp, DevBatch &bt, hi
 // (DevCfg.rs_*, build_run_stream); rebuilt and uploaded when the schedules have changed.
 static int upload_run_streams(nyx_hip_ctx *ctx, hipStream_t stream) {
     DevCfg &dc = ctx->host_cfg;
-    if (ctx->h_tab.empty() || dc.harm_feed == 0 || (dc.flags & NYX_HIP_FLAG_STM) || !ctx->rs_dirty) return NYX_HIP_RC_OK;
+    if (ctx->h_tab.empty() || (dc.harm_feed == 0 && dc.hres_groups == 0) || (dc.flags & NYX_HIP_FLAG_STM) || !ctx->rs_dirty) return NYX_HIP_RC_OK;
     for (int k = 0; k < 3; ++k) {
-        const bool used = k == 0 ? (dc.harm_feed & 1) != 0 : (dc.coop_ok != 0 && (k == 1 ? (dc.harm_feed & 1) != 0 : (dc.harm_feed & 2) != 0));
+        // (the helpers' stream: walked from global memory by the streamed feed, staged from it by the resident one)
+        const bool used = k == 0 ? (dc.harm_feed & 1) != 0 : (dc.coop_ok != 0 && (k == 1 ? (dc.harm_feed & 1) != 0 : ((dc.harm_feed & 2) != 0 || dc.hres_groups > 0)));
         dc.rs_hyb[k] = 0;
         if (!used) continue;
         std::vector<double> &rs = ctx->h_rs[k];
@@ -744,8 +755,11 @@ static int launch_here(nyx_hip_ctx *ctx, const LaunchReq &r) {
     BoundBatch b = bind_batch(r, (ctx->host_cfg.flags & NYX_HIP_FLAG_STM) != 0, ctx->fused_pred);
     if (b.rc != NYX_HIP_RC_OK) { nyx_set_error("%s", b.error); return b.rc; }
     if (int rc = bind_textbook_history(ctx, in->n, b.bt)) return rc;
-    if (int rc = bind_mailboxes(ctx, plan.coop, b.bt, stream)) return rc;
+    if (int rc = bind_mailboxes(ctx, plan.coop, plan.staged_groups, b.bt, stream)) return rc;
     if (int rc = upload_run_streams(ctx, stream)) return rc;
+    // (what helper_body checks before it walks from LDS, checked here too: the report says what ran, not what was planned)
+    if (ctx->last_helper_feed == 2 && !(ctx->host_cfg.rs_hyb[2] != 0 && ctx->host_cfg.hres_groups == plan.staged_groups && b.bt.coop_stage >= helper_stage_bytes(ctx->host_cfg.hres_groups)))
+        ctx->last_helper_feed = (ctx->host_cfg.harm_feed & 2) ? 1 : 0;
     // the column weights of this launch's workgroup shape: measured once per context (see calibrate())
     const WKey key = weight_key(ctx->host_cfg, plan.n_waves, plan.quad, b.bt.coop_helpers > 0);
     ctx->last_key = key;

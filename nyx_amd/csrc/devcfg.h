@@ -94,7 +94,11 @@ struct DevCfg {
     double phi, c_m_s;
 
     int32_t has_grav, deg, ord, n_cols; /* columns 1..n_cols (= deg+1) */
-    int32_t g_slot, _pad_g;             /* >= 0: the field belongs to the body of that slot, not to the integration centre (evaluated at r - r_body) */
+    int32_t g_slot, hres_groups;        /* g_slot >= 0: the field belongs to the body of that slot, not to the integration centre (evaluated at r - r_body) */
+    /* hres_groups (in the word that padded g_slot: the descriptor keeps its size) - resident feed of the helpers (claim mode of the plain
+     * sixteen-wave kernel; launch_plan.h, select_helper_feed): > 0 = the sixteen-row groups of rs_hyb_v[2] a helper workgroup copies into
+     * LDS behind its carve (DEV_HELPER_LDS_BYTES) once per launch and walks from there; 0 = the helpers walk with the feed harm_feed
+     * bit 1 names.  The owner's fallback never uses it. */
     double g_mu, g_re, g_inv_re;
     DevRot g_rot;
     /* second gravity field (nyx_hip_config_t.gravity2): walked in one piece by the perturbation wave with the point-mass share, its own
@@ -149,6 +153,14 @@ struct DevCfg {
      * the stream. */
     uint64_t rs_hyb[3], rs_hyb_v[3], rs_cols[3];
 };
+
+/* LDS of a helper workgroup (pk_cooperative.h, helper_body): DEV_HELPER_SLOTS jobs in flight, each with the partial sums of sixteen
+ * wave slots and the five input rows, then the control words.  The staged rows of the resident feed lie behind it. */
+#define DEV_HELPER_SLOTS 2
+#define DEV_HELPER_LDS_BYTES ((DEV_HELPER_SLOTS * DEV_MAX_WAVES * 4 * DEV_LANES + DEV_HELPER_SLOTS * 5 * DEV_LANES) * 8 + 64 * 4)
+/* What the staged block may take.  A cooperative launch is sized by its owners (~150 KB of LDS, one workgroup per CU) and a helper's
+ * carve is 70 KB of that: a block of up to 80 KB lies in LDS the launch holds anyway, so nothing about residency changes. */
+#define DEV_HELPER_STAGE_MAX (80 * 1024)
 
 /* Column header (32 B = one s_load_dwordx8): rows of column c start at htab[start]: `nb & 0xffff` batches of HARM_BATCH
  * entries, then `nb >> 16` (< HARM_BATCH) single rows; the recursion is seeded with a2 = diag / rho, a1 = 0. */
@@ -230,7 +242,7 @@ struct DevBatch { /* device pointers of one launch */
     int32_t coop_helpers, coop_base;
     int32_t lds_bytes, coop_parts; /* dynamic LDS of the launch: zeroed by every workgroup before use (see propagate_body); coop_parts: sub-jobs per evaluation (1 or 2) */
     int32_t coop_mute, coop_sets; /* coop_sets: owners are dealt into this many sets of <= 16, each watched by its own helpers */ /* test switch (NYX_HIP_COOP_MUTE): helpers exit at once, as if they had never become resident */
-    int32_t coop_fan, _pad_fan; /* 1: fan-out mode - helper h is DEDICATED to owner h % owners, part h / owners of coop_parts (no claims); answers of the parts
+    int32_t coop_fan, coop_stage; /* coop_stage: bytes of table rows a helper stages in LDS behind its carve (resident feed, DevCfg.hres_groups; 0 = none) */ /* 1: fan-out mode - helper h is DEDICATED to owner h % owners, part h / owners of coop_parts (no claims); answers of the parts
                                  * 1.. go to coop_out2[owner * coop_parts + part], the part-0 helper adds them to its own and answers the owner's mailbox */
     struct CoopBox *coop_box; /* one mailbox per trajectory-owning workgroup, zeroed before the launch */
     struct CoopOut *coop_out2; /* [owners] answers of part 1 (coop_parts == 2), else NULL */

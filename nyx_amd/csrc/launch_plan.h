@@ -766,12 +766,56 @@ inline CoopPlan plan_cooperation(const PlanInputs &in, DevCfg &dc, int64_t n, in
     return cp;
 }
 
+// Sixteen-row groups of the run stream of the schedules `ids` (ctx_build.h, build_run_stream, lays out exactly these): every range of
+// every wave starts a group of its own, a column's rows go in once, and the walk's look-ahead adds two groups behind the last row.
+inline int64_t run_stream_groups(const DevSched *sched, std::initializer_list<int> ids, const std::vector<int32_t> &col_len) {
+    int64_t rows = 0;
+    std::vector<char> seen(col_len.size(), 0);
+    for (int k : ids)
+        for (int w = 0; w < DEV_MAX_WAVES; ++w)
+            for (int r = 0; r < sched[k].n_ranges[w]; ++r) {
+                rows = (rows + 15) / 16 * 16;
+                for (int c = sched[k].range_c0[w][r]; c < sched[k].range_c0[w][r] + sched[k].range_cnt[w][r]; ++c) {
+                    if (c < 1 || c >= (int)col_len.size() || seen[c]) continue;
+                    seen[c] = 1;
+                    rows += col_len[c];
+                }
+            }
+    return (rows + 15) / 16 + 2;
+}
+// The staged block of the helpers' resident feed: {t3..t6} of every group (HYB_GROUP doubles), behind the helper's carve.
+inline int64_t helper_stage_bytes(int64_t groups) { return groups * HYB_GROUP * (int64_t)sizeof(double); }
+inline bool helper_stage_fits(int64_t groups) { return groups > 0 && helper_stage_bytes(groups) <= DEV_HELPER_STAGE_MAX; }
+
+// The feed of the helpers' column walk in this launch (DevCfg.hres_groups): resident in LDS for the claim-mode helpers of the plain
+// sixteen-wave kernel with a one-part hand-off, where the rows of the helper schedule fit (helper_stage_fits) and
+// tuning.helper_resident does not say no; the feed of DevCfg.harm_feed everywhere else (two-part hand-offs and the fan-out kernel
+// keep theirs).  The same rows through the same operations: the selection moves no bit.  True when dc changed (upload it, and the
+// helpers' run stream with it).
+inline bool select_helper_feed(const PlanInputs &in, DevCfg &dc, const CoopPlan &cp, int32_t &staged) {
+    staged = 0;
+    // Only a launch with one-part claim-mode helpers reads dc.hres_groups (its kernel alone carries the resident walk, and the launch's
+    // own DevBatch.coop_stage gates it): every other launch leaves the word as it is, so a context that alternates between a
+    // cooperative launch and one that works alone rebuilds and uploads nothing for the feed's sake.
+    if (!(cp.run && !cp.fan && cp.parts == 1 && dc.n_waves == DEV_MAX_WAVES && !(dc.flags & NYX_HIP_FLAG_STM))) return false;
+    int32_t groups = 0;
+    if (in.tune.helper_resident != 0) {
+        const int64_t g = run_stream_groups(dc.sched, {DEV_SCHED_HELPER, DEV_SCHED_HELPER2}, in.col_len);
+        if (helper_stage_fits(g)) groups = (int32_t)g;
+    }
+    staged = groups;
+    if (groups == dc.hres_groups) return false;
+    dc.hres_groups = groups;
+    return true;
+}
+
 // The launch-shape dependent part of a launch of n trajectories: waves per workgroup, STM layout, schedules (rebuilt when the shape
 // differs from `shape`, or when `stale`: weights or tuning changed since they were built) and the cooperative mode.
 struct LaunchPlan {
     int n_waves = 0;
     bool quad = false;
     bool rebuilt = false;  // the schedules in the DevCfg changed (upload it; rebuild the run streams)
+    int32_t staged_groups = 0;  // sixteen-row groups the helpers of THIS launch stage in LDS (select_helper_feed; 0 = none)
     CoopPlan coop;
 };
 inline LaunchPlan plan_launch(const PlanInputs &in, DevCfg &dc, SchedShape &shape, int64_t n, bool stale) {
@@ -784,6 +828,7 @@ inline LaunchPlan plan_launch(const PlanInputs &in, DevCfg &dc, SchedShape &shap
         p.rebuilt = true;
     }
     p.coop = plan_cooperation(in, dc, n, p.n_waves, shape, p.rebuilt);
+    if (select_helper_feed(in, dc, p.coop, p.staged_groups)) p.rebuilt = true;
     return p;
 }
 

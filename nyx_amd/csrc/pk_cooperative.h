@@ -209,8 +209,9 @@ static __device__ __attribute__((noinline)) Partial4 coop_fallback(uint64_t cfg_
 // round trips); more slots do move the claim under the arithmetic - and lose, 84.9 -> 92.3 -> 103.3 ms per 3 h of configs[1]:
 // a job claimed early queues INSIDE this helper behind two or three others while another helper would have been free sooner
 // (lost claims per job 2.4 -> 2.6 -> 4.0): the rate of jobs is the owners', what counts is each job's turnaround.
-constexpr int HELPER_SLOTS = 2;
-constexpr size_t HELPER_LDS_BYTES = (HELPER_SLOTS * DEV_MAX_WAVES * 4 * DEV_LANES + HELPER_SLOTS * 5 * DEV_LANES) * 8 + 64 * 4;
+constexpr int HELPER_SLOTS = DEV_HELPER_SLOTS;
+constexpr size_t HELPER_LDS_BYTES = DEV_HELPER_LDS_BYTES;  // (devcfg.h: the host sizes the staged rows of the resident feed behind it)
+static_assert(HELPER_LDS_BYTES % 128 == 0, "the staged groups behind the carve are read as 128-byte lines");
 DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols, char *smem, int lane, int wave) {
     constexpr int NS = HELPER_SLOTS;
     double *part = (double *)smem;                                  // [NS][16][4][64]
@@ -221,6 +222,12 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
     constexpr int parts = COOP_PARTS_HERE;
     const int answer_wave = (int)(blockDim.x / DEV_LANES) - 1;
     const int n_col_waves = answer_wave - 1;
+#if NYX_HELPER_RESIDENT
+    // resident feed (DevCfg.hres_groups > 0, set by the host where the block fits: launch_plan.h, select_helper_feed): the rows of this
+    // workgroup's schedules go into LDS behind the carve above, once per launch
+    const bool resident = cfg->hres_groups > 0 && cfg->rs_hyb[2] != 0 && bt.coop_stage >= cfg->hres_groups * (HYB_GROUP * 8);  // (the stream is there and the launch holds the room)
+    if (resident) helper_stage_rows(cfg, (double *)(smem + HELPER_LDS_BYTES));
+#endif
     if (wave == 0 || wave == answer_wave) {
         if (wave == 0 && lane < 32) ctl[lane] = 0;
 #pragma unroll
@@ -440,8 +447,14 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
 #else
             const int hsched = sub ? DEV_SCHED_HELPER2 : DEV_SCHED_HELPER;
 #endif
+#if NYX_HELPER_RESIDENT
+            const Partial4 pr = resident ? harmonics_resident((uint64_t)cfg, wave, hsched, (unsigned)(size_t)(LdsCPtr)(const double *)(smem + HELPER_LDS_BYTES), v0, v1, v2, v3, v4)
+                              : (cfg->harm_feed & 2) ? harmonics_stream((uint64_t)cfg, (uint64_t)cols, wave, hsched, v0, v1, v2, v3, v4)
+                                               : harmonics_partial((uint64_t)cfg, (uint64_t)htab, (uint64_t)cols, wave, hsched, v0, v1, v2, v3, v4);
+#else
             const Partial4 pr = (cfg->harm_feed & 2) ? harmonics_stream((uint64_t)cfg, (uint64_t)cols, wave, hsched, v0, v1, v2, v3, v4)
                                                : harmonics_partial((uint64_t)cfg, (uint64_t)htab, (uint64_t)cols, wave, hsched, v0, v1, v2, v3, v4);
+#endif
             double *pp = ps + wave * 4 * DEV_LANES;
             pp[0 * DEV_LANES + lane] = pr.x; pp[1 * DEV_LANES + lane] = pr.y; pp[2 * DEV_LANES + lane] = pr.z; pp[3 * DEV_LANES + lane] = pr.w;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -534,6 +547,10 @@ DEVFN void helper_body(const DevBatch &bt, CfgPtr cfg, HarmPtr htab, ColPtr cols
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (lane == 0) answered[s] = j + 1;  // the slot may be refilled: its partial sums are in registers
         if (lane == 0 && bt.prof != nullptr) atomicAdd((unsigned long long *)bt.prof + 16 * 8 + 4, 1ull);
+#if NYX_HELPER_RESIDENT
+        // [16][6]: the jobs among them whose columns were walked from LDS - the device's own word on which feed ran (tests/test_gpu_helper_resident.py)
+        if (resident && lane == 0 && bt.prof != nullptr) atomicAdd((unsigned long long *)bt.prof + 16 * 8 + 6, 1ull);
+#endif
         if (hprof) { hp_busy += (int64_t)__builtin_readcyclecounter() - hp_c0; ++hp_jobs; }
     }
     if (hprof && lane == 0) {

@@ -477,6 +477,54 @@ static __device__ __attribute__((noinline)) Partial4 harmonics_stream(uint64_t c
     return r;
 }
 
+#if NYX_HELPER_RESIDENT
+// Resident feed of a helper workgroup (DevCfg.hres_groups > 0): the helpers' run stream is the same in every job of a launch, so the
+// vector side of it - t3..t6, 512 bytes per sixteen-row group - is copied into LDS once per launch (helper_stage_rows) and the walk
+// reads its groups from there: one ds_read_b64 at (lane & 15) * 8 fills the register pair row_newbcast picks from, as the coalesced
+// global load of the streamed walk does.  {g, t1, t2} stay on the scalar path, 24 bytes per row.  The generated loop is
+// harmonics_stream's with the group loads exchanged (tools/gen_harm_stream.py, HARM_RESIDENT_ASM): the same nine f64 operations per
+// row on the same operands in the same order - bit-identical to both other feeds.  `lds_v`: LDS byte address of the staged block.
+// Out of line and on its own, like harmonics_stream: only helper_body calls it.
+#include "harm_resident_asm.h"
+static __device__ __attribute__((noinline)) Partial4 harmonics_resident(uint64_t cfg_u, int wave_v, int sched_v, unsigned lds_v, double zr, double zi,
+                                                                      double rho_u, double rho, double inv_rho) {
+    CfgPtr cfg = (CfgPtr)uniform_u64(cfg_u);
+    const int wave = __builtin_amdgcn_readfirstlane(wave_v);
+    const int sched = __builtin_amdgcn_readfirstlane(sched_v);
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    double px = 0.0, py = 0.0, pz = 0.0, pw = 0.0;
+    const double rho2 = rho * rho;
+    const CAS DevSched &sd = cfg->sched[sched];
+    const int nr = sd.n_ranges[wave];
+    const uint64_t hs0 = cfg->rs_hyb[2];          // the helpers' run stream: scalar side ...
+    ColPtr cols = (ColPtr)cfg->rs_cols[2];        // ... and the column headers that point into it
+    const unsigned voff = lds_v + (unsigned)(lane & 15) * 8u;
+    for (int q = 0; q < nr; ++q) {
+        const int c0 = sd.range_c0[wave][q];
+        int cols_left = sd.range_cnt[wave][q];
+        const int srow = cols[c0].start;
+        const uint64_t e = hs0 + (uint64_t)(srow & ~7) * (HYB_KS * 8);
+        unsigned va = voff + (unsigned)(srow >> 4) * (HYB_GROUP * 8);
+        const uint64_t hp = (uint64_t)cols + (uint64_t)c0 * sizeof(ColHdr);
+        double rc, ic;
+        cpow_uniform(zr, zi, c0 - 1, rc, ic);
+        int left = srow & 7, first = 1, sink;
+        const int low_half = (srow & 8) == 0 ? 1 : 0;
+        HARM_RESIDENT_ASM(e, va, hp, left, cols_left, first, low_half, sink, rho_u, rho2, rho, inv_rho, zr, zi, px, py, pz, pw, rc, ic);
+        (void)sink; (void)va;
+    }
+    Partial4 r = {px, py, pz, pw};
+    return r;
+}
+// The staging: every thread of the helper workgroup copies its share of the `groups` sixteen-row groups (64 doubles each) from the
+// vector side of the helpers' run stream to `dst`, before the workgroup's first barrier.
+DEVFN void helper_stage_rows(CfgPtr cfg, double *dst) {
+    const double *src = (const double *)cfg->rs_hyb_v[2];
+    const int nd = cfg->hres_groups * HYB_GROUP;
+    for (int q = (int)threadIdx.x; q < nd; q += (int)blockDim.x) dst[q] = src[q];
+}
+#endif  // NYX_HELPER_RESIDENT
+
 static __device__ __attribute__((noinline)) Partial4 harmonics_partial(uint64_t cfg_u, uint64_t htab_u, uint64_t cols_u, int wave_v,
                                                                      int sched_v, double zr, double zi, double rho_u, double rho,
                                                                      double inv_rho) {

@@ -72,6 +72,14 @@
 #else
 #define COOP_PARTS_HERE 1
 #endif
+// Likewise the resident feed of the helpers' column walk (pk_harmonics.h, harmonics_resident; pk_cooperative.h, helper_body): the host
+// selects it for the one-part claim mode of the plain sixteen-wave kernel only (launch_plan.h, select_helper_feed), and only that
+// kernel carries its code - the two-part, fan-out and small-shape kernels keep the text they had.
+#if (NYX_EMIT & NYX_EMIT_PLAIN16) && !defined(NYX_COOP_TWO_PARTS) && !defined(NYX_COOP_FAN)
+#define NYX_HELPER_RESIDENT 1
+#else
+#define NYX_HELPER_RESIDENT 0
+#endif
 
 #define CAS __attribute__((address_space(4)))
 typedef const CAS DevCfg *CfgPtr;
@@ -1574,7 +1582,8 @@ extern "C" hipError_t nyx_launch_propagate(const DevBatch &bt, const DevCfg *cfg
     }
     const bool stm = bt.o_stm != nullptr;
     size_t lds = nyx_kernel_lds_bytes(n_waves, rec_lds_doubles, stm ? (quad ? 2 : 1) : 0, stm ? 0 : reuse_fields);
-    if (!stm && bt.coop_helpers > 0 && lds < (size_t)HELPER_LDS_BYTES) lds = HELPER_LDS_BYTES;
+    // (a helper's carve, and behind it the rows the resident feed stages: at most DEV_HELPER_STAGE_MAX, select_helper_feed)
+    if (!stm && bt.coop_helpers > 0 && lds < (size_t)HELPER_LDS_BYTES + (size_t)bt.coop_stage) lds = HELPER_LDS_BYTES + (size_t)bt.coop_stage;
     DevBatch btl = bt;
     btl.lds_bytes = (int32_t)lds;
     const bool small = n_waves <= 8;  // (helpers are sixteen-wave workgroups: cooperative launches never are)

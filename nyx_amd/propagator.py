@@ -734,6 +734,11 @@ class GpuContext:
         """Helper workgroups of the last launch (0 = no cooperative mode)."""
         return int(self._lib.nyx_hip_last_coop_helpers(self._h))
 
+    def last_helper_feed(self) -> int:
+        """How the helper workgroups of the last launch walked their columns: 0 = scalar feed, 1 = streamed feed, 2 = table rows
+        resident in LDS (``Tuning.helper_resident``); -1 = the launch had no helpers."""
+        return int(self._lib.nyx_hip_debug_helper_feed(self._h))
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.nyx_hip_last_kernel_ms(self._h))
 

@@ -15,11 +15,26 @@ Register plan (all hard-coded ones are declared as clobbers; caller-saved VGPR r
   s[40:87]   one scalar batch: 8 rows x {g, t1, t2}
   s[88:89] return address of the boundary code, s[90:91] c sqrt2 of the current column, s[92:99] header of the NEXT column
   s[100:101] scalar-side pointer, s[36:37] vector-side pointer, s[38:39] header pointer
+
+Two variants of the same loop are written, HARM_STREAM_ASM (harm_stream_asm.h) and HARM_RESIDENT_ASM (harm_resident_asm.h, a header of
+its own: the owners' translation units keep the text they had); per row both issue the same nine f64
+instructions on the same operands in the same order.  They differ in where a sixteen-row group of {t3..t6} comes from:
+  HARM_STREAM_ASM    four global_load_dwordx2 off s[36:37], retired by `s_waitcnt vmcnt(4)` in front of the rows that read them
+  HARM_RESIDENT_ASM  four ds_read_b64 off the VGPR %[va] (an LDS byte address, advanced by 512 per group): the helpers' rows, staged
+                     in LDS once per launch (helper_body)
+Wait rule of the resident variant.  The registers a v_fmac_f64_dpp picks from are now written by LDS loads, which count on lgkmcnt
+together with the scalar loads of the batch, and scalar loads return out of order: no lgkmcnt(n > 0) says anything about a ds_read.
+So every group load is issued IN FRONT of a scalar batch load, whose `s_waitcnt lgkmcnt(0)` retires it with the batch - always before
+the first row that reads the group, and never with a touch of the next batch in flight (those are issued behind that wait).  Nothing
+stands where the vmcnt waits stood.  The DPP hazards proper (two wait states after a VALU write of the picked register, five after a
+VALU write of EXEC) cannot arise: the picked registers are written by loads only and EXEC is never written
+(tools/check_dpp_hazards.py scans the code object).
 """
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "nyx_amd", "csrc", "harm_stream_asm.h")
+OUT_RESIDENT = os.path.join(ROOT, "nyx_amd", "csrc", "harm_resident_asm.h")
 
 X, Y, T, U, W = "v[48:49]", "v[50:51]", "v[52:53]", "v[54:55]", "v[84:85]"
 S = ["v[64:65]", "v[66:67]", "v[68:69]", "v[70:71]", "v[80:81]", "v[82:83]"]
@@ -31,6 +46,7 @@ BATCH0 = 40
 DPP = "row_mask:0xf bank_mask:0xf"
 
 lines = []
+RESIDENT = False  # which variant emit() is writing
 
 
 def emit(s):
@@ -43,9 +59,19 @@ def add64(reg_lo, reg_hi, imm):
 
 
 def prefetch(regs):
+    if RESIDENT:
+        for j, r in enumerate(regs):
+            emit(f"ds_read_b64 {r}, %[va] offset:{128 * j}")
+        emit("v_add_u32 %[va], 0x200, %[va]")
+        return
     for j, r in enumerate(regs):
         emit(f"global_load_dwordx2 {r}, %[voff], {VP} offset:{128 * j}")
     add64("s36", "s37", 512)
+
+
+def group_wait():
+    if not RESIDENT:  # (resident: retired by the lgkmcnt(0) of the batch load in front, see the header)
+        emit("s_waitcnt vmcnt(4)")
 
 
 def batch_load():
@@ -91,98 +117,126 @@ def stub(k):
     emit(f"s_branch .Lhs_cont{k}_%=")
 
 
-# ---- prologue
-emit(f"s_mov_b64 {EP}, %[e]")
-emit(f"s_mov_b64 {VP}, %[vp]")
-emit(f"s_mov_b64 {HP}, %[hp]")
-emit(f"s_load_dwordx8 s[92:99], {HP}, 0x0")
-add64("s38", "s39", 32)
-prefetch(A)
-for r in [X, Y] + S:
-    emit(f"v_mov_b64 {r}, 0")
-prefetch(B)
-emit("s_cmp_eq_u32 %[low_half], 0")
-emit("s_cbranch_scc1 .Lhs_half_%=")
-emit(".Lhs_top_%=:")
-batch_load()
-emit("s_waitcnt vmcnt(4)")
-for k in range(0, 8):
-    row(k, A)
-emit(".Lhs_half_%=:")
-batch_load()
-emit("s_waitcnt vmcnt(4)")
-for k in range(8, 16):
-    row(k, A)
-prefetch(A)
-batch_load()
-emit("s_waitcnt vmcnt(4)")
-for k in range(16, 24):
-    row(k, B)
-batch_load()
-for k in range(24, 32):
-    row(k, B)
-prefetch(B)
-emit("s_branch .Lhs_top_%=")
-# ---- out of line
-for k in range(32):
-    stub(k)
-emit(".Lhs_boundary_%=:")
-emit("s_cmp_eq_u32 %[first], 0")
-emit("s_cbranch_scc0 .Lhs_nofold_%=")
-emit(f"v_mul_f64 {T}, %[rho], {CSC}")           # rho * c * sqrt(2)
-emit(f"v_mul_f64 {U}, %[ic], {S[1]}")
-emit(f"v_fmac_f64 {U}, %[rc], {S[0]}")
-emit(f"v_fmac_f64 %[px], {T}, {U}")
-emit(f"v_mul_f64 {U}, %[ic], -{S[0]}")
-emit(f"v_fmac_f64 {U}, %[rc], {S[1]}")
-emit(f"v_fmac_f64 %[py], {T}, {U}")
-emit(f"v_mul_f64 {U}, %[ic], {S[3]}")
-emit(f"v_fmac_f64 {U}, %[rc], {S[2]}")
-emit(f"v_fmac_f64 %[pz], %[rho], {U}")
-emit(f"v_mul_f64 {U}, %[ic], {S[5]}")
-emit(f"v_fmac_f64 {U}, %[rc], {S[4]}")
-emit(f"v_add_f64 %[pw], %[pw], -{U}")
-emit(f"v_mul_f64 {T}, %[rc], %[zr]")            # (rc + i ic) *= (zr + i zi), products and sums unfused as in cpow_uniform's caller
-emit(f"v_mul_f64 {U}, %[ic], %[zi]")
-emit(f"v_add_f64 {T}, {T}, -{U}")
-emit(f"v_mul_f64 {U}, %[rc], %[zi]")
-emit(f"v_mul_f64 {W}, %[ic], %[zr]")
-emit(f"v_add_f64 %[ic], {U}, {W}")
-emit(f"v_mov_b64 %[rc], {T}")
-emit(".Lhs_nofold_%=:")
-emit("s_mov_b32 %[first], 0")
-emit("s_cmp_eq_u32 %[cols_left], 0")
-emit("s_cbranch_scc1 .Lhs_done_%=")
-emit("s_add_i32 %[cols_left], %[cols_left], -1")
-emit("s_waitcnt lgkmcnt(0)")
-emit(f"s_mov_b32 %[left], {HDR_ROWS}")
-emit(f"s_mov_b64 {CSC}, {HDR_SCALE}")
-for r in S:
-    emit(f"v_mov_b64 {r}, 0")
-emit(f"s_setpc_b64 {RET}")
-emit(".Lhs_done_%=:")
-emit("s_waitcnt vmcnt(0) lgkmcnt(0)")
+def loop(resident):
+    """The instructions and labels of one variant."""
+    global RESIDENT
+    RESIDENT = resident
+    del lines[:]
+    # ---- prologue
+    emit(f"s_mov_b64 {EP}, %[e]")
+    if not resident:
+        emit(f"s_mov_b64 {VP}, %[vp]")
+    emit(f"s_mov_b64 {HP}, %[hp]")
+    emit(f"s_load_dwordx8 s[92:99], {HP}, 0x0")
+    add64("s38", "s39", 32)
+    prefetch(A)
+    for r in [X, Y] + S:
+        emit(f"v_mov_b64 {r}, 0")
+    prefetch(B)
+    emit("s_cmp_eq_u32 %[low_half], 0")
+    emit("s_cbranch_scc1 .Lhs_half_%=")
+    emit(".Lhs_top_%=:")
+    batch_load()
+    group_wait()
+    for k in range(0, 8):
+        row(k, A)
+    emit(".Lhs_half_%=:")
+    batch_load()
+    group_wait()
+    for k in range(8, 16):
+        row(k, A)
+    prefetch(A)
+    batch_load()
+    group_wait()
+    for k in range(16, 24):
+        row(k, B)
+    batch_load()
+    for k in range(24, 32):
+        row(k, B)
+    prefetch(B)
+    emit("s_branch .Lhs_top_%=")
+    # ---- out of line
+    for k in range(32):
+        stub(k)
+    emit(".Lhs_boundary_%=:")
+    emit("s_cmp_eq_u32 %[first], 0")
+    emit("s_cbranch_scc0 .Lhs_nofold_%=")
+    emit(f"v_mul_f64 {T}, %[rho], {CSC}")           # rho * c * sqrt(2)
+    emit(f"v_mul_f64 {U}, %[ic], {S[1]}")
+    emit(f"v_fmac_f64 {U}, %[rc], {S[0]}")
+    emit(f"v_fmac_f64 %[px], {T}, {U}")
+    emit(f"v_mul_f64 {U}, %[ic], -{S[0]}")
+    emit(f"v_fmac_f64 {U}, %[rc], {S[1]}")
+    emit(f"v_fmac_f64 %[py], {T}, {U}")
+    emit(f"v_mul_f64 {U}, %[ic], {S[3]}")
+    emit(f"v_fmac_f64 {U}, %[rc], {S[2]}")
+    emit(f"v_fmac_f64 %[pz], %[rho], {U}")
+    emit(f"v_mul_f64 {U}, %[ic], {S[5]}")
+    emit(f"v_fmac_f64 {U}, %[rc], {S[4]}")
+    emit(f"v_add_f64 %[pw], %[pw], -{U}")
+    emit(f"v_mul_f64 {T}, %[rc], %[zr]")            # (rc + i ic) *= (zr + i zi), products and sums unfused as in cpow_uniform's caller
+    emit(f"v_mul_f64 {U}, %[ic], %[zi]")
+    emit(f"v_add_f64 {T}, {T}, -{U}")
+    emit(f"v_mul_f64 {U}, %[rc], %[zi]")
+    emit(f"v_mul_f64 {W}, %[ic], %[zr]")
+    emit(f"v_add_f64 %[ic], {U}, {W}")
+    emit(f"v_mov_b64 %[rc], {T}")
+    emit(".Lhs_nofold_%=:")
+    emit("s_mov_b32 %[first], 0")
+    emit("s_cmp_eq_u32 %[cols_left], 0")
+    emit("s_cbranch_scc1 .Lhs_done_%=")
+    emit("s_add_i32 %[cols_left], %[cols_left], -1")
+    emit("s_waitcnt lgkmcnt(0)")
+    emit(f"s_mov_b32 %[left], {HDR_ROWS}")
+    emit(f"s_mov_b64 {CSC}, {HDR_SCALE}")
+    for r in S:
+        emit(f"v_mov_b64 {r}, 0")
+    emit(f"s_setpc_b64 {RET}")
+    emit(".Lhs_done_%=:")
+    emit("s_waitcnt lgkmcnt(0)" if resident else "s_waitcnt vmcnt(0) lgkmcnt(0)")
+    return list(lines)
+
 
 clob = [f"s{i}" for i in range(36, 102)] + [f"v{i}" for r in ((48, 56), (64, 72), (80, 88), (96, 104), (112, 120)) for i in range(*r)]
 clob += ["vcc", "scc", "memory"]
 
-import io  # noqa: E402
 
-f = io.StringIO()
-f.write("// GENERATED by tools/gen_harm_stream.py - do not edit.  The hybrid-feed walk of one column range (see the generator's header).\n")
-f.write("#define HARM_STREAM_ASM(e, vp, hp, voff, left, cols_left, first, low_half, sink, rho_u, rho2, rho, inv_rho, zr, zi, px, py, pz, pw, rc, ic) \\\n")
-f.write("    asm volatile( \\\n")
-for ln in lines:
-    f.write(f'        "{ln}\\n\\t" \\\n')
-f.write('        : [left] "+s"(left), [cols_left] "+s"(cols_left), [first] "+s"(first), [sink] "=&s"(sink), \\\n')
-f.write('          [px] "+v"(px), [py] "+v"(py), [pz] "+v"(pz), [pw] "+v"(pw), [rc] "+v"(rc), [ic] "+v"(ic) \\\n')
-f.write('        : [e] "s"(e), [vp] "s"(vp), [hp] "s"(hp), [voff] "v"(voff), [low_half] "s"(low_half), \\\n')
-f.write('          [rho_u] "v"(rho_u), [rho2] "v"(rho2), [rho] "v"(rho), [inv_rho] "v"(inv_rho), [zr] "v"(zr), [zi] "v"(zi) \\\n')
-f.write("        : " + ", ".join(f'"{c}"' for c in clob) + ")\n")
-text = f.getvalue()
-# written only when the content changes: the header's mtime is a build dependency of every kernel object (__graft_entry__.build),
-# and tests/test_codegen.py imports this module on every run
-if not os.path.exists(OUT) or open(OUT).read() != text:
-    with open(OUT, "w") as out_f:
-        out_f.write(text)
-print(f"wrote {OUT}: {len(lines)} instructions / labels")
+def header(resident):
+    """The text of one generated header: one macro, one asm statement."""
+    body = loop(resident)
+    t = []
+    if resident:
+        t.append("// GENERATED by tools/gen_harm_stream.py - do not edit.  The walk of one column range off rows resident in LDS (see the generator's header).\n")
+        t.append("#define HARM_RESIDENT_ASM(e, va, hp, left, cols_left, first, low_half, sink, rho_u, rho2, rho, inv_rho, zr, zi, px, py, pz, pw, rc, ic) \\\n")
+    else:
+        t.append("// GENERATED by tools/gen_harm_stream.py - do not edit.  The hybrid-feed walk of one column range (see the generator's header).\n")
+        t.append("#define HARM_STREAM_ASM(e, vp, hp, voff, left, cols_left, first, low_half, sink, rho_u, rho2, rho, inv_rho, zr, zi, px, py, pz, pw, rc, ic) \\\n")
+    t.append("    asm volatile( \\\n")
+    for ln in body:
+        t.append(f'        "{ln}\\n\\t" \\\n')
+    t.append('        : [left] "+s"(left), [cols_left] "+s"(cols_left), [first] "+s"(first), [sink] "=&s"(sink), \\\n')
+    if resident:
+        t.append('          [px] "+v"(px), [py] "+v"(py), [pz] "+v"(pz), [pw] "+v"(pw), [rc] "+v"(rc), [ic] "+v"(ic), [va] "+v"(va) \\\n')
+        t.append('        : [e] "s"(e), [hp] "s"(hp), [low_half] "s"(low_half), \\\n')
+    else:
+        t.append('          [px] "+v"(px), [py] "+v"(py), [pz] "+v"(pz), [pw] "+v"(pw), [rc] "+v"(rc), [ic] "+v"(ic) \\\n')
+        t.append('        : [e] "s"(e), [vp] "s"(vp), [hp] "s"(hp), [voff] "v"(voff), [low_half] "s"(low_half), \\\n')
+    t.append('          [rho_u] "v"(rho_u), [rho2] "v"(rho2), [rho] "v"(rho), [inv_rho] "v"(inv_rho), [zr] "v"(zr), [zi] "v"(zi) \\\n')
+    t.append("        : " + ", ".join(f'"{c}"' for c in clob) + ")\n")
+    return "".join(t), len(body)
+
+
+# written only when the content changes: a header's mtime is a build dependency of every kernel object (__graft_entry__.build),
+# and tests/test_codegen.py imports this module on every run.  Importing writes the streamed header, as it always has; the
+# resident one is written when the generator is run, and tests/test_helper_resident_host.py holds the committed file to header(True).
+def write(path, resident):
+    text, count = header(resident)
+    if not os.path.exists(path) or open(path).read() != text:
+        with open(path, "w") as out_f:
+            out_f.write(text)
+    print(f"wrote {path}: {count} instructions / labels")
+
+
+write(OUT, False)
+if __name__ == "__main__":
+    write(OUT_RESIDENT, True)
